@@ -9,11 +9,16 @@ this rank (inputs resident in HBM), plus -- for N > 1 -- the RCCL gather of the 
 rank 0.  Output arrays are zero-filled once before the timed region, exactly as the reference does
 in initialize_ray_results_m (ray_results_m.f90:154-164), not inside trace_rays.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config configs/....in]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config configs/....in] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 `python bench.py --gpus N` without a launcher (no WORLD_SIZE in the environment) starts its N ranks
 itself -- child processes, spawned before the parent touches a GPU -- and relays rank 0's line.
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs DIR if given and prints the line.
+Everything else the line can carry -- the other numerics flavour, the two-streams passes, the host entry
+(rays_hip_trace), the CPU baseline and, for N > 1, the trace-only / gather-only / sharded-result split --
+takes runs of its own and is measured only with --full.
 
 N > 1 is weak scaling: the fan grows to 256*N x 256 rays over the same launch-angle range and is
 block-partitioned, 65536 contiguous rays per rank (the reference's `schedule(static)`).
@@ -159,13 +164,13 @@ def numerics_text(flavour, is_tol_kernel, ev):
     base = ("tolerance: NOT bit-identical (FMA contraction, re-association, once-refined reciprocals and roots); ray counts / "
             "step indices / stop flags exactly the reference's")
     if ev is None:
-        return base + "; per-step and pointwise deviation of this build not measured (see value_exact for the bit-exact flavour)"
+        return base + "; per-step and pointwise deviation of this build not measured (value_exact, with --full, is the bit-exact flavour)"
     where = " (one-GPU fan of this workload)" if ev.get("fan") else ""
     return (base + f" on all {ev['rays_surveyed']} rays surveyed{where}; restarted from every one of the oracle's {ev['steps_restarted']} "
             f"recorded points, {ev['n_above_1e-10']} steps land further than 1e-10 (relative, norm-wise on r and k) from the "
             f"reference's next point, max {ev['max_per_step']:.2e}; accumulated along the rays the traced fan deviates "
             f"pointwise by up to {ev['max_pointwise']:.1e} ({ev['frac_points_above_1e-10']:.1e} of the points above 1e-10) "
-            "-- numerics_evidence; value_exact is the bit-identical flavour")
+            "-- numerics_evidence; value_exact (with --full) is the bit-identical flavour")
 
 
 def cpu_model():
@@ -239,7 +244,8 @@ def cpu_baseline(cfg_path, budget_s=20.0):
     to the C restatement (kind "port") if the binary is not there."""
     from rays_amd.namelist import read_namelist
 
-    cores = os.cpu_count() or 1
+    omp = os.environ.get("OMP_NUM_THREADS", "").split(",")[0].strip()   # the reference binary's OpenMP obeys it too
+    cores = int(omp) if omp.isdigit() and int(omp) > 0 else (os.cpu_count() or 1)
     ref = os.path.join(ROOT, "oracle", "_ref", "rays_ref_dump")
     text0 = open(cfg_path).read()
     nml = read_namelist(cfg_path)
@@ -337,15 +343,79 @@ def host_entry_time(p, r0, n0, reps=3):
     return dict(ms_per_call=1e3 * best, value=steps / best, kernel=hip.kernel_name(p, len(r0)))
 
 
+DUMP_SEED = 20240917          # the fixed sample of rays --dump-outputs writes when a fan is too large to write whole
+DUMP_PER_RAY_BYTES = 12 << 20  # per-ray arrays (npoints, stop codes, end states): every ray up to this size
+DUMP_TRAJ_BYTES = 28 << 20     # whole trajectories (ray_vec, residual) of a sample of rays within this size
+# (with a float32 <name>_nonfinite.npy beside every array, the worst case stays under 64 MB: 1.5 x (12 + 28) + indices)
+NONFINITE_CODES = {"nan": 1.0, "+inf": 2.0, "-inf": 3.0}
+
+
+def dump_outputs(out_dir, per_ray, trajectories, extra=None):
+    """--dump-outputs DIR: what the timed path computed in its last step, as float64 DIR/<name>.npy (< 64 MB in all).
+
+    per_ray: {name: tensor (nray, ...)} written for every ray while they fit DUMP_PER_RAY_BYTES, else for a fixed,
+    seeded sample of rays; trajectories: {name: tensor (nray, npt, ...)} written for a fixed, seeded sample of rays
+    that fits DUMP_TRAJ_BYTES; extra: {name: tensor} written whole.  The indices of the rays written go to
+    ray_index.npy / trajectory_ray_index.npy, so that two builds compare output for output.
+
+    Every value written is finite.  Where an output holds NaN or +-inf -- end_ray_vec does, as the reference's does:
+    it is the state after the ray's last, unrecorded step, and a ray stopped by check_save for 'infinite_Vg' has
+    stepped into NaN -- the entry is written as 0 and <name>_nonfinite.npy (float32, same shape) carries where and
+    what it was: 0 finite, 1 NaN, 2 +inf, 3 -inf.  That file exists only for an array that has such entries."""
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    nray = len(next(iter(per_ray.values())))
+    rng = np.random.default_rng(DUMP_SEED)
+
+    def sample(bytes_per_ray, budget):
+        k = min(nray, max(1, budget // bytes_per_ray))
+        return np.arange(nray) if k == nray else np.sort(rng.choice(nray, size=k, replace=False))
+
+    def write(name, t, idx=None):
+        if idx is not None:
+            t = t.index_select(0, torch.as_tensor(idx, dtype=torch.int64, device=t.device))
+        a = t.detach().cpu().numpy().astype(np.float64)
+        bad = ~np.isfinite(a)
+        if bad.any():
+            code = np.zeros(a.shape, dtype=np.float32)
+            code[np.isnan(a)] = NONFINITE_CODES["nan"]
+            code[np.isposinf(a)] = NONFINITE_CODES["+inf"]
+            code[np.isneginf(a)] = NONFINITE_CODES["-inf"]
+            np.save(os.path.join(out_dir, name + "_nonfinite.npy"), code)
+            a[bad] = 0.0
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+    width = lambda t: 8 * t[0].numel()
+    sel = sample(sum(width(t) for t in per_ray.values()), DUMP_PER_RAY_BYTES)
+    np.save(os.path.join(out_dir, "ray_index.npy"), sel.astype(np.float64))
+    for name, t in per_ray.items():
+        write(name, t, None if len(sel) == nray else sel)
+    tsel = sample(sum(width(t) for t in trajectories.values()), DUMP_TRAJ_BYTES)
+    np.save(os.path.join(out_dir, "trajectory_ray_index.npy"), tsel.astype(np.float64))
+    for name, t in trajectories.items():
+        write(name, t, tsel)
+    for name, t in (extra or {}).items():
+        write(name, t)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (passes over the fan)")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default=os.path.join(ROOT, "configs", "cfg3b_solovev64k_rk4.in"))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-host-entry", action="store_true", help="skip the host_entry leg (rays_hip_trace on host arrays)")
-    ap.add_argument("--no-pipelined", action="store_true", help="skip the two-streams leg (value_two_streams)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own beyond the headline figure: the other numerics flavour "
+                         "(value_exact), the two-streams passes, host_entry, cpu_baseline and, for N>1, the trace-only / "
+                         "gather-only / sharded-result split; off: the line carries the headline figure alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0's arrays) as DIR/<name>.npy, "
+                         "float64: per-ray arrays of every ray, whole trajectories of a fixed seeded sample of rays (< 64 MB); "
+                         "NaN / inf entries are written as 0 and flagged in DIR/<name>_nonfinite.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the cpu_baseline leg")
+    ap.add_argument("--no-host-entry", action="store_true", help="--full: skip the host_entry leg (rays_hip_trace on host arrays)")
+    ap.add_argument("--no-pipelined", action="store_true", help="--full: skip the two-streams leg (value_two_streams)")
     ap.add_argument("--no-gather", action="store_true", help="N>1: skip the trajectory gather (diagnostic)")
     ap.add_argument("--exchange", choices=("gather", "deposition"), default="gather",
                     help="what leaves the GPUs each pass: the packed trajectories, gathered to rank 0 "
@@ -368,6 +438,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args)   # does not return
 
@@ -383,7 +455,7 @@ def main():
     if world != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}: the launcher must start exactly --gpus ranks")
     if not torch.cuda.is_available():
-        raise SystemExit("bench.py needs a GPU (no CPU fallback)")
+        raise SystemExit("bench.py needs a GPU (no CPU fallback): 0 GPU(s) visible")
     ndev = torch.cuda.device_count()
     if local_rank >= ndev and not os.environ.get("RAYS_BENCH_SHARE_GPU"):
         raise SystemExit(f"local rank {local_rank} has no GPU ({ndev} visible)")
@@ -489,7 +561,20 @@ def main():
     # ---- THE timed region of the contract: exactly K steps (trace + this pass's exchange) -------------------
     elapsed, kernel_ms = timed(args.steps)
 
-    # ---- diagnosis of an N > 1 line: where does the time go? (outside the timed region above) ---------------
+    # ---- what the last timed step computed, as rank 0 holds it (before any leg below touches the arrays) ----------
+    if args.dump_outputs and rank == 0:
+        if gather is not None:      # N > 1: the whole fan, gathered to rank 0
+            per_ray = {"npoints": tg.npoints, "stop_code": tg.stop_code}
+            traj = {"ray_vec": tg.ray_vec, "residual": tg.residual}
+        else:
+            per_ray = {"npoints": tr.npoints, "stop_code": tr.stop_code, "end_ray_vec": tr.end_ray_vec,
+                       "end_residuals": tr.end_residuals, "max_residuals": tr.max_residuals}
+            traj = {"ray_vec": tr.ray_vec, "residual": tr.residual}
+        extra = None
+        if deposit is not None:     # --exchange deposition: the profile rank 0 ends up with
+            extra = {"deposition_profile": prof if chain is None else chain.out}
+        dump_outputs(args.dump_outputs, per_ray, traj, extra)
+
     ones = torch.ones(1, dtype=torch.int64, device=dev)
     tot = torch.tensor([steps_local], dtype=torch.int64, device=dev)
     if world > 1:
@@ -499,8 +584,9 @@ def main():
     total_steps = int(tot.item())
     if n_ranks_seen != args.gpus:   # never report an N-GPU line that fewer ranks produced
         raise SystemExit(f"bench.py --gpus {args.gpus}: the collective saw {n_ranks_seen} rank(s)")
+    # ---- --full, diagnosis of an N > 1 line: where does the time go? (outside the timed region above) ----------
     split = {}
-    if world > 1 and gather is not None:
+    if args.full and world > 1 and gather is not None:
         el_trace, _ = timed(args.steps, with_exchange=False)        # the same K passes without the exchange
         reps = 3
         barrier()
@@ -529,9 +615,9 @@ def main():
                           "trace of pass i+1, so ms_per_step ~ max(trace, gather)); value_trace_only = the same K "
                           "passes with the exchange switched off; gather_ms = one exchange on its own")
 
-    # ---- N > 1: the same K passes when every rank's result STAYS on its GPU (a consumer with device-side
+    # ---- --full, N > 1: the same K passes when every rank's result STAYS on its GPU (a consumer with device-side
     # post-processing) and only ray_results_m's per-ray summaries reach rank 0 (outside the timed region) ----
-    if world > 1 and args.exchange == "gather":
+    if args.full and world > 1 and args.exchange == "gather":
         from rays_amd.exchange import SummaryGather
 
         sg = SummaryGather(nray_total, nv, dev)
@@ -552,9 +638,9 @@ def main():
     # the timed passes must have reproduced the first pass (deterministic kernels)
     assert int(torch.clamp(tr.npoints.to(torch.int64) - 1, min=0).sum().item()) == steps_local
 
-    # ---- the other numerics flavour of the same kernel, same K passes (one GPU; outside the timed region) ----
+    # ---- --full: the other numerics flavour of the same kernel, same K passes (one GPU; outside the timed region) ----
     other = None
-    if world == 1 and args.exchange == "gather":
+    if args.full and world == 1 and args.exchange == "gather":
         this_kernel = hip.kernel_name(p, hi - lo)
         hip.set_numerics("exact" if args.numerics == "tolerance" else "tolerance")
         if hip.kernel_name(p, hi - lo) != this_kernel:   # (configurations without a tolerance flavour run one kernel)
@@ -571,14 +657,14 @@ def main():
         tr.launch(zero_fill=False)     # leave the arrays as the timed flavour wrote them
         torch.cuda.synchronize()
 
-    # ---- two independent passes in flight (one GPU; outside the timed region) ------------------------------------------
+    # ---- --full: two independent passes in flight (one GPU; outside the timed region) -----------------------------------
     # One 64k fan is one ray per resident lane and the pass lasts as long as its longest ray: 55 % of the SIMD-time is
     # idle (simd_idle_frac).  A host with INDEPENDENT fans to trace (a parameter scan, a time loop over launch conditions)
     # can fill it: the same K passes issued alternately on two streams into two complete sets of result arrays, so that
     # the blocks of pass i + 1 start on the CUs whose blocks of pass i have ended.  Reported next to `value`, never as it:
     # `value` is K passes one after the other on one stream.
     pipelined = None
-    if world == 1 and args.exchange == "gather" and not args.no_pipelined and 16.0 * (nv + 1) * npt * (hi - lo) <= 40e9:
+    if args.full and world == 1 and args.exchange == "gather" and not args.no_pipelined and 16.0 * (nv + 1) * npt * (hi - lo) <= 40e9:
         tr2 = DeviceTrace(p, r0[lo:hi], n0[lo:hi], device=dev)
         s_a, s_b = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)
         with torch.cuda.stream(s_b):
@@ -707,7 +793,7 @@ def main():
         if pipelined is not None:
             line.update(pipelined)
         host_bytes = 8.0 * (nv + 1) * (p.nstep_max + 1) * nray_total   # the caller's padded ray_results_m arrays
-        if world == 1 and not args.no_host_entry and args.exchange == "gather" and host_bytes <= 8e9:
+        if args.full and world == 1 and not args.no_host_entry and args.exchange == "gather" and host_bytes <= 8e9:
             try:   # outside the timed region: the rate the reference's own call site sees, both flavours
                 del tr
                 torch.cuda.empty_cache()
@@ -722,7 +808,7 @@ def main():
                 line["host_entry"] = he
             except Exception as e:
                 print(f"[bench] host_entry leg failed: {e}", file=sys.stderr)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args.config)
         print(json.dumps(line))
     if world > 1:

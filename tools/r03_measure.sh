@@ -3,7 +3,7 @@
 # configs dispatch (both numerics flavours of the headline), pass times of every config.  Raw output -> gpurun_out/r03/.
 R=$PWD; O=gpurun_out/r03; mkdir -p $O
 timeout -k 10 900 python -m pytest tests -m gpu -x -q > $O/gputest.log 2>&1; echo "EXIT $?" >> $O/gputest.log; tail -3 $O/gputest.log
-python bench.py --steps 20 --warmup 5 > $O/bench_n1.json 2> $O/bench_n1.err; cat $O/bench_n1.json | head -c 600; echo
+python bench.py --full --steps 20 --warmup 5 > $O/bench_n1.json 2> $O/bench_n1.err; cat $O/bench_n1.json | head -c 600; echo
 python tools/tol_flavour_check.py 2>&1 | grep -v amdgpu.ids | tee $O/rk4_flavours_pass_times.txt
 python tools/sg_ab.py 2>&1 | grep -v amdgpu.ids | tee $O/sg_pass_times.txt
 bash tools/profile_bench.sh rk4_64k_tol > $O/prof_rk4_64k_tol.log 2>&1

@@ -6,7 +6,7 @@
 R=$PWD; O=gpurun_out/r04; mkdir -p $O
 timeout -k 10 900 python -m pytest tests -m gpu -x -q > $O/gputest.log 2>&1; echo "EXIT $?" >> $O/gputest.log; tail -3 $O/gputest.log
 cp gpurun_out/numerics_evidence.json $O/ 2>/dev/null
-python bench.py --steps 20 --warmup 5 > $O/bench_n1.json 2> $O/bench_n1.err; head -c 600 $O/bench_n1.json; echo
+python bench.py --full --steps 20 --warmup 5 > $O/bench_n1.json 2> $O/bench_n1.err; head -c 600 $O/bench_n1.json; echo
 python tools/sg_ab.py 2>&1 | grep -v amdgpu.ids | tee $O/sg_pass_times.txt
 for n in exact tolerance; do RAYS_HIP_NUMERICS=$n python tools/time_rk4_configs.py 2>&1 | grep -v amdgpu.ids; done | tee $O/rk4_flavours_pass_times.txt
 bash tools/dropin_trace_deposition_timing.sh > $O/dropin_cfg5b_trace_deposition_timing.txt 2>&1
@@ -29,7 +29,7 @@ done | tee $O/profile_overview.txt
 # the line to be tracked: once more, now that this session's counters and numerics evidence exist (in this scratch copy of the
 # repo), so that its roofline.traffic / roofline_fp64 / numerics_evidence are the ones of these sources
 python tools/update_counters.py gpurun_out/prof_*/pmc_summary.json > /dev/null 2>&1; cp gpurun_out/numerics_evidence.json profiles/numerics_evidence.json 2>/dev/null
-python bench.py --steps 20 --warmup 5 > $O/bench_n1.json 2> $O/bench_n1.err; head -c 200 $O/bench_n1.json; echo
+python bench.py --full --steps 20 --warmup 5 > $O/bench_n1.json 2> $O/bench_n1.err; head -c 200 $O/bench_n1.json; echo
 # (the N = 2 / 4 rehearsal is its own gpurun call -- `bash tools/rehearse_multi_gpu.sh`, ~10 min of gloo copies: with it
 #  this script overran the 20-minute limit of one call)
 python tools/kernel_resources_all.py > $O/kernel_resources.txt 2> $O/kernel_resources.err; tail -3 $O/kernel_resources.txt
