@@ -240,9 +240,9 @@ int rays_hip_set_eqdsk_lin_tables(const rays_axisym_tables_t* t, double dR, doub
  *     arithmetic but the reference's own (a ray's last recorded step before two modes coalesce) are handed over to a
  *     kernel of the exact build.  Built for ode_solver = RK4 with ray_deriv = cold (without
  *     multi_spec_damping); every other configuration runs its exact kernel under either setting (finite-difference
- *     dD amplifies an ulp by 1e8, and the adaptive solver then takes another step sequence).  Fans of 131072 rays and
- *     more run a two-waves-per-SIMD build without the hand-over: on Solovev fans that large a ray's last recorded step
- *     can deviate by up to 4.5e-10.
+ *     dD amplifies an ulp by 1e8, and the adaptive solver then takes another step sequence).  The two-waves-per-SIMD
+ *     build, which has no hand-over, serves slab fans only under this setting (they have no such step); Solovev and
+ *     axisym fans of every size run the kernel with the hand-over.
  * The environment variable RAYS_HIP_NUMERICS = exact | tolerance sets the initial value.  Returns the previous
  * setting, or -1 for an unknown mode. */
 enum { RAYS_NUMERICS_EXACT = 0, RAYS_NUMERICS_TOLERANCE = 1 };

@@ -1383,6 +1383,41 @@ int rays_oracle_trace(const rays_params_t* P, int nray, const double* rvec0,
 }
 
 /* --------------------------------------------------------------------------------------------
+ * One output step of trace_rays' loop body (ray_tracing.f90:118-243) from an arbitrary state: RK4_ode from
+ * (v0, s0) to s0 + ds, then check_save, exactly as trace_one composes them.  code = the stop code of RK4_ode
+ * (stopped = 1) or check_save's flag (stopped = its stop_ode).  The sout > s_max / nstep_max exits are decided
+ * outside the step and are not part of it.
+ * ------------------------------------------------------------------------------------------ */
+int rays_oracle_step(const rays_params_t* P, int n, const double* v0, const double* s0, double* v1,
+                     double* resid, int32_t* code, int32_t* stopped, int nthreads) {
+  int rc = rays_oracle_check_params(P);
+  if (rc) return rc;
+  if (P->ode_solver != RAYS_ODE_RK4) return 100; /* a restarted SG step is not the reference's next step */
+  const size_t nv = (size_t)P->nv;
+  const rf_ctx rf = {P->omgrf, P->k0};
+#ifdef _OPENMP
+  if (nthreads <= 0) nthreads = omp_get_max_threads();
+#pragma omp parallel for schedule(dynamic, 256) num_threads(nthreads)
+#endif
+  for (int i = 0; i < n; i++) {
+    double v[RAYS_ORACLE_NV_MAX];
+    for (size_t j = 0; j < nv; j++) v[j] = v0[(size_t)i * nv + j];
+    double s = s0 ? s0[i] : 0.;
+    double sout = s + P->ds; /* :118-119 */
+    double r = 0.;
+    int stop = 0;
+    int flag = rk4_ode(P, rf, v, &s, sout);
+    if (flag) stop = 1;                              /* :177-197 */
+    else flag = check_save(P, rf, v, &r, &stop);     /* :212 */
+    for (size_t j = 0; j < nv; j++) v1[(size_t)i * nv + j] = v[j];
+    resid[i] = r;
+    code[i] = flag;
+    stopped[i] = stop;
+  }
+  return 0;
+}
+
+/* --------------------------------------------------------------------------------------------
  * probe: evaluate the RHS pieces at one state (unit parity against the reference dump)
  * eq_out: bvec3 bmag gradbmag3 bunit3 gradbunit9 gradbtensor9 (Fortran column-major order, as
  * written by ref_dump_driver.f90) then per species ns gradns3 ts gradts3 omgc omgp2 alpha gamma.

@@ -29,6 +29,14 @@ int rays_oracle_trace(const rays_params_t* P, int nray, const double* rvec0,
                       double* end_residuals, double* max_residuals, int nthreads,
                       long long* nrhs_total);
 
+/* One output step (RK4_ode + check_save, as rays_oracle_trace composes them) from each of n arbitrary states:
+ * v0[n][nv], s0[n] (null = 0) -> v1[n][nv], resid[n], code[n] (RK4_ode's stop code or check_save's flag),
+ * stopped[n] (the reference would end the ray inside this step and record no point).  RK4 only: returns 100 for
+ * Shampine-Gordon, whose output step depends on state the recorded point does not carry.  nthreads <= 0 = all
+ * OpenMP threads. */
+int rays_oracle_step(const rays_params_t* P, int n, const double* v0, const double* s0, double* v1,
+                     double* resid, int32_t* code, int32_t* stopped, int nthreads);
+
 /* One-state probe of equilibrium / deriv_cold / deriv_num / eqn_ray / check_save.
  * eq_out needs 28 + 12*(nspec+1) doubles; cold7/num7 = dddx(3) dddk(3) dddw; codes[4]. */
 void rays_oracle_probe(const rays_params_t* P, const double* v, double* eq_out, double* cold7,

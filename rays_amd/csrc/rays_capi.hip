@@ -127,7 +127,11 @@ int initial_numerics() {
 std::atomic<int> g_numerics{initial_numerics()};
 
 // nray: fan size (0 = unknown).  From two waves per SIMD worth of rays on, the two-waves-per-SIMD build
-// of the kernel is preferred where one exists (rays_rk4.hpp).
+// of the kernel is preferred where one exists (rays_rk4.hpp) -- under the tolerance flavour for the slab only: the
+// two-waves build has no hand-over of ill-conditioned steps (rays_rk4_body.inc), which the slab fans do not need
+// (no coalescence; surveyed on 32.8 M steps) and every other equilibrium may.
+// force_exact: the exact twin of a tolerance kernel, whose resume kernel takes the handed-over steps: always the
+// one-wave-per-SIMD entry (the only one that carries a resume kernel), whatever the fan size or the developer switch.
 const rays::KernelEntry* find_kernel(const rays_params_t& p, long long nray = 0, bool force_exact = false) {
   using namespace rays;
   typedef const KernelEntry* (*Getter)(int*);
@@ -154,8 +158,10 @@ const rays::KernelEntry* find_kernel(const rays_params_t& p, long long nray = 0,
     if (nray > 0 && hipGetDevice(&dev) == hipSuccess) ncu = device_cu_count(dev);
   }
   bool big = nray >= 2ll * ncu * 256;  // >= two waves per SIMD
+  if (tol && p.equilib_model != RAYS_EQ_SLAB) big = false;
   if (const char* f = std::getenv("RAYS_HIP_FORCE_WAVES_PER_SIMD"))  // developer measurement: "1" | "2"
     big = f[0] == '2';
+  if (force_exact) big = false;
   // SG with finite-difference dD (nv = 7) exists in two mappings: one ray per group of four lanes
   // (rays_sg_group.hpp, the default: 212 against 300 ms per pass on the 64k-ray Solovev fan) and one ray per lane
   // (rays_sg.hpp; RAYS_HIP_SG_GROUP=0, for A/B measurements).  Both are bit-identical to the reference.
@@ -714,7 +720,7 @@ int launch_trace(const rays_params_t* p, int nray, const double* d_rvec0, const 
   // kStopResumeExact): the exact twin's resume kernel follows it on the stream.  The hand-over travels in the per-ray
   // summaries, so they exist for such a launch whether or not the caller asked for them.
   const rays::KernelEntry* twin = nullptr;
-  if (kernel->eq & rays::kEqTol) {
+  if ((kernel->eq & rays::kEqTol) && kernel->occ == 1) {  // (the two-waves build hands nothing over)
     twin = find_kernel(*p, 0, true);
     if (!twin || !twin->resume) return fail("rays_hip: the tolerance kernel's exact twin is not in this build");
     if (!A.end_ray_vec || !A.max_residuals) {

@@ -118,8 +118,9 @@
 // and resume with the one arithmetic the host has: bit-identical to the fixtures by construction, control flow covered.)
 // Built into the one-wave-per-SIMD kernel only.  In the two-waves build (one loop, 230 registers) the same few lines cost
 // the 1 M-ray slab fan of cfg 4 24 % (28.2 -> 35.0 ms, A/B on one box: profiles/r04/measurements/w2_handover_ab.txt),
-// and that fan has no such step: max per-step deviation 4.6e-13 over 32.8 M restarts without it.  A Solovev fan of
-// 131072 rays or more (not a BASELINE config) therefore keeps its handful of last steps at up to 4.5e-10.
+// and that fan has no such step: max per-step deviation 4.6e-13 over 32.8 M restarts without it.  Under the tolerance
+// setting the dispatcher therefore takes the two-waves build for the slab only (rays_capi.hip: find_kernel): a Solovev
+// or axisym fan of any size runs the one-wave kernel with the hand-over, so that its last steps keep the bar too.
 #if (defined(RAYS_TOL_FLAVOUR) || defined(RAYS_EMUL_HANDOVER)) && RAYS_RK4_LONG_FIRST && !defined(RAYS_RK4_NO_HANDOVER)
 #define RAYS_RK4_HANDOVER 1
 #else

@@ -36,6 +36,8 @@ def lib():
         _lib.rays_oracle_trace.restype = C.c_int
         _lib.rays_oracle_trace.argtypes = [C.POINTER(RaysParams), C.c_int, dp, dp, dp, dp, ip, ip,
                                            dp, dp, dp, C.c_int, C.POINTER(C.c_longlong)]
+        _lib.rays_oracle_step.restype = C.c_int
+        _lib.rays_oracle_step.argtypes = [C.POINTER(RaysParams), C.c_int, dp, dp, dp, dp, ip, ip, C.c_int]
         _lib.rays_oracle_probe.restype = None
         _lib.rays_oracle_probe.argtypes = [C.POINTER(RaysParams), dp, dp, dp, dp, dp, dp, ip]
         _lib.rays_oracle_set_zfun_table.restype = C.c_int
@@ -81,6 +83,26 @@ def trace(p: RaysParams, rvec0, rindex_vec0, nthreads: int = 0) -> dict:
         raise RuntimeError(f"rays_oracle_trace rc={rc}")
     out["nrhs"] = nrhs.value
     return out
+
+
+def step(p: RaysParams, v0, s0=None, nthreads: int = 0):
+    """rays_oracle_step: one output step of the reference's loop body (RK4_ode + check_save) from each state
+    v0[n][nv] at arc length s0[n] (None: 0).  Returns (v1, resid, code, stopped): `stopped` marks the states from which
+    the reference would end the ray inside the step (and record no point), `code` is then the ray's stop code.
+    nthreads = 0: OpenMP's own default (OMP_NUM_THREADS is honoured)."""
+    v0 = np.ascontiguousarray(v0, dtype=np.float64).reshape(-1, p.nv)
+    n = len(v0)
+    if s0 is not None:
+        s0 = np.ascontiguousarray(s0, dtype=np.float64)
+        if s0.shape != (n,):
+            raise ValueError("oracle_lib.step: s0 must hold one arc length per state")
+    v1, resid = np.zeros((n, p.nv)), np.zeros(n)
+    code, stopped = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+    rc = lib().rays_oracle_step(C.byref(p), n, _dp(v0), None if s0 is None else _dp(s0), _dp(v1), _dp(resid),
+                                _ip(code), _ip(stopped), int(nthreads))
+    if rc:
+        raise RuntimeError(f"rays_oracle_step rc={rc}" + (" (RK4 only)" if rc == 100 else ""))
+    return v1, resid, code, stopped.astype(bool)
 
 
 def probe(p: RaysParams, v) -> dict:

@@ -42,12 +42,14 @@ def test_cfg5_equilibrium_file_is_what_the_references_own_tool_writes(tmp_path):
     configs/solovev_2_eqdsk_129.in, byte for byte; cfg 5 and cfg 5b must name it and the splined temperature model."""
     import shutil
     import subprocess
+    import numpy as np
     from rays_amd.namelist import read_namelist
     for cfg in ("cfg5_axisym256k_sg_damp.in", "cfg5b_axisym256k_rk4_damp.in"):
         nml = read_namelist(os.path.join(ROOT, "configs", cfg))
         assert nml["eqdsk_magnetics_spline_interp_list"]["eqdsk_file_name"].strip() == "solovev_129x129.geqdsk"
-        assert str(nml["axisym_toroid_eq_list"]["temperature_prof_model"][0]).strip() == "temperature_spline_interp" \
-            if isinstance(nml["axisym_toroid_eq_list"]["temperature_prof_model"], (list, tuple, dict)) else True
+        m = nml["axisym_toroid_eq_list"]["temperature_prof_model"]   # scalar, list, or {species index: model}
+        models = [m[k] for k in sorted(m)] if isinstance(m, dict) else list(np.atleast_1d(m))
+        assert models and all(str(x).strip() == "temperature_spline_interp" for x in models), (cfg, m)
     tool = os.path.join(ROOT, "oracle", "_ref", "solovev_2_eqdsk")
     if not os.path.exists(tool):
         pytest.skip("oracle/_ref/solovev_2_eqdsk not built (needs /root/reference)")

@@ -4,7 +4,12 @@ import numpy as np
 import pytest
 
 from tests import oracle_lib
-from tests.common import GOLDEN_CASES, assert_matches_golden, load_golden, stop_codes
+from tests.common import (GOLDEN_CASES, assert_matches_golden, host_libm_is_the_variant_the_fixtures_were_cut_with,
+                          load_golden, stop_codes)
+
+RK4_CASES = [n for n in GOLDEN_CASES if "_rk4" in n]
+# stop flags that trace_rays decides between two steps (ray_tracing.f90:128-172), not inside one
+OUTSIDE_THE_STEP = ("sout > s_max", " nstep > nstep_max")
 
 
 @pytest.mark.parametrize("name", GOLDEN_CASES)
@@ -24,6 +29,67 @@ def test_oracle_rhs_pieces_equal_reference_probes(name):
         for key in keys:
             assert np.array_equal(o[key], rec[key], equal_nan=True), key
         assert o["resid"] == rec["resid"] or (np.isnan(o["resid"]) and np.isnan(rec["resid"]))
+
+
+def _s_of_point(p, n):
+    """s of recorded point k as trace_rays accumulates it: sout = sout + ds, k times (ray_tracing.f90:118-121)."""
+    return np.concatenate([[0.0], np.cumsum(np.full(n, float(p.ds)))])
+
+
+def test_the_rk4_fixtures_are_the_ones_named_so():
+    for name in GOLDEN_CASES:
+        g, nml, p = load_golden(name)
+        assert (p.ode_solver == 0) == (name in RK4_CASES), name
+
+
+@pytest.mark.parametrize("name", RK4_CASES)
+def test_oracle_step_is_the_references_next_point(name):
+    """oracle_lib.step (RK4_ode + check_save from an arbitrary state) pinned to the reference-generated fixtures:
+    from EVERY recorded point k of every ray it returns point k + 1 and its residual bit for bit and does not stop;
+    from a ray's last recorded point it stops with the ray's stop flag, for every ray whose end is decided inside a step."""
+    g, nml, p = load_golden(name)
+    ref, res, npts = g["ray_vec"], g["residual"], g["npoints"].astype(np.int64)
+    nmax = ref.shape[1]
+    s_tab = _s_of_point(p, nmax)
+    has_next = np.arange(nmax - 1)[None, :] < (npts - 1)[:, None]          # [ray][k]: point k has a successor
+    kk = np.broadcast_to(np.arange(nmax - 1)[None, :], has_next.shape)[has_next]
+    assert has_next.sum() == (npts - 1).sum() > 0
+    v1, resid, code, stopped = oracle_lib.step(p, ref[:, :-1][has_next], s_tab[kk])
+    want, want_res = ref[:, 1:][has_next], res[:, 1:][has_next]
+    assert not stopped.any(), f"{int(stopped.sum())} recorded steps come back stopped (codes {set(code[stopped])})"
+    if host_libm_is_the_variant_the_fixtures_were_cut_with():
+        np.testing.assert_array_equal(v1, want)
+        np.testing.assert_array_equal(resid, want_res)
+    else:   # the documented bars of tests.common.assert_matches_golden, per step
+        for sl in (slice(0, 3), slice(3, 6)):
+            num, den = np.linalg.norm(v1[:, sl] - want[:, sl], axis=-1), np.linalg.norm(want[:, sl], axis=-1)
+            assert (num <= 1e-10 * den).all()
+        np.testing.assert_allclose(resid, want_res, rtol=0, atol=1e-12)
+    # ---- each ray's last recorded point ----
+    rays = np.arange(len(npts))
+    v1, resid, code, stopped = oracle_lib.step(p, ref[rays, npts - 1], s_tab[npts - 1])
+    inside = np.array([str(f) not in OUTSIDE_THE_STEP for f in g["stop_flag"]])
+    assert stopped[inside].all(), f"rays {rays[inside & ~stopped]} end inside a step in the fixture but not for step()"
+    np.testing.assert_array_equal(code[inside], stop_codes(g["stop_flag"])[inside])
+
+
+def test_oracle_step_edges():
+    g, nml, p = load_golden("cfg1_slab16_rk4")
+    v1, resid, code, stopped = oracle_lib.step(p, np.zeros((0, p.nv)))
+    assert v1.shape == (0, p.nv) and resid.shape == code.shape == stopped.shape == (0,)
+    # s0 = None is s = 0: the first step of every ray
+    a = oracle_lib.step(p, g["ray_vec"][:, 0])
+    b = oracle_lib.step(p, g["ray_vec"][:, 0], np.zeros(len(g["ray_vec"])))
+    for x, y in zip(a, b):
+        np.testing.assert_array_equal(x, y)
+    np.testing.assert_array_equal(a[0], g["ray_vec"][:, 1])
+    # the thread count does not enter the result
+    c = oracle_lib.step(p, g["ray_vec"][:, 0], nthreads=1)
+    np.testing.assert_array_equal(a[0], c[0])
+    # Shampine-Gordon: a restarted output step is not the reference's next step -- refused, not approximated
+    g, nml, p = load_golden("gold_solovev64_sg_cold")
+    with pytest.raises(RuntimeError, match="RK4 only"):
+        oracle_lib.step(p, g["ray_vec"][:, 0])
 
 
 def test_oracle_full_counts():
