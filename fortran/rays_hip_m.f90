@@ -110,6 +110,12 @@
     integer(c_int), parameter :: RAYS_TRACE_NO_ZERO_FILL = 1
     integer(c_int), parameter :: RAYS_NUMERICS_EXACT = 0, RAYS_NUMERICS_TOLERANCE = 1
     integer(c_int), parameter :: RAYS_DEP_PTOTAL_PSI = 0, RAYS_DEP_PTOTAL_RHO = 1, RAYS_DEP_PTOTAL_X = 2
+    ! fields of the per-point ray diagnostics (bit numbers of `fields`; the order of the output's leading dimension)
+    integer(c_int), parameter :: RAYS_DIAG_S = 0, RAYS_DIAG_NE = 1, RAYS_DIAG_TE_KEV = 2, RAYS_DIAG_MODB = 3, &
+         & RAYS_DIAG_ALPHA_E = 4, RAYS_DIAG_GAMMA_E = 5, RAYS_DIAG_PSI = 6, RAYS_DIAG_R = 7, RAYS_DIAG_X = 8, &
+         & RAYS_DIAG_Y = 9, RAYS_DIAG_Z = 10, RAYS_DIAG_N_PAR = 11, RAYS_DIAG_N_PERP = 12, RAYS_DIAG_P_ABSORBED = 13, &
+         & RAYS_DIAG_N_IMAG = 14, RAYS_DIAG_XI_0 = 15, RAYS_DIAG_XI_1 = 16, RAYS_DIAG_XI_2 = 17, RAYS_DIAG_RESIDUAL = 18, &
+         & RAYS_DIAG_NFIELDS = 19
 
     interface
 
@@ -299,6 +305,21 @@
           real(c_double), intent(in) :: initial_ray_power(*)
           real(c_double), intent(inout) :: work(*), profile(*)
        end function rays_hip_deposition_last
+
+       ! The post-processors' ray_detailed_diagnostics loop (axisym_toroid_processor_m.f90:351-419) on the GPU: host
+       ! arrays in the reference's layouts, out(nstep_max+1, nray, k) with k over the set bits of `fields` in
+       ! RAYS_DIAG_* order; first_bad_point(nray) (fortran/ray_diagnostics_hip.f90 is the caller)
+       integer(c_int) function rays_hip_ray_diagnostics(p, nray, ray_vec, residual, npoints, fields, out, &
+                    & first_bad_point) bind(C, name='rays_hip_ray_diagnostics')
+          import :: c_int, c_int32_t, c_double, rays_params_t
+          type(rays_params_t), intent(in) :: p
+          integer(c_int), value :: nray
+          real(c_double), intent(in) :: ray_vec(*), residual(*)
+          integer(c_int32_t), intent(in) :: npoints(*)
+          integer(c_int32_t), value :: fields
+          real(c_double), intent(inout) :: out(*)
+          integer(c_int32_t), intent(inout) :: first_bad_point(*)
+       end function rays_hip_ray_diagnostics
 
        ! Replaces the serial launch loops of ray_init_m's launchers (solovev_ray_init_nphi_ntheta_m.f90:
        ! 60-198 etc.): fills rvec0(3,nray_max), rindex_vec0(3,nray_max), ray_pwr_wt(nray_max), nray.

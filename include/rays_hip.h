@@ -451,6 +451,56 @@ int rays_hip_keep_last_result(int on);
 int rays_hip_deposition_last(const rays_params_t* p, int which, int n_bins, int nray, const double* initial_ray_power,
                              double* work, double* profile);
 
+/* ---- per-point ray diagnostics on the device (the post-processors' ray_detailed_diagnostics) ---------
+ * Replaces the serial loop over every recorded point of every ray of
+ *   ray_detailed_diagnostics        post_process_lib/axisym_toroid_processor_m.f90:252-482 (loop :351-419)
+ *   ray_detailed_diagnostics_slab   post_process_lib/slab_processor_m.f90
+ * (calculate_ray_diag = .true. is the processors' default): equilibrium + axisym_toroid_psi at the point and, with
+ * damping, deriv_cold + damping for the imaginary index -- one GPU lane per recorded POINT.  Fields, per point:
+ *   S, X, Y, Z, P_ABSORBED, RESIDUAL   copies: v(7), v(1), v(2), v(3), v(8) (0 when damping_model = 'no_damp'),
+ *                                      residual(istep, iray)
+ *   R                                  sqrt(x**2 + y**2)
+ *   NE, MODB, ALPHA_E                  eq%ns(0), eq%bmag, eq%alpha(0)
+ *   GAMMA_E                            abs(eq%gamma(0))
+ *   TE_KEV                             eq%Ts(0)/e/1000.
+ *   PSI                                psiN of axisym_toroid_psi (all three magnetics models); 0 for the slab.
+ *                                      equilib_model = 'solovev' has no processor in the reference: an extension, PSI
+ *                                      is then psiN of solovev_psi (solovev_eq_m.f90:308-318)
+ *   N_PAR, N_PERP                      k3/k0, k1/k0 with k3 = sum(kvec*bunit), k1 = sqrt(sum((kvec - k3*bunit)**2))
+ *   N_IMAG                             ki/k0, ki from damping(eq, v, vg = -dddk/dddw) with the COLD derivatives at
+ *                                      nvec = kvec/k0 whatever ray_deriv is (the reference tests ray_dispersion_model);
+ *                                      0 without damping
+ *   XI_0, XI_1, XI_2                   (omgrf + m omgc(0))/(k3*vth), vth = sqrt(2.*ts(0)/ms(0)), m = 0, 1, 2, where
+ *                                      ts(0) > 0 and abs(k3) > 0; else 0
+ * The union of the axisym set and the slab set (X, Y there in place of Psi, R).  `fields` selects by bit
+ * (1u << RAYS_DIAG_*); a field that is not selected costs neither its store nor, where separable, its arithmetic (no
+ * equilibrium for the copies and R, no deriv_cold / damping without N_IMAG).  Always the exact arithmetic
+ * (bit-identical to the reference's loop); rays_hip_set_numerics does not affect it.  Built for the species counts and
+ * equilibria of the trace kernels (all of them under make FULL=1); another shape is refused by name.
+ * The one behavioural difference: where the reference stops the program ('infinite group velocity',
+ * abs(dddw) <= tiny(dddw), :395-400) the point gets N_IMAG = 0, first_bad_point[iray] is set to the 1-based index of
+ * the ray's first such point (0 = none) and the call still returns 0. */
+enum { RAYS_DIAG_S = 0, RAYS_DIAG_NE, RAYS_DIAG_TE_KEV, RAYS_DIAG_MODB, RAYS_DIAG_ALPHA_E, RAYS_DIAG_GAMMA_E,
+       RAYS_DIAG_PSI, RAYS_DIAG_R, RAYS_DIAG_X, RAYS_DIAG_Y, RAYS_DIAG_Z, RAYS_DIAG_N_PAR, RAYS_DIAG_N_PERP,
+       RAYS_DIAG_P_ABSORBED, RAYS_DIAG_N_IMAG, RAYS_DIAG_XI_0, RAYS_DIAG_XI_1, RAYS_DIAG_XI_2, RAYS_DIAG_RESIDUAL,
+       RAYS_DIAG_NFIELDS };
+/* Device-pointer form, on the arrays as rays_hip_trace_device left them (current device).
+ * d_out[k][nray][nstep_max+1]: k counts the set bits of `fields` in enum order (== the reference's
+ * field(max_number_of_points, number_of_rays) arrays, one after another); slots past npoints(iray) are written as
+ * +0.0 by the call (the reference allocates with source = 0).  Asynchronous on hip_stream. */
+int rays_hip_ray_diagnostics_device(const rays_params_t* p, int nray, const double* d_ray_vec,
+                                    const double* d_residual, const int32_t* d_npoints, uint32_t fields,
+                                    double* d_out, int32_t* d_first_bad_point /* may be NULL */, void* hip_stream);
+/* Host-pointer form: ray_results_m arrays in, out[k][nray][nstep_max+1]; processes the rays in blocks so that the
+ * device footprint is bounded whatever nray is (at most 2**21 trajectory slots per block; the environment variable
+ * RAYS_HIP_DIAG_BLOCK_RAYS sets the rays per block instead); only recorded points cross PCIe in either direction
+ * (packed on the host, evaluated in the packed layout, scattered back by the host, which zero-fills the rest).
+ * Blocking, and plain: it runs on the CURRENT HIP device (the device list of rays_hip_init[_devices] is not used),
+ * block after block without overlapping copies and kernels, through pageable copies and device buffers allocated and
+ * freed per call.  Its time has not been measured; the figures quoted for the kernel are the device-pointer form's. */
+int rays_hip_ray_diagnostics(const rays_params_t* p, int nray, const double* ray_vec, const double* residual,
+                             const int32_t* npoints, uint32_t fields, double* out, int32_t* first_bad_point);
+
 /* Diagnostic entry used by the parity tests: evaluates equilibrium + deriv_cold + deriv_num +
  * eqn_ray + check_save at n states on the current device (host pointers; nv must be 7, nspec 1|2).
  * cold7/num7[n][7] = dddx(3) dddk(3) dddw; dvds[n][7]; resid[n]; codes[n][4] = equilibrium err,

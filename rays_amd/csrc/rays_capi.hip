@@ -23,6 +23,7 @@
 #include "rays_launch.hpp"
 #include "rays_ray_init.hpp"
 #include "rays_deposition.hpp"
+#include "rays_capi_internal.hpp"
 
 namespace rays {
 #define RAYS_DECL_ENTRIES(s, e, d) \
@@ -624,6 +625,34 @@ const char* rays_hip_kernel_name_for(const rays_params_t* p, int nray) {
 // Common launcher of the trace kernels: `extra` carries the optional per-ray starting conditions and the
 // per-run steps of a fused scan (rays_trace.hpp: TraceArgs).
 namespace {
+// The device pointers of the tables p's kernels read, on the current device: the Z-function spline (with damping) and
+// the axisym_toroid tables (uploaded when stale).
+int device_tables(const rays_params_t* p, rays::DevParams* Dp) {
+  rays::DevParams& D = *Dp;
+  int rc = 0;
+  if (p->damping_model == RAYS_DAMP_FUND_ECH) {
+    const double* zf = nullptr;
+    rc = get_zfun_device(&zf);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(g_mu);
+    D.zf_fspl = zf;
+    D.zf_nx = g_zfun.nx;
+    D.zf_xmin = g_zfun.xmin;
+    D.zf_xmax = g_zfun.xmax;
+  }
+  if (p->equilib_model == RAYS_EQ_AXISYM) {
+    rc = get_axisym_device(&D);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(g_mu);
+    const bool need_ne = p->axisym.density_prof_model == RAYS_AXI_N_SPLINE && g_axi.n_ne < 2;
+    bool need_t = false;
+    for (int is = 0; is <= p->nspec; is++)
+      if (p->axisym.t_prof_model[is] == RAYS_AXI_T_SPLINE && (g_axi.n_te < 2 || g_axi.n_ti < 2)) need_t = true;
+    if (need_ne || need_t) return fail("axisym_toroid: spline profile model selected but its table was not set");
+  }
+  return 0;
+}
+
 struct TraceExtras {
   const double* v0 = nullptr;
   const double* s0 = nullptr;
@@ -696,26 +725,8 @@ int launch_trace(const rays_params_t* p, int nray, const double* d_rvec0, const 
     A.sg_far = ws;
   }
   rays::DevParams D = make_dev_params(*p);
-  if (p->damping_model == RAYS_DAMP_FUND_ECH) {
-    const double* zf = nullptr;
-    rc = get_zfun_device(&zf);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lk(g_mu);
-    D.zf_fspl = zf;
-    D.zf_nx = g_zfun.nx;
-    D.zf_xmin = g_zfun.xmin;
-    D.zf_xmax = g_zfun.xmax;
-  }
-  if (p->equilib_model == RAYS_EQ_AXISYM) {
-    rc = get_axisym_device(&D);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lk(g_mu);
-    const bool need_ne = p->axisym.density_prof_model == RAYS_AXI_N_SPLINE && g_axi.n_ne < 2;
-    bool need_t = false;
-    for (int is = 0; is <= p->nspec; is++)
-      if (p->axisym.t_prof_model[is] == RAYS_AXI_T_SPLINE && (g_axi.n_te < 2 || g_axi.n_ti < 2)) need_t = true;
-    if (need_ne || need_t) return fail("axisym_toroid: spline profile model selected but its table was not set");
-  }
+  rc = device_tables(p, &D);
+  if (rc) return rc;
   // A tolerance-flavour kernel hands its ill-conditioned steps over to the reference's arithmetic (rays_rk4_body.inc:
   // kStopResumeExact): the exact twin's resume kernel follows it on the stream.  The hand-over travels in the per-ray
   // summaries, so they exist for such a launch whether or not the caller asked for them.
@@ -741,6 +752,21 @@ int launch_trace(const rays_params_t* p, int nray, const double* d_rvec0, const 
   return counter_launched(counter_slot, stream);
 }
 }  // namespace
+
+// rays_capi_internal.hpp: this file's state for the entry points defined in other translation units
+extern "C++" {
+namespace rays {
+int capi_fail(const char* msg) { return fail(msg); }
+int capi_hip_fail(hipError_t e, const char* what) { return hip_fail(e, what); }
+int capi_dev_params(const rays_params_t* p, DevParams* D, bool* unit_exp) {
+  int rc = rays_hip_check_params(p);
+  if (rc) return rc;
+  *D = make_dev_params(*p);
+  if (unit_exp) *unit_exp = unit_exponents(*p);
+  return device_tables(p, D);
+}
+}  // namespace rays
+}  // extern "C++"
 
 int rays_hip_trace_device(const rays_params_t* p, int nray, const double* d_rvec0,
                           const double* d_rindex_vec0, double* d_ray_vec, double* d_residual,

@@ -32,6 +32,7 @@ EXPORTED_SYMBOLS = (
     "rays_hip_set_rho_table", "rays_hip_deposition_device", "rays_hip_deposition",
     "rays_hip_keep_last_result", "rays_hip_deposition_last",
     "rays_hip_set_numerics", "rays_hip_get_numerics",
+    "rays_hip_ray_diagnostics_device", "rays_hip_ray_diagnostics",
 )
 
 _lib = None
@@ -127,6 +128,13 @@ def load():
     lib.rays_hip_set_numerics.restype = C.c_int
     lib.rays_hip_set_numerics.argtypes = [C.c_int]
     lib.rays_hip_get_numerics.restype = C.c_int
+    # (defined in a translation unit of their own, rays_diag.hip: a library given through RAYS_HIP_LIB that is built
+    # from rays_capi.hip alone -- the CPU tier's emulated C ABI -- does not have them; calling them there raises)
+    if hasattr(lib, "rays_hip_ray_diagnostics_device"):
+        lib.rays_hip_ray_diagnostics_device.restype = C.c_int
+        lib.rays_hip_ray_diagnostics_device.argtypes = [pp, C.c_int, vp, vp, vp, C.c_uint32, vp, vp, vp]
+        lib.rays_hip_ray_diagnostics.restype = C.c_int
+        lib.rays_hip_ray_diagnostics.argtypes = [pp, C.c_int, dp, dp, ip, C.c_uint32, dp, ip]
     _lib = lib
     return lib
 
@@ -273,6 +281,69 @@ def deposition_host(p: RaysParams, which: str, n_bins: int, ray_vec, npoints, in
     _check(load().rays_hip_deposition(C.byref(p), DEP_PROFILES[which], int(n_bins), nray, _dp(ray_vec), _ip(npoints),
                                       _dp(power), _dp(work), _dp(prof)), "rays_hip_deposition")
     return work, prof
+
+
+# RAYS_DIAG_* of include/rays_hip.h, in enum order; the names are the variables of the reference's
+# ray_detailed_diagnostics files (axisym_toroid_processor_m.f90:424-445; X, Y: the slab processor's)
+DIAG_FIELDS = ("s", "ne", "Te_kev", "modB", "alpha_e", "gamma_e", "Psi", "R", "X", "Y", "Z", "n_par", "n_perp",
+               "P_absorbed", "n_imag", "xi_0", "xi_1", "xi_2", "residual")
+
+
+def diag_field_mask(fields=None):
+    """(bit mask, names in enum order -- the order of the output's leading dimension) of a selection of DIAG_FIELDS
+    (None: all nineteen)."""
+    if fields is None:
+        fields = DIAG_FIELDS
+    if isinstance(fields, str):
+        fields = (fields,)
+    unknown = [f for f in fields if f not in DIAG_FIELDS]
+    if unknown or not len(fields):
+        raise ValueError(f"ray diagnostics: unknown or empty field selection {unknown or fields}; known: {DIAG_FIELDS}")
+    names = tuple(f for f in DIAG_FIELDS if f in fields)
+    return sum(1 << DIAG_FIELDS.index(f) for f in names), names
+
+
+def ray_diagnostics_device(p: RaysParams, nray: int, d_ray_vec: int, d_residual: int, d_npoints: int, fields,
+                           d_out: int, d_first_bad_point: int = 0, stream: int = 0):
+    """rays_hip_ray_diagnostics_device on device pointers (torch `.data_ptr()`s): d_out[k][nray][nstep_max+1] with k
+    over the selected fields in DIAG_FIELDS order; asynchronous on `stream`.  Returns the names in that order."""
+    ensure_tables(p)
+    mask, names = diag_field_mask(fields)
+    _check(load().rays_hip_ray_diagnostics_device(C.byref(p), int(nray), d_ray_vec, d_residual, d_npoints, mask, d_out,
+                                                  d_first_bad_point or None, stream or None),
+           "rays_hip_ray_diagnostics_device")
+    return names
+
+
+def ray_diagnostics_host(p: RaysParams, ray_vec, residual, npoints, fields=None, block_rays: int = 0):
+    """rays_hip_ray_diagnostics: the ray_results_m arrays in, ({name: array[nray][nstep_max+1]}, first_bad_point[nray])
+    out.  Blocking, on the current device.  block_rays > 0 is a TEST HOOK: rays per device block instead of the
+    library's bound of 2**21 trajectory slots per block, handed over by setting RAYS_HIP_DIAG_BLOCK_RAYS in os.environ
+    around the call -- not thread-safe, and a child process started meanwhile inherits it."""
+    ensure_tables(p)
+    mask, names = diag_field_mask(fields)
+    ray_vec = np.ascontiguousarray(ray_vec, dtype=np.float64)
+    residual = np.ascontiguousarray(residual, dtype=np.float64)
+    npoints = np.ascontiguousarray(npoints, dtype=np.int32)
+    nray, npt = len(npoints), p.nstep_max + 1
+    if ray_vec.shape != (nray, npt, p.nv) or residual.shape != (nray, npt):
+        raise ValueError("ray_diagnostics_host: arrays do not have the ray_results_m shapes of this run")
+    out = np.zeros((len(names), nray, npt))
+    bad = np.zeros(nray, dtype=np.int32)
+    saved = os.environ.get("RAYS_HIP_DIAG_BLOCK_RAYS")
+    if block_rays:
+        os.environ["RAYS_HIP_DIAG_BLOCK_RAYS"] = str(int(block_rays))
+    try:
+        rc = load().rays_hip_ray_diagnostics(C.byref(p), nray, _dp(ray_vec), _dp(residual), _ip(npoints), mask, _dp(out),
+                                             _ip(bad))
+    finally:
+        if block_rays:
+            if saved is None:
+                del os.environ["RAYS_HIP_DIAG_BLOCK_RAYS"]
+            else:
+                os.environ["RAYS_HIP_DIAG_BLOCK_RAYS"] = saved
+    _check(rc, "rays_hip_ray_diagnostics")
+    return {n: out[k] for k, n in enumerate(names)}, bad
 
 
 NO_KEPT_RESULT = 5   # RAYS_HIP_NO_KEPT_RESULT

@@ -395,6 +395,50 @@ def write_results_NC(path: str, r: RunResults) -> None:
     _write_netcdf_classic(path, dims, [("RAYS_run_label", r.RAYS_run_label.ljust(_FLAG_LEN))], variables)
 
 
+# variables of the reference's ray_detailed_diagnostics files in definition order
+# (axisym_toroid_processor_m.f90:433-451; slab_processor_m.f90: X, Y, Z in place of Psi, R, Z)
+_DIAG_VARS_AXISYM = ("s", "ne", "Te_kev", "modB", "alpha_e", "gamma_e", "Psi", "R", "Z", "n_par", "n_perp", "P_absorbed",
+                     "n_imag", "xi_0", "xi_1", "xi_2", "residual")
+_DIAG_VARS_SLAB = tuple({"Psi": "X", "R": "Y"}.get(v, v) for v in _DIAG_VARS_AXISYM)
+
+
+def ray_diagnostics_file_name(run_label: str, slab: bool = False) -> str:
+    """'ray_detailed_diagnostics.<label>.nc' (axisym_toroid_processor_m.f90:329), '..._slab.<label>.nc' for the slab"""
+    return ("ray_detailed_diagnostics_slab." if slab else "ray_detailed_diagnostics.") + str(run_label).strip() + ".nc"
+
+
+def write_ray_diagnostics_NC(path: str, diag: Dict[str, Any], npoints, dim_v_vector: int, run_label: str = "",
+                             date_vector=None, slab: bool = False) -> None:
+    """The NetCDF part of ray_detailed_diagnostics (axisym_toroid_processor_m.f90:424-480; slab=True: the slab
+    processor's twin): dimensions number_of_rays, max_number_of_points, dim_v_vector, d8 (:427-430); date_vector,
+    npoints and the seventeen per-point variables in the reference's definition order (:433-451; the Fortran dimension
+    lists reversed into the file's C order: [number_of_rays][max_number_of_points]); global attribute RAYS_run_label
+    (:454).  diag: {field name: array[nray][>= maxval(npoints)]} as hip.ray_diagnostics_host / RayResults.diagnostics
+    return it; the arrays are cut to maxval(npoints), the max_number_of_points of the results file the reference's
+    processors read (ray_results_m.f90:202)."""
+    npoints = np.ascontiguousarray(npoints, dtype=np.int32)
+    nray = len(npoints)
+    npt = int(npoints.max()) if nray else 0
+    if date_vector is None:
+        now = datetime.datetime.now().astimezone()
+        off = now.utcoffset()
+        date_vector = [now.year, now.month, now.day, int(off.total_seconds() // 60) if off else 0, now.hour, now.minute, now.second,
+                       now.microsecond // 1000]
+    names = _DIAG_VARS_SLAB if slab else _DIAG_VARS_AXISYM
+    missing = [n for n in names if n not in diag]
+    if missing:
+        raise ValueError(f"write_ray_diagnostics_NC: fields {missing} are not in `diag`")
+    R, P = "number_of_rays", "max_number_of_points"
+    dims = [(R, nray), (P, npt), ("dim_v_vector", int(dim_v_vector)), ("d8", 8)]
+    variables = [("date_vector", "int", ("d8",), np.asarray(date_vector, dtype=np.int32)), ("npoints", "int", (R,), npoints)]
+    for n in names:
+        a = np.asarray(diag[n], dtype=np.float64)
+        if a.ndim != 2 or a.shape[0] != nray or a.shape[1] < npt:
+            raise ValueError(f"write_ray_diagnostics_NC: {n} has shape {a.shape}, expected [{nray}][>= {npt}]")
+        variables.append((n, "double", (R, P), a[:, :npt]))
+    _write_netcdf_classic(path, dims, [("RAYS_run_label", str(run_label).ljust(_FLAG_LEN))], variables)
+
+
 def read_results_NC(path: str) -> Dict[str, Any]:
     """read_results_instance_NC (ray_results_m.f90:253-361)."""
     from scipy.io import netcdf_file

@@ -50,6 +50,15 @@ class RayResults:
     def total_steps(self) -> int:
         return int(np.maximum(self.npoints.astype(np.int64) - 1, 0).sum())
 
+    def diagnostics(self, params: RaysParams, fields=None) -> Dict[str, np.ndarray]:
+        """The post-processors' ray_detailed_diagnostics (axisym_toroid_processor_m.f90:252-482) of these host arrays,
+        evaluated on the GPU (hip.ray_diagnostics_host): {field name: array[nray][nstep_max+1]} for `fields`
+        (hip.DIAG_FIELDS; None = all), plus "first_bad_point"[nray] (include/rays_hip.h).  `params`: the run's
+        parameter block (a RayResults does not hold it)."""
+        out, bad = hip.ray_diagnostics_host(params, self.ray_vec, self.residual, self.npoints, fields)
+        out["first_bad_point"] = bad
+        return out
+
 
 def load_axisym_tables(namelist_path: str, nml: Dict[str, Dict[str, Any]]) -> Optional[Dict[str, Any]]:
     """Host-built spline tables of an eqdsk equilibrium: `<eqdsk_file_name>.tables.npz` next to the
@@ -167,6 +176,22 @@ class DeviceTrace:
                          self.stop_code.data_ptr(), self.end_ray_vec.data_ptr(),
                          self.end_residuals.data_ptr(), self.max_residuals.data_ptr(),
                          stream=stream, zero_fill=zero_fill)
+
+    def diagnostics(self, fields=None) -> Dict[str, Any]:
+        """ray_detailed_diagnostics of the trace as it lies on the device (hip.ray_diagnostics_device): {field name:
+        tensor[nray][nstep_max+1]} for `fields` (hip.DIAG_FIELDS; None = all) -- views of one [k][nray][nstep_max+1]
+        block -- plus "first_bad_point"[nray] (int32).  Asynchronous on the current torch stream, behind launch()."""
+        t = self.torch
+        _, names = hip.diag_field_mask(fields)
+        with t.cuda.device(self.device):
+            out = t.empty((len(names), self.nray, self.params.nstep_max + 1), dtype=t.float64, device=self.device)
+            bad = t.empty(self.nray, dtype=t.int32, device=self.device)
+            hip.ray_diagnostics_device(self.params, self.nray, self.ray_vec.data_ptr(), self.residual.data_ptr(),
+                                       self.npoints.data_ptr(), names, out.data_ptr(), bad.data_ptr(),
+                                       stream=t.cuda.current_stream(self.device).cuda_stream)
+        res: Dict[str, Any] = {n: out[k] for k, n in enumerate(names)}
+        res["first_bad_point"] = bad
+        return res
 
     def results(self) -> RayResults:
         self.torch.cuda.synchronize(self.device)
