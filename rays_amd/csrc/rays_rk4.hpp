@@ -5,12 +5,18 @@
 //   RK4_ode      RK4_ode_m.f90:59-94      (4 stages, early return leaves v untouched)
 //   eqn_ray / check_save                  (rays_device.hpp)
 //
-// Per lane the integrator is a 4-state machine around ONE RHS evaluation per wave-loop trip:
+// The integrator is a 4-state machine around ONE RHS evaluation per wave-loop trip:
 //   stage 0,1,2 : evaluate f at w (= v + ds*f1/2, v + ds*f2/2, v + ds*f3)  -> f2, f3, f4
 //   stage 3     : w = v + ds*(f1 + 2 f2 + 2 f3 + f4)/6 ; check_save(w) fused with the next step's
 //                 f1 = eqn_ray(w) (same equilibrium + dispersion derivatives, evaluated once)
 // A new ray starts in stage 3 with w = v0 (`first`), which is exactly the reference's initial
 // check_save call (ray_tracing.f90:100) and also yields the first step's f1.
+// The stage belongs to the WAVE: a lane under way advances by one stage on every trip, and a wave starts
+// rays only when no lane is under way or when the lanes under way are about to run stage 3, so all lanes
+// under way are at the same stage on every trip.  The stage is a scalar (one SGPR, never assigned under
+// lane-divergent control), the state machine a scalar switch with one region of lanes under way per arm,
+// check_save's share of the evaluation is skipped by a scalar branch on three trips of four, and whether
+// a pass is due is only asked on the trip that stage 3 follows (rays_rk4_body.inc).
 //
 // Recorded points: the one-wave-per-SIMD kernel with nv = 7 passes them through a per-lane LDS window
 // and writes whole 64-byte sectors (PointWindow, rays_trace.hpp: HBM write traffic 1.06x the
@@ -23,6 +29,9 @@
 #pragma once
 
 #include "rays_trace.hpp"
+#if defined(RAYS_HOST_EMUL) && defined(RAYS_EMUL_CHECK_UNIFORM_STAGE)
+#include <cstdio>
+#endif
 
 namespace rays {
 
@@ -103,6 +112,21 @@ rk4_resume_kernel(const DevParams P, const TraceArgs A) {
   if (ray >= A.nray || A.stop_code[ray] != kStopResumeExact) return;
   rk4_resume_ray<EQ, NS, DERIV, NV>(P, A, ray);
 }
+
+#if defined(RAYS_HOST_EMUL) && defined(RAYS_EMUL_CHECK_UNIFORM_STAGE)
+// Host emulation only: the trace bodies report a lane under way whose own stage differs from its wave's (or a lane whose
+// copy of the wave's stage differs from lane 0's) here -- on stderr, and counted for the test that built this.
+extern "C" __attribute__((visibility("default"), used)) inline int* rays_emul_uniform_stage_violations() {
+  static int n = 0;
+  return &n;
+}
+inline void uniform_stage_violation(int ray, int lane_stage, int wave_stage) {
+  int& n = *rays_emul_uniform_stage_violations();
+  if (n++ < 8)
+    std::fprintf(stderr, "[rays_rk4] UNIFORM STAGE VIOLATED: ray %d is at stage %d, its wave at stage %d\n", ray, lane_stage,
+                 wave_stage);
+}
+#endif
 
 #ifndef RAYS_HOST_EMUL
 // One wave per SIMD (all 256 VGPRs): fastest while the fan has at most one wave per SIMD (<= 64k rays).

@@ -39,8 +39,19 @@
     ray = (int)r;
   }
 #endif
-  int j = 3;            // stage
-  int first = 1;        // stage-3 evaluation is the initial check_save (int, not bool: see rays_sg.hpp)
+  // The stage of the WAVE, not of a lane: a ray starts at stage 3, a lane under way advances by one stage per trip and
+  // never sits a trip out, and a pass starts rays only when no lane is under way or the lanes under way are about to
+  // run stage 3 -- so all lanes under way are at the same stage on every trip.  It is never assigned under
+  // lane-divergent control (it advances once per trip, a pass sets it to 3), so it lives in a scalar register, the
+  // state machine below is a scalar switch and check_save's share of rhs_eval is skipped by a scalar branch.
+  // (-DRAYS_EMUL_CHECK_UNIFORM_STAGE, host emulation only: every lane also keeps the stage it would have on its own,
+  // and a lane under way that disagrees with the wave is reported -- rays_rk4.hpp: uniform_stage_violation.)
+  int jw = 3;
+#if defined(RAYS_HOST_EMUL) && defined(RAYS_EMUL_CHECK_UNIFORM_STAGE)
+  int j_lane = 3;
+#endif
+  // stage-3 evaluation is the initial check_save (int, not bool: see rays_sg.hpp); of a parked lane: its stop code
+  int first = 1;
   int nstep = 0;
   double s = 0., sout = 0., dsl = 0.;
   double ds_ray = P.ds;  // output step of this lane's run (a fused scan gives every run its own)
@@ -133,7 +144,13 @@
   // travels in the value -- a lane mask of its own across the wave loop cost 23 spilled SGPRs)
   double dddw_f1 = 0.;
   bool can_refill = (unsigned)A_hot.nray > total_lanes;  // wave-uniform: the counter may still hand out a ray
-  int idle_acc = 0;                             // wave-uniform
+  // Idle lane-trips since the last pass (wave-uniform).  A pass can only become due on a trip that is followed by stage
+  // 3, so the sum is only needed there, every fourth trip.  Between two passes the lanes that hold a ray or want one
+  // (`occupied`, counted by the pass) stay the same and lanes only go from under way to parked, so the idle lanes of a
+  // trip are occupied minus the lanes under way: the common trip adds its count of lanes under way to alive_sum -- the
+  // count that also tells whether any lane is left -- and the fourth settles: idle_acc += 4 * occupied - alive_sum.
+  // Trip for trip the sum the threshold sees is what a ballot of the parked lanes on every trip gave.
+  int idle_acc = 0, alive_sum = 0, occupied = 0;
   // RAYS_RK4_LONG_FIRST (the one-wave-per-SIMD kernel): two loops -- the outer one is the pass (cold: a handful of
   // times per wave), the inner one the trips between two passes (hot) -- and the rays are handed out "long rays first"
   // (rays_trace.hpp: take_rays).  As ONE loop with that pass inside an `if`, the pass's registers (cursors, window
@@ -153,21 +170,22 @@
     do {  // ---- the trips until the next pass is due ----
 #else
   for (;;) {
-    const unsigned long long under_way = __ballot(alive);
-    const unsigned long long waiting = __ballot(pending || need_init);
-    if (waiting) {  // wave-uniform
-      bool fire = under_way == 0;
-      if (!fire && can_refill) {
-        idle_acc += (int)__popcll(waiting);
-#ifndef RAYS_RK4_NO_STAGE_ALIGN
-        fire = idle_acc >= RAYS_REFILL_EVENT_COST && __ballot(alive && j == 3) != 0;
-#else
-        fire = idle_acc >= RAYS_REFILL_EVENT_COST;
-#endif
+    const int n_alive = (int)__popcll(__ballot(alive));
+    bool fire = false;
+    if (n_alive == 0) {  // wave-uniform
+      fire = __any(pending || need_init);
+    } else {
+      alive_sum += n_alive;
+      if (jw == 3) {  // the lanes under way are about to run stage 3: fresh rays can join them in step
+        if (can_refill && occupied > n_alive) {
+          idle_acc += 4 * occupied - alive_sum;
+          fire = idle_acc >= RAYS_REFILL_EVENT_COST;
+        }
+        alive_sum = 0;
       }
-      if (fire) {
+    }
+    if (fire) {
 #include "rays_rk4_pass.inc"
-      }
     }
     if (!__any(alive)) break;
     {
@@ -177,52 +195,64 @@
     double f[NV], resid = 0.;
     int code = 0, cs_flag = 0;
     bool cs_stop = false;
-#if RAYS_RK4_HANDOVER
-    // (the detection itself sits in the state machine's own branches below -- stage 2 tests, stage 3 re-arms: as a
-    // block of its own behind the evaluation it cost the trip four more exec-mask regions and 7 % of the pass)
-    double dddw_now = 0.;
-    if constexpr (DERIV == RAYS_DERIV_COLD) {
-      if (alive) rhs_eval<EQ, NS, DERIV, NV>(P, w, j == 3, resid, cs_flag, cs_stop, code, f, &dddw_now);
-    } else
+    // ---- the trip of the lanes under way: ONE region -- the evaluation, then the integrator's state machine as scalar
+    // branches on the wave's stage.  (A lane whose ray ends is parked until the wave's next pass over its idle lanes: its
+    // stop code goes into `first`.)
+#if defined(RAYS_HOST_EMUL) && defined(RAYS_EMUL_CHECK_UNIFORM_STAGE)
+    const int jw_lane0 = __shfl(jw, 0);  // (every lane of the emulated wave keeps its own copy of the wave's stage)
+    if (jw_lane0 != jw || (alive && j_lane != jw)) uniform_stage_violation(ray, alive ? j_lane : -1, jw);
+    j_lane = (j_lane + 1) & 3;
 #endif
-    if (alive) rhs_eval<EQ, NS, DERIV, NV>(P, w, j == 3, resid, cs_flag, cs_stop, code, f);
-
-    // ---- per-lane integrator state machine ---------------------------------------------------
-    int stop = 0;        // 0 = keep going
-    int done = 0;        // ray finished this trip
     if (alive) {
-      if (j < 3) {
-        if (code) {  // RK4_ode_m.f90:83-89: stage stopped, v untouched
-          stop = code;
-          done = 1;
-        } else if (j == 0) {
-#pragma unroll
-          for (int i = 0; i < NV; i++) {
-            acc[i] = acc[i] + 2.0 * f[i];
-            w[i] = v[i] + dsl * f[i] * 0.5;  // (ds*f2)/2.0, exact scaling
-          }
-          j = 1;
-        } else if (j == 1) {
-#pragma unroll
-          for (int i = 0; i < NV; i++) {
-            acc[i] = acc[i] + 2.0 * f[i];
-            w[i] = v[i] + dsl * f[i];
-          }
-          j = 2;
-        } else {
+#if RAYS_RK4_HANDOVER
+      // (the detection itself sits in the state machine's own branches below -- stage 2 tests, stage 3 re-arms: as a
+      // block of its own behind the evaluation it cost the trip four more exec-mask regions and 7 % of the pass)
+      double dddw_now = 0.;
+      if constexpr (DERIV == RAYS_DERIV_COLD)
+        rhs_eval<EQ, NS, DERIV, NV>(P, w, jw == 3, resid, cs_flag, cs_stop, code, f, &dddw_now);
+      else
+#endif
+        rhs_eval<EQ, NS, DERIV, NV>(P, w, jw == 3, resid, cs_flag, cs_stop, code, f);
+      // The two arms are two if-then regions in sequence, not an if / else: as an if / else the compiler's structured
+      // control flow runs the second arm behind a guard AFTER the first, keeps the first arm's inputs alive for it and
+      // joins the arms' results by copies (33 64-bit moves per stage-3 trip, 8 per other trip); in sequence each arm
+      // updates acc, w and v in place.  Hence the second, opaque copy of the stage for the second test.
+      int jw_again = jw;
+#ifndef RAYS_HOST_EMUL
+      asm volatile("" : "+s"(jw_again));
+#endif
+      if (jw != 3) {
+        // Stages 0, 1, 2: acc += c f (c = 2, 2, 1) and w = v + (ds f)/2, v + ds f, v + (ds acc)/6.  The products by the
+        // wave-uniform 1.0 and 2.0 are exact, so every stage rounds as it does written out on its own.  Updated whether
+        // or not the stage stopped (RK4_ode_m.f90:83-89 leaves v untouched): acc and w of a parked lane are dead.
+        if (jw == 2) {
 #pragma unroll
           for (int i = 0; i < NV; i++) {
             acc[i] = acc[i] + f[i];
             w[i] = v[i] + div(dsl * acc[i], R6);  // RK4_ode_m.f90:91  (ds*(...))/6.0
           }
-          j = 3;
 #if RAYS_RK4_HANDOVER
           // the last stage sits a whole step ahead: has dD/dw collapsed (or changed sign, or is it NaN) since the step's start?
           if constexpr (DERIV == RAYS_DERIV_COLD)
             if (!(dddw_now * dddw_f1 >= RAYS_RK4_HANDOVER_RATIO * (dddw_f1 * dddw_f1))) dddw_f1 = __builtin_nan("");
 #endif
+        } else {
+          const double h = jw == 0 ? 0.5 : 1.0;
+#pragma unroll
+          for (int i = 0; i < NV; i++) {
+            acc[i] = acc[i] + 2.0 * f[i];
+            w[i] = v[i] + dsl * f[i] * h;  // (ds*f2)/2.0, exact scaling; ds*f3
+          }
         }
-      } else {
+        if (code) {  // the stage stopped
+          alive = false;
+          pending = true;
+          first = code;
+        }
+      }
+      if (jw_again == 3) {
+        int stop = 0;        // 0 = keep going
+        int done = 0;        // ray finished this trip
         // stage 3: w is the new state; check_save decides whether the step is recorded
         if (first) {
           // ray_tracing.f90:92-112: point 1 = initial state, residual(1) = 0
@@ -275,51 +305,47 @@
 #if RAYS_RK4_HANDOVER
         dddw_f1 = dddw_now;  // this evaluation is also the next step's first
 #endif
-        if (!done) {  // top of the next trajectory trip, ray_tracing.f90:118-172
-          s = sout;
-          sout = sout + ds_ray;
-          if (sout > P.s_max) {
-            stop = RAYS_STOP_SOUT_GT_SMAX;
-            done = 1;
-          } else if (nstep + 1 > P.nstep_max) {
-            stop = RAYS_STOP_NSTEP_MAX;
-            done = 1;
-          } else if (code) {  // first RK4 stage of the next step stops (RK4_ode_m.f90:82-83)
-            stop = code;
-            done = 1;
-          } else {
-            {
-              RAYS_FP_AS_WRITTEN  // (s + ds) - s as the reference rounds it -- re-association folds it to ds
-              dsl = sout - s;     // RK4_ode_m.f90:81
-            }
+        // Top of the next trajectory trip, ray_tracing.f90:118-172, and the first stage of the next step -- without a
+        // branch: s, sout, dsl, acc and w of a lane that parks here are dead, so a ray that has just ended computes them too
+        // (the reference's order of the three tests is kept by the order of the selects).
+        s = sout;
+        sout = sout + ds_ray;
+        if (!done) {
+          stop = code;  // first RK4 stage of the next step stops (RK4_ode_m.f90:82-83)
+          if (nstep + 1 > P.nstep_max) stop = RAYS_STOP_NSTEP_MAX;
+          if (sout > P.s_max) stop = RAYS_STOP_SOUT_GT_SMAX;
+          done = stop != 0;
+        }
+        {
+          RAYS_FP_AS_WRITTEN  // (s + ds) - s as the reference rounds it -- re-association folds it to ds
+          dsl = sout - s;     // RK4_ode_m.f90:81
+        }
 #pragma unroll
-            for (int i = 0; i < NV; i++) {
-              acc[i] = f[i];
-              w[i] = v[i] + dsl * f[i] * 0.5;
-            }
-            j = 0;
-          }
+        for (int i = 0; i < NV; i++) {
+          acc[i] = f[i];
+          w[i] = v[i] + dsl * f[i] * 0.5;
+        }
+        if (done) {
+          alive = false;
+          pending = true;
+          first = stop;
         }
       }
-      if (done) {  // parked until the wave's next pass over its idle lanes (above)
-        alive = false;
-        pending = true;
-        j = stop;
-      }
     }
+    jw = (jw + 1) & 3;
 #if RAYS_RK4_LONG_FIRST
     // ---- is a pass due? ------------------------------------------------------------------------------------------------
-    const unsigned long long waiting = __ballot(pending || hungry);
-    fire = !__any(alive);
-    if (waiting && !fire && can_refill) {  // wave-uniform
-      // A fresh ray joins the lanes under way at stage 3 (its first evaluation is the initial check_save), so that
-      // the wave stays in step and check_save's share of the RHS runs on every fourth trip only.
-      idle_acc += (int)__popcll(waiting);
-#ifndef RAYS_RK4_NO_STAGE_ALIGN
-      fire = idle_acc >= RAYS_REFILL_EVENT_COST && __ballot(alive && j == 3) != 0;
-#else
-      fire = idle_acc >= RAYS_REFILL_EVENT_COST;
-#endif
+    // A fresh ray joins the lanes under way at stage 3 (its first evaluation is the initial check_save): only a trip that
+    // is followed by stage 3 asks the threshold; the other three count their lanes under way and go on.
+    const int n_alive = (int)__popcll(__ballot(alive));
+    alive_sum += n_alive;
+    fire = n_alive == 0;
+    if (jw == 3 && !fire) {  // wave-uniform
+      if (can_refill && occupied > n_alive) {
+        idle_acc += 4 * occupied - alive_sum;
+        fire = idle_acc >= RAYS_REFILL_EVENT_COST;
+      }
+      alive_sum = 0;
     }
     } while (!fire);
   }

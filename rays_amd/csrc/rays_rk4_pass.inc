@@ -2,6 +2,7 @@
 // the one place its loop structure runs it): ended rays are written out (what the LDS window still holds, the per-ray
 // summary), free lanes get their next ray and start it.  Uses the body's variables.
     idle_acc = 0;
+    alive_sum = 0;
     const TraceArgs& Ac = cold_args(A_hot);
 #if RAYS_RK4_LONG_FIRST
     const int S = (Ac.sched_stride > 1 && (unsigned)Ac.nray > total_lanes) ? Ac.sched_stride : 0;
@@ -15,7 +16,7 @@
         Window::phases(A, ray, npt, pv, pr);
         win.finish(A, (long long)ray * npt, nstep + 1, pv, pr);
       }
-      const int stop = j;
+      const int stop = first;  // parked there by the trip that ended the ray
       if (stop >= 0) {  // ray_tracing.f90:252-260
         A.npoints[ray] = nstep + 1;
         A.stop_code[ray] = stop;
@@ -65,8 +66,10 @@
       start_ray<EQ, NS, NV>(P, A, ray, v, sout, ds_ray);
 #pragma unroll
       for (int i = 0; i < NV; i++) w[i] = v[i];
-      j = 3;
       first = 1;
+#if defined(RAYS_HOST_EMUL) && defined(RAYS_EMUL_CHECK_UNIFORM_STAGE)
+      j_lane = 3;
+#endif
       nstep = 0;
       s = sout;
       last_resid = 0.;
@@ -75,3 +78,7 @@
       need_init = false;
       alive = true;
     }
+    // A pass runs when no lane is under way or when the lanes under way are about to run stage 3, and the rays it has
+    // just started begin there: the wave's stage (wave-uniform, assigned outside every lane-divergent region).
+    jw = 3;
+    occupied = (int)__popcll(__ballot(alive || pending || hungry));  // constant until the next pass
