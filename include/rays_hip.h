@@ -419,8 +419,14 @@ int rays_hip_ray_init_device(const rays_params_t* p, const rays_fan_t* fan, int 
  *                          reference's sum(work, 2): ranks that hold consecutive ray blocks chain
  *                          their partial sums through d_profile_in and obtain the single-process
  *                          result bit for bit (a few-KB exchange instead of the trajectory gather).
- * Grid = [0, 1] in psiN or rho, [xmin, xmax] for Ptotal_x; the reference's default is n_bins = 100
- * (n_bins <= 320 here). */
+ * Grid = [0, 1] in psiN or rho, [xmin, xmax] for Ptotal_x; the reference's default is n_bins = 100.
+ * LIMIT: 1 <= n_bins <= RAYS_DEP_MAX_BINS = 320 (the binning kernel keeps the rows of one wave, 64 x n_bins doubles,
+ * in the 160 KB of LDS of a compute unit).  All three entries refuse a larger n_bins with an error that names the
+ * limit, before anything is allocated or launched.
+ * Bins 1..n_bins receive exactly what the reference's statements give them; the one update the reference makes to
+ * binned_Q(n_bins + 1) -- an upper segment end just below the grid maximum whose real-number index rounds up to
+ * n_bins; undefined there -- is not made. */
+#define RAYS_DEP_MAX_BINS 320
 enum { RAYS_DEP_PTOTAL_PSI = 0, RAYS_DEP_PTOTAL_RHO = 1, RAYS_DEP_PTOTAL_X = 2 };
 /* rho(psiN) spline of the eqdsk equilibrium (rho_profile of eqdsk_magnetics_spline_interp_m.f90:42,
  * 190-193; fspl(4, n) on grid(n)); needed for RAYS_DEP_PTOTAL_RHO.  Copied. */

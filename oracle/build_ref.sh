@@ -6,13 +6,16 @@
 #   oracle/_ref/solovev_2_eqdsk the reference's own tool that writes the g-eqdsk of a Solovev equilibrium
 #                               (RAYS_project/solovev_2_eqdsk/solovev_2_eqdsk.f90): BASELINE config 5's 129 x 129 file
 #                               is its output (oracle/make_cfg5_eqdsk.sh)
+#   oracle/_ref/ref_binner      the reference's binner_real (math_functions_lib/bin_to_uniform_grid_m.f90) under
+#                               oracle/ref_binner_driver.f90: synthetic rays in, binned rows out -- the reference for
+#                               tests/golden/deposition_binner_cases.npz
 #   oracle/_ref/rays_hip_dropin reference host (initialize/ray_results/...) with trace_rays
 #                               REPLACED by fortran/trace_rays_hip.f90, the three ray launchers by
 #                               fortran/{solovev,simple_slab,axisym_toroid}_ray_init_hip.f90 and the
 #                               deposition binning by fortran/deposition_profiles_hip.f90 -> C-ABI
 #
 # Nothing from /root/reference is kept: sources are streamed through `sed` into a scratch
-# directory that is deleted before the script exits (objects, .mod files too); only the two
+# directory that is deleted before the script exits (objects, .mod files too); only the
 # linked executables stay, and oracle/_ref/ is git-ignored.
 #
 # The reference builds with gfortran + NetCDF + cmake; this image has amdflang and no NetCDF,
@@ -121,6 +124,10 @@ awk '/^ *open\(unit=input_unit, file=.rays.in./ { held = $0; next }
      { print }' "$P/solovev_2_eqdsk/solovev_2_eqdsk.f90" > "$W/solovev_2_eqdsk.f90"                  # P8
 $FC $FFLAGS -c solovev_2_eqdsk.f90 -o solovev_2_eqdsk.o
 $FC $FFLAGS -o "$OUT/solovev_2_eqdsk" solovev_2_eqdsk.o $LIBOBJS
+
+# ---- (1c) the reference's uniform grid binner alone, under a driver of this repo ---------------------------
+$FC $FFLAGS -c "$HERE/ref_binner_driver.f90" -o ref_binner_driver.o
+$FC $FFLAGS -o "$OUT/ref_binner" ref_binner_driver.o bin_to_uniform_grid_m.o
 
 # ---- (2) drop-in: same host objects, trace_rays replaced by the HIP shim --------------------
 LIBHIP=$ROOT/rays_amd/lib/librays_hip.so

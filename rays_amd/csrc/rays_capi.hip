@@ -1380,6 +1380,14 @@ int rays_hip_set_rho_table(const double* grid, const double* fspl, int n) {
   return 0;
 }
 
+// deposit_rays_kernel keeps 64 rows of n_bins doubles in LDS (rays_deposition.hip): 320 bins are the 160 KB of a CU
+static int refuse_bin_count(int n_bins) {
+  if (n_bins > RAYS_DEP_MAX_BINS)
+    return fail("rays_hip_deposition: n_bins = " + std::to_string(n_bins) + " exceeds the limit of " +
+                std::to_string(RAYS_DEP_MAX_BINS) + " bins (RAYS_DEP_MAX_BINS: one wave's rows must fit in 160 KB of LDS)");
+  return 0;
+}
+
 int rays_hip_deposition_device(const rays_params_t* p, int which, int n_bins, int nray, const double* d_ray_vec,
                                const int32_t* d_npoints, const double* d_initial_ray_power, double* d_work,
                                const double* d_profile_in, double* d_profile_out, void* hip_stream) {
@@ -1395,6 +1403,7 @@ int rays_hip_deposition_device(const rays_params_t* p, int which, int n_bins, in
                                        : (which != RAYS_DEP_PTOTAL_PSI && which != RAYS_DEP_PTOTAL_RHO))
     return fail("initialize_deposition_profiles: unimplemented profile for this equilib_model");  // :162-169, 204-212
   if (n_bins < 1 || nray < 0) return fail("rays_hip_deposition: bad n_bins / nray");
+  if (refuse_bin_count(n_bins)) return 1;
   if (!d_ray_vec || !d_npoints || !d_initial_ray_power || !d_work || !d_profile_out)
     return fail("rays_hip_deposition: null device pointer");
   rays::DevParams D = make_dev_params(*p);
@@ -1429,6 +1438,7 @@ int rays_hip_deposition(const rays_params_t* p, int which, int n_bins, int nray,
   int rc = rays_hip_check_params(p);
   if (rc) return rc;
   if (n_bins < 1 || nray < 0) return fail("rays_hip_deposition: bad n_bins / nray");
+  if (refuse_bin_count(n_bins)) return 1;
   if (nray == 0) {
     if (profile) std::memset(profile, 0, sizeof(double) * (size_t)n_bins);
     return 0;
@@ -1486,6 +1496,7 @@ int rays_hip_deposition_last(const rays_params_t* p, int which, int n_bins, int 
   int rc = rays_hip_check_params(p);
   if (rc) return rc;
   if (n_bins < 1 || nray < 0 || !initial_ray_power || !profile) return fail("rays_hip_deposition_last: bad argument");
+  if (refuse_bin_count(n_bins)) return 1;
   std::vector<KeptBlock> blocks;
   {
     std::lock_guard<std::mutex> lk(g_mu);

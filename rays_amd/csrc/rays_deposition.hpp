@@ -105,7 +105,9 @@ RAYS_DEV void deposit_ray(const DevParams& P, const DepArgs& D, int iray, RowPtr
           const double Q_incrL = delta_Q * (((double)index_low - ix_low) / delta_ix);
           row[index_low - 1] = row[index_low - 1] + Q_incrL;
           const double Q_incrH = delta_Q * ((ix_high - (double)(index_high - 1)) / delta_ix);
-          row[index_high - 1] = row[index_high - 1] + Q_incrH;
+          // x_high just below xmax whose quotient rounds up to n_bins: index_high = n_bins + 1, one element past
+          // the row (the reference updates binned_Q(n_bins + 1) there: undefined)
+          if (index_high <= n_bins) row[index_high - 1] = row[index_high - 1] + Q_incrH;
           for (int i = index_low + 1; i <= index_high - 1; i++) row[i - 1] = row[i - 1] + Q_density;
         }
       }

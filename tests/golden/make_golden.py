@@ -5,7 +5,8 @@ Runs oracle/_ref/rays_ref_dump (the reference RAYS_project hot path compiled fro
 /root/reference by oracle/build_ref.sh, amdflang -O2 -ffp-contract=off) on the namelists in
 configs/, and cuts small fixtures (inputs + expected outputs, data only) from its raw dump.
 Only runs where /root/reference was available to build the binary; the committed .npz files are
-what the tests read.
+what the tests read.  tests/golden/deposition_binner_cases.npz comes from oracle/_ref/ref_binner (the reference's
+binner_real alone) on the synthetic rays of tests/deposition_cases.py.
 
     python tests/golden/make_golden.py [fixture names ...]    (re)generate
     python tests/golden/make_golden.py --check                 regenerate everything into a scratch directory and
@@ -30,6 +31,7 @@ sys.path.insert(0, ROOT)
 from tests.refdump import read_axisym_tables, read_deposition, read_dump  # noqa: E402
 
 REF = os.path.join(ROOT, "oracle", "_ref", "rays_ref_dump")
+REF_BINNER = os.path.join(ROOT, "oracle", "_ref", "ref_binner")
 
 # (fixture name, config, ray subset (None = all), probe stride, n probes kept)
 CASES = [
@@ -157,6 +159,42 @@ def deposition_file_fixture(out_root):
     print("deposition_profiles.gaxi")
 
 
+BINNER_FIXTURE = os.path.join("tests", "golden", "deposition_binner_cases.npz")
+
+
+def binner_fixture(out_root):
+    """tests/golden/deposition_binner_cases.npz: the synthetic rays of tests/deposition_cases.py (every ray on every
+    grid at every bin count) and what the reference's own binner_real makes of them (oracle/_ref/ref_binner =
+    math_functions_lib/bin_to_uniform_grid_m.f90 under oracle/ref_binner_driver.f90): inputs, rows and ierr.  The second
+    list (edge_*: segments the reference is undefined for) carries inputs only."""
+    from tests import deposition_cases as dc
+    out = dict(grids=np.array(dc.GRIDS), n_bins=np.array(dc.N_BINS, dtype=np.int32), families=np.array(dc.FAMILIES))
+    for ig, (xmin, xmax) in enumerate(dc.GRIDS):
+        for nb in dc.N_BINS:
+            x, q, npts = dc.cases(xmin, xmax, nb)
+            if "Q" in out:   # power and point counts of a ray are the same on every grid
+                assert same_bits(out["Q"], q) and same_bits(out["npoints"], npts)
+            out["Q"], out["npoints"] = q, npts
+            out["x_" + dc.key(ig, nb)] = x
+    out["edge_grid"], out["edge_n_bins"], out["edge_x"], out["edge_Q"], out["edge_npoints"] = dc.edge_cases()
+    flat = dc.case_list_of_fixture(out)
+    with tempfile.TemporaryDirectory() as d:
+        dc.write_case_file(os.path.join(d, "cases.bin"), flat)
+        subprocess.run([REF_BINNER, "cases.bin", "rows.bin"], cwd=d, check=True, stdout=subprocess.DEVNULL)
+        rows, ierr = dc.read_result_file(os.path.join(d, "rows.bin"), flat)
+    assert all(np.isfinite(r).all() for r in rows)
+    nray, i = len(out["npoints"]), 0
+    for ig in range(len(dc.GRIDS)):
+        for nb in dc.N_BINS:
+            out["rows_" + dc.key(ig, nb)] = np.stack(rows[i:i + nray])
+            out["ierr_" + dc.key(ig, nb)] = np.array(ierr[i:i + nray], dtype=np.int32)
+            i += nray
+    path = os.path.join(out_root, BINNER_FIXTURE)
+    np.savez_compressed(path, **out)
+    print(f"deposition_binner_cases: {len(flat)} cases of {nray} rays, {len(out['edge_grid'])} undefined-edge rays "
+          f"-> {os.path.getsize(path) / 1e3:.0f} kB")
+
+
 def same_bits(a, b):
     """Two arrays of a fixture: same dtype, shape and bytes (floats compared through their bit patterns)."""
     a, b = np.asarray(a), np.asarray(b)
@@ -184,6 +222,8 @@ def generate(out_root, only=()):
         results_file_fixture(out_root)
     if not only or "deposition_profiles.gaxi" in only:
         deposition_file_fixture(out_root)
+    if not only or "deposition_binner_cases" in only:
+        binner_fixture(out_root)
     host_tabs = {}
     for name, cfg, subset, stride, nprobe in CASES:
         if only and name not in only:
@@ -286,7 +326,7 @@ def check():
     diffs = []
     with tempfile.TemporaryDirectory() as d:
         generate(d)
-        for name in [c[0] + ".npz" for c in CASES]:
+        for name in [c[0] + ".npz" for c in CASES] + [os.path.basename(BINNER_FIXTURE)]:
             a, b = np.load(os.path.join(d, "tests", "golden", name)), np.load(os.path.join(ROOT, "tests", "golden", name))
             if set(a.files) != set(b.files):
                 diffs.append(f"{name}: keys differ: only regenerated {sorted(set(a.files) - set(b.files))}, "
@@ -308,6 +348,8 @@ def main():
     args = sys.argv[1:]
     if not os.path.exists(REF):
         sys.exit("oracle/_ref/rays_ref_dump missing: run `bash oracle/build_ref.sh` first")
+    if not os.path.exists(REF_BINNER):
+        sys.exit("oracle/_ref/ref_binner missing: run `bash oracle/build_ref.sh` first")
     if "--check" in args:
         diffs = check()
         for x in diffs:

@@ -165,6 +165,13 @@ def test_ray_launcher_and_deposition_config_errors_need_no_gpu():
     q.nv, q.damping_model = 7, 0
     with pytest.raises(hip.RaysHipError, match="damping"):
         hip.deposition_device(q, "Ptotal_psi", 100, 1, 1, 1, 1, 1, None, 1)
+    # more bins than one wave's rows have LDS for: refused by name, by all three entries, before any device work
+    with pytest.raises(hip.RaysHipError, match="limit of 320 bins"):
+        hip.deposition_device(ps, "Ptotal_x", 321, 1, 1, 1, 1, 1, None, 1)
+    with pytest.raises(hip.RaysHipError, match="limit of 320 bins"):
+        hip.deposition_host(ps, "Ptotal_x", 321, np.zeros((1, ps.nstep_max + 1, ps.nv)), np.ones(1, dtype=np.int32), np.ones(1))
+    with pytest.raises(hip.RaysHipError, match="limit of 320 bins"):
+        hip.deposition_last(ps, "Ptotal_x", 321, np.ones(1))
     gm, nmlm, pm = load_golden("gold_axisym64_solmag_damp_rk4")   # analytic magnetics: no rho(psiN) in the reference
     with pytest.raises(hip.RaysHipError, match="rho is only implemented"):
         hip.deposition_device(pm, "Ptotal_rho", 100, 1, 1, 1, 1, 1, None, 1)
