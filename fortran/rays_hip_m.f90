@@ -116,6 +116,8 @@
          & RAYS_DIAG_Y = 9, RAYS_DIAG_Z = 10, RAYS_DIAG_N_PAR = 11, RAYS_DIAG_N_PERP = 12, RAYS_DIAG_P_ABSORBED = 13, &
          & RAYS_DIAG_N_IMAG = 14, RAYS_DIAG_XI_0 = 15, RAYS_DIAG_XI_1 = 16, RAYS_DIAG_XI_2 = 17, RAYS_DIAG_RESIDUAL = 18, &
          & RAYS_DIAG_NFIELDS = 19
+    ! layouts of the trajectory arrays handed to rays_hip_ray_diagnostics_packed_device
+    integer(c_int), parameter :: RAYS_DIAG_IN_PADDED = 0, RAYS_DIAG_IN_PACKED = 1
 
     interface
 
@@ -320,6 +322,30 @@
           real(c_double), intent(inout) :: out(*)
           integer(c_int32_t), intent(inout) :: first_bad_point(*)
        end function rays_hip_ray_diagnostics
+
+       ! The packed layout on the device (include/rays_hip.h): d_offsets(0:nray) (int64) = exclusive prefix sum of
+       ! the rays' point counts, the total in d_offsets(nray); asynchronous on hip_stream
+       integer(c_int) function rays_hip_point_offsets_device(nray, nstep_max, d_npoints, d_offsets, hip_stream) &
+                    & bind(C, name='rays_hip_point_offsets_device')
+          import :: c_int, c_ptr
+          integer(c_int), value :: nray, nstep_max
+          type(c_ptr), value :: d_npoints, d_offsets, hip_stream
+       end function rays_hip_point_offsets_device
+
+       ! The diagnostics of the recorded points alone: d_out(out_stride, k), point j (1-based) of ray i at
+       ! d_out(d_offsets(i) + j, k); in_layout = RAYS_DIAG_IN_PADDED (the trace's arrays) or RAYS_DIAG_IN_PACKED
+       ! (ray_vec(nv, total), residual(total)); nothing at or beyond out_stride of a field is written
+       integer(c_int) function rays_hip_ray_diagnostics_packed_device(p, nray, in_layout, d_ray_vec, d_residual, &
+                    & d_npoints, d_offsets, out_stride, fields, d_out, d_first_bad_point, hip_stream) &
+                    & bind(C, name='rays_hip_ray_diagnostics_packed_device')
+          import :: c_int, c_int32_t, c_int64_t, c_ptr, rays_params_t
+          type(rays_params_t), intent(in) :: p
+          integer(c_int), value :: nray, in_layout
+          type(c_ptr), value :: d_ray_vec, d_residual, d_npoints, d_offsets
+          integer(c_int64_t), value :: out_stride
+          integer(c_int32_t), value :: fields
+          type(c_ptr), value :: d_out, d_first_bad_point, hip_stream
+       end function rays_hip_ray_diagnostics_packed_device
 
        ! Replaces the serial launch loops of ray_init_m's launchers (solovev_ray_init_nphi_ntheta_m.f90:
        ! 60-198 etc.): fills rvec0(3,nray_max), rindex_vec0(3,nray_max), ray_pwr_wt(nray_max), nray.

@@ -497,6 +497,33 @@ enum { RAYS_DIAG_S = 0, RAYS_DIAG_NE, RAYS_DIAG_TE_KEV, RAYS_DIAG_MODB, RAYS_DIA
 int rays_hip_ray_diagnostics_device(const rays_params_t* p, int nray, const double* d_ray_vec,
                                     const double* d_residual, const int32_t* d_npoints, uint32_t fields,
                                     double* d_out, int32_t* d_first_bad_point /* may be NULL */, void* hip_stream);
+/* The packed layout on the device: only recorded points, rays in order, points in order -- ray_vec[total][nv],
+ * residual[total], one field [total] -- with the exclusive prefix sum of the rays' point counts to find a ray's run
+ * (what rays_hip_pack_device / rays_hip_unpack_device and the RCCL gather already move).
+ * rays_hip_point_offsets_device computes that prefix sum on the device: d_offsets[i] = sum over the rays before i of
+ * clamp(npoints, 0, nstep_max + 1), i = 0 .. nray, so d_offsets[nray] is the total and the first nray entries are
+ * what rays_hip_pack_device takes; nray = 0 writes the single 0.  Integer sums: exact.  Asynchronous on hip_stream, no
+ * host synchronisation, no memory besides d_offsets (the current device). */
+int rays_hip_point_offsets_device(int nray, int nstep_max, const int32_t* d_npoints,
+                                  int64_t* d_offsets /* [nray + 1] */, void* hip_stream);
+/* The diagnostics in the packed layout: point j (0-based) of ray i lands at d_out[k * out_stride + d_offsets[i] + j],
+ * k counting the set bits of `fields` in enum order as above, and nothing else of d_out is written: there are no zero
+ * slots, and the launched work follows the recorded points (one wave per 64 consecutive packed points).
+ *   in_layout    RAYS_DIAG_IN_PADDED: d_ray_vec / d_residual are the arrays as rays_hip_trace_device left them;
+ *                RAYS_DIAG_IN_PACKED: they are [total][nv] / [total] as rays_hip_pack_device wrote them
+ *   d_offsets    [nray + 1], of rays_hip_point_offsets_device for this d_npoints
+ *   out_stride   the caller's capacity per field, in doubles.  The call does not synchronise, so it cannot compare
+ *                out_stride with d_offsets[nray]: THE KERNEL NEVER STORES AT AN INDEX >= out_stride OF A FIELD, points
+ *                beyond it are dropped.  A caller that does not know the total passes its allocation size per field
+ *                (nray * (nstep_max + 1) always suffices); one that has read d_offsets[nray] passes that.
+ * Same fields, same `fields` semantics, same refusals and same first_bad_point as the padded entry; exact arithmetic
+ * only.  Asynchronous on hip_stream (current device). */
+enum { RAYS_DIAG_IN_PADDED = 0, RAYS_DIAG_IN_PACKED = 1 };
+int rays_hip_ray_diagnostics_packed_device(const rays_params_t* p, int nray, int in_layout,
+        const double* d_ray_vec, const double* d_residual, const int32_t* d_npoints,
+        const int64_t* d_offsets /* [nray + 1] */, int64_t out_stride, uint32_t fields,
+        double* d_out /* [k][out_stride] */, int32_t* d_first_bad_point /* may be NULL */,
+        void* hip_stream);
 /* Host-pointer form: ray_results_m arrays in, out[k][nray][nstep_max+1]; processes the rays in blocks so that the
  * device footprint is bounded whatever nray is (at most 2**21 trajectory slots per block; the environment variable
  * RAYS_HIP_DIAG_BLOCK_RAYS sets the rays per block instead); only recorded points cross PCIe in either direction

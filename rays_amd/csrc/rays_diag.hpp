@@ -134,4 +134,51 @@ struct DiagArgs {
   int* first_bad;        // [nray], zeroed by the launcher; may be null
 };
 
+// ---- the packed form (rays_hip_ray_diagnostics_packed_device): work follows the recorded points ----------------------
+// offsets[0 .. nray] is the exclusive prefix sum of the rays' point counts (rays_hip_point_offsets_device), so that
+// flat index j of the packed arrays is point j - offsets[r] of the ray r with offsets[r] <= j < offsets[r + 1]; rays
+// without points share their offset with the next ray and are never the answer.
+
+// The ray of flat index j, 0 <= j < offsets[nray], by bisection: the largest r in [0, nray) with offsets[r] <= j.
+// (numpy: searchsorted(offsets, j, side = "right") - 1.)  An index outside that range gives 0 or nray - 1.
+RAYS_DEV int diag_locate(const long long* offsets, int nray, long long j) {
+  int lo = 0, hi = nray;  // offsets[lo] <= j (or lo == 0), offsets[hi] > j (or hi == nray)
+  while (hi - lo > 1) {
+    const int mid = lo + (hi - lo) / 2;
+    if (offsets[mid] <= j) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+// The same answer for j >= offsets[r0], found from r0 outwards: doubling strides until a ray starts beyond j, then
+// bisection between the last two probes -- 1 probe where j lies in ray r0, O(log(r - r0)) otherwise, so that a wave
+// whose first point lies in r0 settles its 64 lanes in a few probes however many rays of 0 or 1 points it spans.
+RAYS_DEV int diag_locate_from(const long long* offsets, int nray, int r0, long long j) {
+  int lo = r0, hi = r0 + 1;
+  for (int step = 1; hi < nray && offsets[hi] <= j; step += step) {
+    lo = hi;
+    hi = nray - hi > step ? hi + step : nray;
+  }
+  while (hi - lo > 1) {
+    const int mid = lo + (hi - lo) / 2;
+    if (offsets[mid] <= j) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+// Arguments of the packed kernel.  out[k][out_stride]; flat index j of field k lands at out[k * out_stride + j]; no
+// store at or beyond min(offsets[nray], capacity) of any field, capacity = min(out_stride, nray * npt).
+struct DiagPackedArgs {
+  int nray, npt, nv;     // npt = nstep_max + 1: the row count per ray of the padded input
+  int in_packed;         // ray_vec[total][nv], residual[total] (else the padded arrays of the trace)
+  unsigned fields;
+  const double* ray_vec;
+  const double* residual;
+  const int* npoints;
+  const long long* offsets;  // [nray + 1]
+  long long out_stride, capacity;
+  double* out;
+  int* first_bad;        // [nray], zeroed by the launcher; may be null
+};
+
 }  // namespace rays

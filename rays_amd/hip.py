@@ -33,6 +33,7 @@ EXPORTED_SYMBOLS = (
     "rays_hip_keep_last_result", "rays_hip_deposition_last",
     "rays_hip_set_numerics", "rays_hip_get_numerics",
     "rays_hip_ray_diagnostics_device", "rays_hip_ray_diagnostics",
+    "rays_hip_point_offsets_device", "rays_hip_ray_diagnostics_packed_device",
 )
 
 _lib = None
@@ -135,6 +136,11 @@ def load():
         lib.rays_hip_ray_diagnostics_device.argtypes = [pp, C.c_int, vp, vp, vp, C.c_uint32, vp, vp, vp]
         lib.rays_hip_ray_diagnostics.restype = C.c_int
         lib.rays_hip_ray_diagnostics.argtypes = [pp, C.c_int, dp, dp, ip, C.c_uint32, dp, ip]
+        lib.rays_hip_point_offsets_device.restype = C.c_int
+        lib.rays_hip_point_offsets_device.argtypes = [C.c_int, C.c_int, vp, vp, vp]
+        lib.rays_hip_ray_diagnostics_packed_device.restype = C.c_int
+        lib.rays_hip_ray_diagnostics_packed_device.argtypes = [pp, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int64, C.c_uint32,
+                                                               vp, vp, vp]
     _lib = lib
     return lib
 
@@ -313,6 +319,83 @@ def ray_diagnostics_device(p: RaysParams, nray: int, d_ray_vec: int, d_residual:
                                                   d_first_bad_point or None, stream or None),
            "rays_hip_ray_diagnostics_device")
     return names
+
+
+DIAG_IN_PADDED, DIAG_IN_PACKED = 0, 1   # RAYS_DIAG_IN_* of include/rays_hip.h
+
+
+def point_offsets_device(nray: int, nstep_max: int, d_npoints: int, d_offsets: int, stream: int = 0):
+    """rays_hip_point_offsets_device: d_offsets[0 .. nray] (int64) = exclusive prefix sum of clamp(npoints, 0,
+    nstep_max + 1), the total in d_offsets[nray]; asynchronous on `stream`."""
+    _check(load().rays_hip_point_offsets_device(int(nray), int(nstep_max), d_npoints or None, d_offsets or None,
+                                                stream or None), "rays_hip_point_offsets_device")
+
+
+def ray_diagnostics_packed_device(p: RaysParams, nray: int, d_ray_vec: int, d_residual: int, d_npoints: int,
+                                  d_offsets: int, out_stride: int, fields, d_out: int, d_first_bad_point: int = 0,
+                                  stream: int = 0, packed_input: bool = False):
+    """rays_hip_ray_diagnostics_packed_device on device pointers: d_out[k][out_stride], point j of ray i at
+    d_out[k][d_offsets[i] + j], nothing else written and nothing at or beyond out_stride of a field; d_ray_vec /
+    d_residual are the padded arrays of the trace, or with packed_input the packed ones of pack_device.  Asynchronous
+    on `stream`.  Returns the names in DIAG_FIELDS order."""
+    ensure_tables(p)
+    mask, names = diag_field_mask(fields)
+    _check(load().rays_hip_ray_diagnostics_packed_device(
+        C.byref(p), int(nray), DIAG_IN_PACKED if packed_input else DIAG_IN_PADDED, d_ray_vec, d_residual, d_npoints,
+        d_offsets, int(out_stride), mask, d_out, d_first_bad_point or None, stream or None),
+        "rays_hip_ray_diagnostics_packed_device")
+    return names
+
+
+def diag_offsets(npoints, nstep_max=None):
+    """The host restatement of point_offsets_device: int64[nray + 1]."""
+    n = np.asarray(npoints, dtype=np.int64)
+    n = np.clip(n, 0, None if nstep_max is None else int(nstep_max) + 1)
+    return np.concatenate([np.zeros(1, dtype=np.int64), np.cumsum(n, dtype=np.int64)])
+
+
+def diag_unpack(packed, offsets, npt: int):
+    """Host scatter of a packed diagnostics dictionary ({field: array[total]}, "offsets", "first_bad_point" as
+    DeviceTrace.diagnostics(packed=True) / RayResults.diagnostics(packed=True) return it, as numpy arrays) into the
+    padded one: {field: array[nray][npt]} with +0.0 wherever no point was recorded, "first_bad_point" passed on."""
+    offsets = np.asarray(offsets, dtype=np.int64)
+    nray = len(offsets) - 1
+    cnt = np.diff(offsets)
+    if nray and (cnt.min() < 0 or cnt.max() > npt):
+        raise ValueError("diag_unpack: `offsets` is not the prefix sum of point counts within 0 .. npt")
+    total = int(offsets[-1])
+    live = np.arange(npt)[None, :] < cnt[:, None]
+    out = {}
+    for k, a in packed.items():
+        if k == "offsets":
+            continue
+        a = np.asarray(a)
+        if k == "first_bad_point":
+            out[k] = a
+            continue
+        if a.ndim != 1 or len(a) < total:
+            raise ValueError(f"diag_unpack: {k} has shape {a.shape}, expected [>= {total}]")
+        full = np.zeros((nray, npt))
+        full[live] = a[:total]
+        out[k] = full
+    return out
+
+
+def diag_pack(padded, npoints):
+    """The inverse of diag_unpack: {field: array[nray][npt]} -> {field: array[total]} plus "offsets"."""
+    npoints = np.asarray(npoints)
+    out = {}
+    npt = None
+    for k, a in padded.items():
+        a = np.asarray(a)
+        if k == "first_bad_point":
+            out[k] = a
+            continue
+        npt = a.shape[1]
+        live = np.arange(npt)[None, :] < np.clip(npoints, 0, npt)[:, None]
+        out[k] = np.ascontiguousarray(a[live])
+    out["offsets"] = diag_offsets(npoints, None if npt is None else npt - 1)
+    return out
 
 
 def ray_diagnostics_host(p: RaysParams, ray_vec, residual, npoints, fields=None, block_rays: int = 0):

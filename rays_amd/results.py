@@ -415,7 +415,9 @@ def write_ray_diagnostics_NC(path: str, diag: Dict[str, Any], npoints, dim_v_vec
     lists reversed into the file's C order: [number_of_rays][max_number_of_points]); global attribute RAYS_run_label
     (:454).  diag: {field name: array[nray][>= maxval(npoints)]} as hip.ray_diagnostics_host / RayResults.diagnostics
     return it; the arrays are cut to maxval(npoints), the max_number_of_points of the results file the reference's
-    processors read (ray_results_m.f90:202)."""
+    processors read (ray_results_m.f90:202).  A packed dictionary (diagnostics(packed=True): {field name: array[>=
+    total]} with "offsets") is scattered into the file's padded variables here on the host, +0.0 where no point was
+    recorded: the file is byte for byte the one of the padded dictionary."""
     npoints = np.ascontiguousarray(npoints, dtype=np.int32)
     nray = len(npoints)
     npt = int(npoints.max()) if nray else 0
@@ -428,6 +430,13 @@ def write_ray_diagnostics_NC(path: str, diag: Dict[str, Any], npoints, dim_v_vec
     missing = [n for n in names if n not in diag]
     if missing:
         raise ValueError(f"write_ray_diagnostics_NC: fields {missing} are not in `diag`")
+    if "offsets" in diag:
+        from .hip import diag_offsets, diag_unpack
+
+        offsets = np.asarray(diag["offsets"], dtype=np.int64)
+        if len(offsets) != nray + 1 or not np.array_equal(offsets, diag_offsets(npoints)):
+            raise ValueError("write_ray_diagnostics_NC: the packed dictionary's offsets are not those of `npoints`")
+        diag = diag_unpack({n: diag[n] for n in names}, offsets, npt)
     R, P = "number_of_rays", "max_number_of_points"
     dims = [(R, nray), (P, npt), ("dim_v_vector", int(dim_v_vector)), ("d8", 8)]
     variables = [("date_vector", "int", ("d8",), np.asarray(date_vector, dtype=np.int32)), ("npoints", "int", (R,), npoints)]

@@ -50,14 +50,49 @@ class RayResults:
     def total_steps(self) -> int:
         return int(np.maximum(self.npoints.astype(np.int64) - 1, 0).sum())
 
-    def diagnostics(self, params: RaysParams, fields=None) -> Dict[str, np.ndarray]:
+    def diagnostics(self, params: RaysParams, fields=None, packed: bool = False) -> Dict[str, np.ndarray]:
         """The post-processors' ray_detailed_diagnostics (axisym_toroid_processor_m.f90:252-482) of these host arrays,
         evaluated on the GPU (hip.ray_diagnostics_host): {field name: array[nray][nstep_max+1]} for `fields`
         (hip.DIAG_FIELDS; None = all), plus "first_bad_point"[nray] (include/rays_hip.h).  `params`: the run's
-        parameter block (a RayResults does not hold it)."""
+        parameter block (a RayResults does not hold it).
+        packed=True: {field name: array[sum(npoints)]}, the recorded points alone, rays in order, plus "offsets"
+        (int64[nray + 1], hip.diag_offsets) and "first_bad_point" -- the packed device entry on the packed arrays
+        (hip.ray_diagnostics_packed_device, one upload of the recorded points, no blocks)."""
+        if packed:
+            return self._diagnostics_packed(params, fields)
         out, bad = hip.ray_diagnostics_host(params, self.ray_vec, self.residual, self.npoints, fields)
         out["first_bad_point"] = bad
         return out
+
+    def _diagnostics_packed(self, params: RaysParams, fields) -> Dict[str, np.ndarray]:
+        import torch
+
+        _, names = hip.diag_field_mask(fields)
+        nray, npt = len(self.npoints), params.nstep_max + 1
+        if self.ray_vec.shape != (nray, npt, params.nv) or self.residual.shape != (nray, npt):
+            raise ValueError("RayResults.diagnostics: arrays do not have the ray_results_m shapes of this run")
+        off = hip.diag_offsets(self.npoints, params.nstep_max)
+        total = int(off[-1])
+        live = np.arange(npt)[None, :] < np.diff(off)[:, None]
+        d_rv = torch.as_tensor(np.ascontiguousarray(self.ray_vec[live])).cuda()
+        d_res = torch.as_tensor(np.ascontiguousarray(self.residual[live])).cuda()
+        d_np = torch.as_tensor(np.ascontiguousarray(self.npoints, dtype=np.int32)).cuda()
+        d_off = torch.empty(nray + 1, dtype=torch.int64, device="cuda")
+        out = torch.empty((len(names), total), dtype=torch.float64, device="cuda")
+        bad = torch.empty(nray, dtype=torch.int32, device="cuda")
+        stream = torch.cuda.current_stream().cuda_stream
+        hip.point_offsets_device(nray, params.nstep_max, d_np.data_ptr(), d_off.data_ptr(), stream)
+        if total:
+            hip.ray_diagnostics_packed_device(params, nray, d_rv.data_ptr(), d_res.data_ptr(), d_np.data_ptr(),
+                                              d_off.data_ptr(), total, names, out.data_ptr(), bad.data_ptr(), stream,
+                                              packed_input=True)
+        else:   # no recorded point: the arrays are empty, and the entry refuses their null pointers
+            bad.zero_()
+        h = out.cpu().numpy()
+        res: Dict[str, np.ndarray] = {n: h[k] for k, n in enumerate(names)}
+        res["offsets"] = d_off.cpu().numpy()
+        res["first_bad_point"] = bad.cpu().numpy()
+        return res
 
 
 def load_axisym_tables(namelist_path: str, nml: Dict[str, Dict[str, Any]]) -> Optional[Dict[str, Any]]:
@@ -177,12 +212,35 @@ class DeviceTrace:
                          self.end_residuals.data_ptr(), self.max_residuals.data_ptr(),
                          stream=stream, zero_fill=zero_fill)
 
-    def diagnostics(self, fields=None) -> Dict[str, Any]:
+    def diagnostics(self, fields=None, packed: bool = False) -> Dict[str, Any]:
         """ray_detailed_diagnostics of the trace as it lies on the device (hip.ray_diagnostics_device): {field name:
         tensor[nray][nstep_max+1]} for `fields` (hip.DIAG_FIELDS; None = all) -- views of one [k][nray][nstep_max+1]
-        block -- plus "first_bad_point"[nray] (int32).  Asynchronous on the current torch stream, behind launch()."""
+        block -- plus "first_bad_point"[nray] (int32).  Asynchronous on the current torch stream, behind launch().
+        packed=True (hip.ray_diagnostics_packed_device on the padded trace arrays): {field name: tensor[total]}, the
+        recorded points alone, rays in order -- views of one [k][total] block, no zero slots -- plus "offsets"
+        (int64[nray + 1] on the device: point j of ray i is element offsets[i] + j) and "first_bad_point".  To
+        allocate k * total doubles instead of k * nray * (nstep_max + 1) it reads offsets[nray] once before
+        allocating: ONE 8-BYTE SYNCHRONISING COPY behind launch(); the diagnostics kernel itself is asynchronous."""
         t = self.torch
         _, names = hip.diag_field_mask(fields)
+        if packed:
+            with t.cuda.device(self.device):
+                stream = t.cuda.current_stream(self.device).cuda_stream
+                off = t.empty(self.nray + 1, dtype=t.int64, device=self.device)
+                hip.point_offsets_device(self.nray, self.params.nstep_max, self.npoints.data_ptr(), off.data_ptr(), stream)
+                total = int(off[self.nray].item())   # the one synchronising copy
+                out = t.empty((len(names), total), dtype=t.float64, device=self.device)
+                bad = t.empty(self.nray, dtype=t.int32, device=self.device)
+                if total:
+                    hip.ray_diagnostics_packed_device(self.params, self.nray, self.ray_vec.data_ptr(),
+                                                      self.residual.data_ptr(), self.npoints.data_ptr(), off.data_ptr(),
+                                                      total, names, out.data_ptr(), bad.data_ptr(), stream)
+                else:   # no recorded point: `out` is empty, and the entry refuses its null pointer
+                    bad.zero_()
+            res = {n: out[k] for k, n in enumerate(names)}
+            res["offsets"] = off
+            res["first_bad_point"] = bad
+            return res
         with t.cuda.device(self.device):
             out = t.empty((len(names), self.nray, self.params.nstep_max + 1), dtype=t.float64, device=self.device)
             bad = t.empty(self.nray, dtype=t.int32, device=self.device)

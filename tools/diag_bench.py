@@ -6,7 +6,11 @@
 For the headline fan (configs/cfg3b_solovev64k_rk4.in) and cfg 5b (configs/cfg5b_axisym256k_rk4_damp.in): trace on the
 device (exact numerics), then HIP events around `reps` back-to-back launches of (a) the exact trace pass, (b) the
 diagnostics with all nineteen fields, (c) the diagnostics without N_IMAG (no deriv_cold / damping), alternating the
-three so that they see the same clocks.  Each figure is the median over the repetitions of one launch's time.  Points/s
+three so that they see the same clocks, and with them the PACKED form (rays_hip_ray_diagnostics_packed_device, out_stride
+= the total read once beforehand) in both input layouts -- (d), (e) on the padded trace arrays, (f), (g) on the arrays
+packed once by rays_hip_pack_device -- with all nineteen fields and without N_IMAG.  Each figure is the median over the
+repetitions of one launch's time; `packed_speedup` sets the packed form against the padded one of the same process and
+against the ratio of their algorithmic bytes (the expectation: the stores dominate, so the time follows them).  Points/s
 and the algorithmic bytes (what the kernel must read and write: nv + 1 doubles in per recorded point, one double out per
 selected field per SLOT, npoints once) are computed from the shapes here; the FETCH_SIZE / WRITE_SIZE to set against
 them come from a rocprofv3 --pmc run of --one CONFIG --pmc-pass (one launch of each variant, nothing timed).
@@ -48,7 +52,27 @@ def one(cfg, reps, warmup, pmc_pass):
         hip.ray_diagnostics_device(p, tr.nray, tr.ray_vec.data_ptr(), tr.residual.data_ptr(), tr.npoints.data_ptr(),
                                    fields, out.data_ptr(), bad.data_ptr(), stream=stream)
 
-    variants = {"trace_exact": lambda: tr.launch(), "diag_all": lambda: diag(None), "diag_no_n_imag": lambda: diag(no_imag)}
+    # the packed form: offsets and the total once, outside the timed launches; the packed input made once
+    off = torch.empty(tr.nray + 1, dtype=torch.int64, device="cuda")
+    hip.point_offsets_device(tr.nray, p.nstep_max, tr.npoints.data_ptr(), off.data_ptr(), stream)
+    total = int(off[-1].item())
+    assert total == points
+    pv = torch.empty((total, p.nv), dtype=torch.float64, device="cuda")
+    pr = torch.empty(total, dtype=torch.float64, device="cuda")
+    hip.pack_device(tr.nray, p.nv, p.nstep_max, tr.npoints.data_ptr(), off.data_ptr(), tr.ray_vec.data_ptr(),
+                    tr.residual.data_ptr(), pv.data_ptr(), pr.data_ptr(), stream)
+    pout = torch.empty((19, total), dtype=torch.float64, device="cuda")
+
+    def packed(fields, packed_input):
+        rv, rs = (pv, pr) if packed_input else (tr.ray_vec, tr.residual)
+        hip.ray_diagnostics_packed_device(p, tr.nray, rv.data_ptr(), rs.data_ptr(), tr.npoints.data_ptr(), off.data_ptr(),
+                                          total, fields, pout.data_ptr(), bad.data_ptr(), stream, packed_input=packed_input)
+
+    variants = {"trace_exact": lambda: tr.launch(), "diag_all": lambda: diag(None), "diag_no_n_imag": lambda: diag(no_imag),
+                "packed_all": lambda: packed(None, False), "packed_no_n_imag": lambda: packed(no_imag, False),
+                "packed_in_all": lambda: packed(None, True), "packed_in_no_n_imag": lambda: packed(no_imag, True),
+                "point_offsets": lambda: hip.point_offsets_device(tr.nray, p.nstep_max, tr.npoints.data_ptr(),
+                                                                  off.data_ptr(), stream)}
     if pmc_pass:
         for fn in variants.values():
             fn()
@@ -77,6 +101,17 @@ def one(cfg, reps, warmup, pmc_pass):
         res[k + "_points_per_s"] = points / (ms * 1e-3)
         rd, wr = 8 * (p.nv + 1) * points + 4 * tr.nray, 8 * nf * slots
         res[k + "_algorithmic_bytes"] = dict(read=rd, write=wr, gb_per_s=(rd + wr) / (ms * 1e-3) / 1e9)
+    for k, nf in (("packed_all", 19), ("packed_no_n_imag", 18), ("packed_in_all", 19), ("packed_in_no_n_imag", 18)):
+        ms = res[k + "_ms"]["median"]
+        res[k + "_points_per_s"] = points / (ms * 1e-3)
+        rd = 8 * (p.nv + 1) * points + 8 * (tr.nray + 1) + (0 if "_in_" in k else 4 * tr.nray)
+        wr = 8 * nf * points
+        res[k + "_algorithmic_bytes"] = dict(read=rd, write=wr, gb_per_s=(rd + wr) / (ms * 1e-3) / 1e9)
+        ref = "diag_all" if nf == 19 else "diag_no_n_imag"
+        rb = res[ref + "_algorithmic_bytes"]
+        speedup, expected = res[ref + "_ms"]["median"] / ms, (rb["read"] + rb["write"]) / (rd + wr)
+        res[k + "_packed_speedup"] = dict(over=ref, measured=speedup, ratio_of_algorithmic_bytes=expected,
+                                          achieved_fraction=speedup / expected)
     res["first_bad_points"] = int((bad != 0).sum().item())
     return res
 
