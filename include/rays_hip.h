@@ -177,6 +177,12 @@ int rays_hip_init(int ngpu);
  * device, each with its own host thread, stream and staging buffers, so one slot's device-to-host
  * copy overlaps another's trace.  Returns n, or a negative value on failure. */
 int rays_hip_init_devices(int n, const int* device_ids);
+/* Returns everything the library holds on the devices and in pinned host memory to the driver: the RCCL
+ * communicators, the kept and the gathered result (their pointers are invalid from here on), the per-stream
+ * workspaces and scratch blocks, the device copies of the tables, the staging buffers, the cached blocks and
+ * streams, the device list.  Call it with no other entry running.  The library may be used again afterwards and
+ * then behaves as on first use: the tables set so far are uploaded again from their host copies, and the
+ * numerics setting and the rays_hip_keep_last_result switch are unchanged.  Returns 0. */
 int rays_hip_finalize(void);
 int rays_hip_device_count(void);
 /* sizeof(rays_params_t) as compiled into the library: lets a foreign-language binding (ctypes,

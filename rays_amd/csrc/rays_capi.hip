@@ -3,6 +3,10 @@
 // Host side of the drop-in boundary for `call trace_rays` (RAYS_project/RAYS_lib/ray_tracing.f90).
 // No oracle, no CPU fallback: every entry point either runs the HIP kernels or fails with an
 // error message.
+//
+// Every device resource behind these entries has one owner in rays_capi_resources.hpp -- the workspaces per (device,
+// stream), the tables' device copies, the block cache, the buffers of one call -- and rays_hip_finalize releases them
+// all; an entry that fails returns at once and its DeviceBuffers gives the call's blocks back.
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
 
@@ -13,6 +17,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
 #include <map>
 #include <mutex>
 #include <string>
@@ -24,6 +29,7 @@
 #include "rays_ray_init.hpp"
 #include "rays_deposition.hpp"
 #include "rays_capi_internal.hpp"
+#include "rays_capi_resources.hpp"
 
 namespace rays {
 #define RAYS_DECL_ENTRIES(s, e, d) \
@@ -64,6 +70,7 @@ __global__ void probe_kernel(const DevParams P, int eq, int ns, int nv, int n, c
 }  // namespace rays
 
 namespace {
+using namespace rays::host;
 
 thread_local std::string g_err;
 std::mutex g_mu;
@@ -78,11 +85,13 @@ int hip_fail(hipError_t e, const char* what) {
   g_err = std::string(what) + ": " + hipGetErrorString(e);
   return 2;
 }
-#define HIP_TRY(call)                              \
-  do {                                             \
-    hipError_t e_ = (call);                        \
-    if (e_ != hipSuccess) return hip_fail(e_, #call); \
+// `what`: the HIP call behind a call of a resource owner (rays_capi_resources.hpp; these report a bare hipError_t)
+#define HIP_TRY_AS(what, call)                       \
+  do {                                               \
+    hipError_t e_ = (call);                          \
+    if (e_ != hipSuccess) return hip_fail(e_, what); \
   } while (0)
+#define HIP_TRY(call) HIP_TRY_AS(#call, call)
 
 struct FlagText {
   int code;
@@ -181,56 +190,31 @@ const rays::KernelEntry* find_kernel(const rays_params_t& p, long long nray = 0,
   return found;
 }
 
-// Z-function spline table (host copy + lazily uploaded per-device copies)
-struct ZfunTable {
-  std::vector<double> host;  // [nx][4]
+// Z-function spline table: host = fspl[nx][4].  (g_mu guards the three tables and their shapes.)
+struct ZfunTable : DeviceTable {
   int nx = 0;
   double xmin = 0., xmax = 0.;
-  unsigned long long version = 0;
-};
-ZfunTable g_zfun;
-struct ZfunDevice {
-  double* ptr = nullptr;
-  unsigned long long version = 0;
-};
-std::vector<ZfunDevice> g_zfun_dev;
+} g_zfun;
 
 int get_zfun_device(const double** out) {
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
   std::lock_guard<std::mutex> lk(g_mu);
   if (g_zfun.nx <= 0) return fail("damping_model = 'damp_fund_ECH' needs rays_hip_set_zfun_table() first");
-  if ((int)g_zfun_dev.size() <= dev) g_zfun_dev.resize(dev + 1);
-  ZfunDevice& z = g_zfun_dev[dev];
-  if (z.version != g_zfun.version) {
-    if (z.ptr) (void)hipFree(z.ptr);
-    z.ptr = nullptr;
-    HIP_TRY(hipMalloc(&z.ptr, sizeof(double) * g_zfun.host.size()));
-    HIP_TRY(hipMemcpy(z.ptr, g_zfun.host.data(), sizeof(double) * g_zfun.host.size(), hipMemcpyHostToDevice));
-    z.version = g_zfun.version;
-  }
-  *out = z.ptr;
+  HIP_TRY_AS("hipMalloc / hipMemcpy (Z-function table)", g_zfun.device_ptr(out));
   return 0;
 }
 
-// axisym_toroid spline tables: one packed host copy, lazily uploaded per device
-struct AxisymHost {
-  std::vector<double> blob;  // all arrays back to back
+// axisym_toroid spline tables: host = all arrays back to back
+struct AxisymTable : DeviceTable {
   size_t off[11] = {0};      // r_grid z_grid psi rb_grid rb_fspl ne_grid ne_fspl te_grid te_fspl ti_grid ti_fspl
   int nr = 0, nz = 0, n_rb = 0, n_ne = 0, n_te = 0, n_ti = 0;
   bool lin = false;          // tables of 'eqdsk_magnetics_lin_interp': psi = Psi(nr, nz) raw, rb_fspl = T(nr), rb_grid empty
   double dR = 0., dZ = 0.;
-  unsigned long long version = 0;
-};
-AxisymHost g_axi;
-std::vector<ZfunDevice> g_axi_dev;
+} g_axi;
 
 int get_axisym_device(rays::DevParams* D) {
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
   std::lock_guard<std::mutex> lk(g_mu);
   const bool analytic = D->a_mag_model == RAYS_AXI_MAG_SOLOVEV;  // 'solovev_magnetics': no psi / RBphi tables
-  if (analytic && g_axi.blob.empty()) {
+  if (analytic && g_axi.host.empty()) {
     D->a_nr = D->a_nz = D->a_n_rb = D->a_n_ne = D->a_n_te = D->a_n_ti = 0;
     D->a_r_grid = D->a_z_grid = D->a_psi_fspl = D->a_rb_grid = D->a_rb_fspl = nullptr;
     D->a_ne_grid = D->a_ne_fspl = D->a_te_grid = D->a_te_fspl = D->a_ti_grid = D->a_ti_fspl = nullptr;
@@ -244,16 +228,8 @@ int get_axisym_device(rays::DevParams* D) {
     return fail("magnetics_model = 'eqdsk_magnetics_lin_interp' needs rays_hip_set_eqdsk_lin_tables() first");
   if (!analytic && !lin && (g_axi.lin || g_axi.nr <= 1 || g_axi.nz <= 1 || g_axi.n_rb <= 1))
     return fail("equilib_model = 'axisym_toroid' needs rays_hip_set_axisym_tables() first");
-  if ((int)g_axi_dev.size() <= dev) g_axi_dev.resize(dev + 1);
-  ZfunDevice& z = g_axi_dev[dev];
-  if (z.version != g_axi.version) {
-    if (z.ptr) (void)hipFree(z.ptr);
-    z.ptr = nullptr;
-    HIP_TRY(hipMalloc(&z.ptr, sizeof(double) * g_axi.blob.size()));
-    HIP_TRY(hipMemcpy(z.ptr, g_axi.blob.data(), sizeof(double) * g_axi.blob.size(), hipMemcpyHostToDevice));
-    z.version = g_axi.version;
-  }
-  const double* b = z.ptr;
+  const double* b = nullptr;
+  HIP_TRY_AS("hipMalloc / hipMemcpy (axisym tables)", g_axi.device_ptr(&b));
   D->a_nr = g_axi.nr; D->a_nz = g_axi.nz; D->a_n_rb = g_axi.n_rb;
   D->a_n_ne = g_axi.n_ne; D->a_n_te = g_axi.n_te; D->a_n_ti = g_axi.n_ti;
   D->a_r_grid = b + g_axi.off[0]; D->a_z_grid = b + g_axi.off[1]; D->a_psi_fspl = b + g_axi.off[2];
@@ -261,18 +237,30 @@ int get_axisym_device(rays::DevParams* D) {
   D->a_ne_grid = b + g_axi.off[5]; D->a_ne_fspl = b + g_axi.off[6];
   D->a_te_grid = b + g_axi.off[7]; D->a_te_fspl = b + g_axi.off[8];
   D->a_ti_grid = b + g_axi.off[9]; D->a_ti_fspl = b + g_axi.off[10];
-  D->a_tab1d_doubles = (int)(g_axi.blob.size() - g_axi.off[3]);  // rb .. ti: contiguous at the end of the blob
+  D->a_tab1d_doubles = (int)(g_axi.host.size() - g_axi.off[3]);  // rb .. ti: contiguous at the end of the blob
   for (int k = 0; k < 8; k++) D->a_tab_off[k] = (int)(g_axi.off[3 + k] - g_axi.off[3]);
   D->a_lin_dR = g_axi.dR;
   D->a_lin_dZ = g_axi.dZ;
   D->a_lds_tab = 0;
   D->a_lds_rz = 0;
   {
-    const double* h = g_axi.blob.data();  // the host image of the same blob
+    const double* h = g_axi.host.data();  // the host image of the same blob
     const auto at = [&](int k, int n) { return n > 1 ? h + g_axi.off[k] : nullptr; };
     set_spline_axes(*D, at(0, g_axi.nr), at(1, g_axi.nz), at(3, g_axi.n_rb), at(5, g_axi.n_ne), at(7, g_axi.n_te),
                     at(9, g_axi.n_ti));
   }
+  return 0;
+}
+
+// rho(psiN) spline table: host = grid[n] then fspl[n][4]
+struct RhoTable : DeviceTable {
+  int n = 0;
+} g_rho;
+int get_rho_device(const double** out, int* n) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (g_rho.n < 2) return fail("Ptotal_rho needs rays_hip_set_rho_table() first");
+  HIP_TRY_AS("hipMalloc / hipMemcpy (rho table)", g_rho.device_ptr(out));
+  *n = g_rho.n;
   return 0;
 }
 
@@ -288,12 +276,12 @@ struct DeviceWorkspace {
   bool used[kCounterSlots] = {};
   int next = 0;
 };
-DeviceWorkspace g_ws[16];
+DeviceWorkspace g_ws[kMaxDevices];
 
 int get_counter(unsigned int** out, int* slot_out) {
   int dev = 0;
   HIP_TRY(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 16) return fail("rays_hip: device ordinal >= 16");
+  if (dev < 0 || dev >= kMaxDevices) return fail("rays_hip: device ordinal >= 16");
   hipEvent_t wait_for = nullptr;
   {
     std::lock_guard<std::mutex> lk(g_mu);
@@ -313,53 +301,13 @@ int get_counter(unsigned int** out, int* slot_out) {
   }
   return 0;
 }
-// Workspace of the SG kernels' upper storage tiers (TraceArgs::sg_far), one per (device, stream): launches on a
-// stream run one after another, so they may share it; grown on demand, released by rays_hip_finalize.
-struct SgWorkspace {
-  double* ptr = nullptr;
-  size_t bytes = 0;
-};
-std::map<std::pair<int, hipStream_t>, SgWorkspace> g_sg_ws;
-int get_sg_workspace(hipStream_t stream, size_t bytes, double** out) {
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lk(g_mu);
-  SgWorkspace& w = g_sg_ws[std::make_pair(dev, stream)];
-  if (w.bytes < bytes) {
-    if (w.ptr) {
-      HIP_TRY(hipStreamSynchronize(stream));  // an earlier launch on this stream may still use the old block
-      (void)hipFree(w.ptr);
-    }
-    w.ptr = nullptr;
-    w.bytes = 0;
-    HIP_TRY(hipMalloc(&w.ptr, bytes));
-    w.bytes = bytes;
-  }
-  *out = w.ptr;
-  return 0;
-}
-
-// State of the "long rays first" hand-out order of the RK4 kernels (TraceArgs::sched; rays_trace.hpp: take_rays), one
-// block per (device, stream) like the SG workspace.
-std::map<std::pair<int, hipStream_t>, SgWorkspace> g_sched_ws;
-int get_sched_workspace(hipStream_t stream, size_t bytes, unsigned int** out) {
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lk(g_mu);
-  SgWorkspace& w = g_sched_ws[std::make_pair(dev, stream)];
-  if (w.bytes < bytes) {
-    if (w.ptr) {
-      HIP_TRY(hipStreamSynchronize(stream));
-      (void)hipFree(w.ptr);
-    }
-    w.ptr = nullptr;
-    w.bytes = 0;
-    HIP_TRY(hipMalloc(&w.ptr, bytes));
-    w.bytes = bytes;
-  }
-  *out = reinterpret_cast<unsigned int*>(w.ptr);
-  return 0;
-}
+// One block per (device, stream) each, grown on demand, released by rays_hip_finalize:
+StreamWorkspace g_sg_ws;     // the SG kernels' upper storage tiers (TraceArgs::sg_far); a tolerance launch's summaries
+StreamWorkspace g_sched_ws;  // state of the "long rays first" hand-out order of the RK4 kernels (TraceArgs::sched;
+                             // rays_trace.hpp: take_rays)
+// scratch of rays_hip_ode_step_device (a host that calls the entry per time step would otherwise pay four hipMalloc /
+// hipFree per call)
+StreamWorkspace g_step_ws;
 // Neighbourhood size of that order: every second row of 64 rays is traced first (cfg 5b: 4.05 | 3.26 | 3.34 | 3.42 ms for
 // index order | 2 | 4 | 8; the model of tools/refill_model.py agrees: the more pilots, the better the later half is
 // ordered).  RAYS_HIP_RAY_ORDER=index hands the rays out in index order instead (for A/B measurements; the results
@@ -431,8 +379,8 @@ int set_axisym_tables_impl(const rays_axisym_tables_t* t, bool lin, double dR, d
       (t->n_ti > 0 && (!t->ti_grid || !t->ti_fspl)))
     return fail("rays_hip_set_axisym_tables: profile table pointers missing");
   std::lock_guard<std::mutex> lk(g_mu);
-  AxisymHost& h = g_axi;
-  h.blob.clear();
+  AxisymTable& h = g_axi;
+  h.host.clear();
   const double* src[11] = {t->r_grid, t->z_grid, t->psi_fspl, t->rb_grid, t->rb_fspl, t->ne_grid, t->ne_fspl,
                            t->te_grid, t->te_fspl, t->ti_grid, t->ti_fspl};
   // ('eqdsk_magnetics_lin_interp': raw Psi(nr, nz) and T(nr) in the psi / rb_fspl slots, no rb_grid)
@@ -441,9 +389,9 @@ int set_axisym_tables_impl(const rays_axisym_tables_t* t, bool lin, double dR, d
                           (size_t)(t->n_te > 0 ? t->n_te : 0), (size_t)4 * (t->n_te > 0 ? t->n_te : 0),
                           (size_t)(t->n_ti > 0 ? t->n_ti : 0), (size_t)4 * (t->n_ti > 0 ? t->n_ti : 0)};
   for (int k = 0; k < 11; k++) {
-    h.off[k] = h.blob.size();
-    if (len[k]) h.blob.insert(h.blob.end(), src[k], src[k] + len[k]);
-    while (h.blob.size() % 16) h.blob.push_back(0.);  // keep every table 128-B aligned
+    h.off[k] = h.host.size();
+    if (len[k]) h.host.insert(h.host.end(), src[k], src[k] + len[k]);
+    while (h.host.size() % 16) h.host.push_back(0.);  // keep every table 128-B aligned
   }
   h.nr = t->nr; h.nz = t->nz; h.n_rb = t->n_rb;
   h.n_ne = t->n_ne > 0 ? t->n_ne : 0; h.n_te = t->n_te > 0 ? t->n_te : 0; h.n_ti = t->n_ti > 0 ? t->n_ti : 0;
@@ -477,7 +425,7 @@ int rays_hip_init(int ngpu) {
     return -1;
   }
   if (ngpu <= 0 || ngpu > n) ngpu = n;
-  if (ngpu > 16) ngpu = 16;
+  if (ngpu > kMaxDevices) ngpu = kMaxDevices;
   std::lock_guard<std::mutex> lk(g_mu);
   g_devices.clear();
   for (int i = 0; i < ngpu; i++) g_devices.push_back(i);
@@ -491,7 +439,7 @@ int rays_hip_init_devices(int n, const int* device_ids) {
     g_err = "rays_hip_init_devices: no HIP device visible";
     return -1;
   }
-  if (n <= 0 || n > 16 || !device_ids) {
+  if (n <= 0 || n > kMaxDevices || !device_ids) {
     g_err = "rays_hip_init_devices: 1..16 device slots";
     return -1;
   }
@@ -506,42 +454,29 @@ int rays_hip_init_devices(int n, const int* device_ids) {
   return n;
 }
 
-static void release_cached_device_blocks();
 static void rccl_close_all();
-static void release_step_scratch();
 static void drop_kept_result();
+static void drop_gathered_result();
+static void release_staging();
+// Everything the library holds on the devices and in pinned memory goes back to the driver; the settings (tables'
+// host copies, numerics, the keep switch) stay, and the next call initialises lazily as the first one did.
 int rays_hip_finalize(void) {
   rccl_close_all();
   drop_kept_result();
+  drop_gathered_result();
   std::lock_guard<std::mutex> lk(g_mu);
-  for (int d = 0; d < 16; d++)
+  for (int d = 0; d < kMaxDevices; d++)
     if (g_ws[d].counters) {
       (void)hipSetDevice(d);
       (void)hipDeviceSynchronize();
       (void)hipFree(g_ws[d].counters);
-      g_ws[d].counters = nullptr;
-      for (int i = 0; i < kCounterSlots; i++) {
-        if (g_ws[d].done[i]) (void)hipEventDestroy(g_ws[d].done[i]);
-        g_ws[d].done[i] = nullptr;
-        g_ws[d].used[i] = false;
-      }
-      g_ws[d].next = 0;
+      for (hipEvent_t e : g_ws[d].done)
+        if (e) (void)hipEventDestroy(e);
+      g_ws[d] = DeviceWorkspace();
     }
-  for (auto& kv : g_sg_ws)
-    if (kv.second.ptr) {
-      (void)hipSetDevice(kv.first.first);
-      (void)hipDeviceSynchronize();
-      (void)hipFree(kv.second.ptr);
-    }
-  g_sg_ws.clear();
-  for (auto& kv : g_sched_ws)
-    if (kv.second.ptr) {
-      (void)hipSetDevice(kv.first.first);
-      (void)hipDeviceSynchronize();
-      (void)hipFree(kv.second.ptr);
-    }
-  g_sched_ws.clear();
-  release_step_scratch();
+  for (StreamWorkspace* w : {&g_sg_ws, &g_sched_ws, &g_step_ws}) w->release_all();
+  for (DeviceTable* t : std::initializer_list<DeviceTable*>{&g_zfun, &g_axi, &g_rho}) t->release_all();
+  release_staging();
   release_cached_device_blocks();
   g_devices.clear();
   return 0;
@@ -702,8 +637,7 @@ int launch_trace(const rays_params_t* p, int nray, const double* d_rvec0, const 
     if ((long long)nray > (long long)rays::device_cu_count(dev) * rays::kBlock) {
       const size_t words = 4 + rays::sched_pilots((unsigned)nray, stride);
       unsigned int* ws = nullptr;
-      rc = get_sched_workspace(stream, sizeof(unsigned int) * words, &ws);
-      if (rc) return rc;
+      HIP_TRY_AS("hipMalloc (ray order workspace)", g_sched_ws.get(stream, sizeof(unsigned int) * words, (void**)&ws));
       HIP_TRY(hipMemsetAsync(ws, 0, sizeof(unsigned int) * words, stream));
       A.sched = ws;
       A.sched_stride = stride;
@@ -720,8 +654,8 @@ int launch_trace(const rays_params_t* p, int nray, const double* d_rvec0, const 
     const long long want = ((long long)nray + rays_per_block - 1) / rays_per_block * rays::kBlock;
     A.sg_far_lanes = want < resident ? want : resident;
     double* ws = nullptr;
-    rc = get_sg_workspace(stream, sizeof(double) * (size_t)kernel->sg_far_per_lane * (size_t)A.sg_far_lanes, &ws);
-    if (rc) return rc;
+    const size_t far_bytes = sizeof(double) * (size_t)kernel->sg_far_per_lane * (size_t)A.sg_far_lanes;
+    HIP_TRY_AS("hipMalloc (SG workspace)", g_sg_ws.get(stream, far_bytes, (void**)&ws));
     A.sg_far = ws;
   }
   rays::DevParams D = make_dev_params(*p);
@@ -736,8 +670,9 @@ int launch_trace(const rays_params_t* p, int nray, const double* d_rvec0, const 
     if (!twin || !twin->resume) return fail("rays_hip: the tolerance kernel's exact twin is not in this build");
     if (!A.end_ray_vec || !A.max_residuals) {
       double* ws = nullptr;
-      rc = get_sg_workspace(stream, sizeof(double) * ((size_t)p->nv + 1) * (size_t)nray, &ws);  // (no SG kernel runs with it at the same time: one stream)
-      if (rc) return rc;
+      // (no SG kernel runs with it at the same time: one stream)
+      const size_t sum_bytes = sizeof(double) * ((size_t)p->nv + 1) * (size_t)nray;
+      HIP_TRY_AS("hipMalloc (SG workspace)", g_sg_ws.get(stream, sum_bytes, (void**)&ws));
       if (!A.end_ray_vec) A.end_ray_vec = ws;
       if (!A.max_residuals) A.max_residuals = ws + (size_t)p->nv * (size_t)nray;
     }
@@ -825,30 +760,6 @@ __global__ void ode_step_collect_kernel(int n, int nv, const double* __restrict_
 }
 }  // namespace rays
 
-namespace {
-// scratch of rays_hip_ode_step_device, one block per (device, stream), grown on demand and kept (a host that calls
-// the entry per time step would otherwise pay four hipMalloc / hipFree per call); released by rays_hip_finalize
-std::map<std::pair<int, hipStream_t>, SgWorkspace> g_step_ws;
-int get_step_scratch(hipStream_t stream, size_t bytes, char** out) {
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lk(g_mu);
-  SgWorkspace& w = g_step_ws[std::make_pair(dev, stream)];
-  if (w.bytes < bytes) {
-    if (w.ptr) {
-      HIP_TRY(hipStreamSynchronize(stream));
-      (void)hipFree(w.ptr);
-    }
-    w.ptr = nullptr;
-    w.bytes = 0;
-    HIP_TRY(hipMalloc(&w.ptr, bytes));
-    w.bytes = bytes;
-  }
-  *out = reinterpret_cast<char*>(w.ptr);
-  return 0;
-}
-}  // namespace
-
 int rays_hip_ode_step_device(const rays_params_t* p, int n, const double* d_v0, const double* d_s0,
                              double* d_v1, double* d_resid, int32_t* d_stop_code, void* hip_stream) {
   int rc = rays_hip_check_params(p);
@@ -866,8 +777,7 @@ int rays_hip_ode_step_device(const rays_params_t* p, int n, const double* d_v0, 
                off_np = off_ev + sizeof(double) * nv * N, off_sc = off_np + sizeof(int32_t) * N,
                total = off_sc + sizeof(int32_t) * N;
   char* base = nullptr;
-  rc = get_step_scratch(stream, total, &base);
-  if (rc) return rc;
+  HIP_TRY_AS("hipMalloc (ode_step scratch)", g_step_ws.get(stream, total, (void**)&base));
   double *d_rv = reinterpret_cast<double*>(base), *d_res = reinterpret_cast<double*>(base + off_res),
          *d_ev = reinterpret_cast<double*>(base + off_ev);
   int32_t *d_np = reinterpret_cast<int32_t*>(base + off_np), *d_sc = reinterpret_cast<int32_t*>(base + off_sc);
@@ -885,112 +795,6 @@ int rays_hip_ode_step_device(const rays_params_t* p, int n, const double* d_v0, 
   return 0;  // asynchronous on `stream` like rays_hip_trace_device (the scratch block outlives the call)
 }
 
-static void release_step_scratch() {  // caller holds g_mu
-  for (auto& kv : g_step_ws)
-    if (kv.second.ptr) {
-      (void)hipSetDevice(kv.first.first);
-      (void)hipDeviceSynchronize();
-      (void)hipFree(kv.second.ptr);
-    }
-  g_step_ws.clear();
-}
-
-// Device buffers of rays_hip_trace are kept between calls (a host that traces repeatedly -- ray_scan, a
-// time loop -- otherwise pays ~6 ms per call for hipMalloc/hipFree of the 64k fan's 5 GB): a released
-// block goes to its device's free list and serves the next request of a similar size.  Everything is
-// returned to the driver by rays_hip_finalize, or at once when an allocation fails.
-// (One cache per SLOT of the device list rays_hip_init[_devices] selected -- a device may appear in
-// several slots, each with its own host thread, stream and buffers.)
-struct DeviceBlockCache {
-  struct Block { void* p; size_t cap; };
-  int device = -1;
-  std::mutex mu;
-  std::vector<Block> idle;
-  std::map<void*, size_t> live;
-  hipStream_t stream = nullptr;  // the entry's stream on this device (creating one costs ~8 ms per call)
-  void drop_idle() {  // caller holds mu and has the device current
-    for (auto& b : idle) (void)hipFree(b.p);
-    idle.clear();
-  }
-};
-static DeviceBlockCache g_blocks[17];  // slots 0..15: the device list; 16: the gathered result (rays_gather.inc)
-static hipError_t cached_malloc(int slot, void** out, size_t bytes) {
-  if (slot < 0 || slot >= 17) return hipMalloc(out, bytes);
-  DeviceBlockCache& c = g_blocks[slot];
-  std::lock_guard<std::mutex> lk(c.mu);
-  size_t best = c.idle.size();
-  for (size_t i = 0; i < c.idle.size(); i++)
-    if (c.idle[i].cap >= bytes && c.idle[i].cap <= bytes + bytes / 4 + (1u << 20) &&
-        (best == c.idle.size() || c.idle[i].cap < c.idle[best].cap))
-      best = i;
-  if (best < c.idle.size()) {
-    *out = c.idle[best].p;
-    c.live[*out] = c.idle[best].cap;
-    c.idle.erase(c.idle.begin() + (long)best);
-    return hipSuccess;
-  }
-  hipError_t e = hipMalloc(out, bytes ? bytes : 1);
-  if (e != hipSuccess) {  // give the idle blocks back and try once more
-    (void)hipGetLastError();
-    c.drop_idle();
-    e = hipMalloc(out, bytes ? bytes : 1);
-  }
-  if (e == hipSuccess) c.live[*out] = bytes ? bytes : 1;
-  return e;
-}
-static hipError_t cached_stream(int slot, hipStream_t* out, bool* owned) {
-  *owned = slot < 0 || slot >= 17;
-  if (*owned) return hipStreamCreate(out);
-  DeviceBlockCache& c = g_blocks[slot];
-  std::lock_guard<std::mutex> lk(c.mu);
-  if (!c.stream) {
-    hipError_t e = hipStreamCreate(&c.stream);
-    if (e != hipSuccess) return e;
-  }
-  *out = c.stream;
-  return hipSuccess;
-}
-static void cached_free(int slot, void* ptr) {
-  if (!ptr) return;
-  if (slot < 0 || slot >= 17) { (void)hipFree(ptr); return; }
-  DeviceBlockCache& c = g_blocks[slot];
-  std::lock_guard<std::mutex> lk(c.mu);
-  auto it = c.live.find(ptr);
-  if (it == c.live.end()) { (void)hipFree(ptr); return; }
-  c.idle.push_back({ptr, it->second});
-  c.live.erase(it);
-}
-
-// A cache slot serves one device at a time (its stream and idle blocks live there).  Every user of a slot -- the
-// blocks of rays_hip_trace and of rays_hip_trace_gather alike -- claims it for the device it is about to use: a slot
-// that last served another device (e.g. four slots on device 0 for a large fan, then one slot per device for a
-// gather) first gives that device's blocks and stream back.  Caller has `dev` current; it is current on return.
-static void claim_slot_for_device(int slot, int dev) {
-  if (slot < 0 || slot >= 17) return;
-  DeviceBlockCache& c = g_blocks[slot];
-  std::lock_guard<std::mutex> lk(c.mu);
-  if (c.device >= 0 && c.device != dev) {
-    (void)hipSetDevice(c.device);
-    c.drop_idle();
-    if (c.stream) (void)hipStreamDestroy(c.stream);
-    c.stream = nullptr;
-    (void)hipSetDevice(dev);
-  }
-  c.device = dev;
-}
-
-static void release_cached_device_blocks() {
-  for (int d = 0; d < 17; d++) {
-    DeviceBlockCache& c = g_blocks[d];
-    std::lock_guard<std::mutex> lk(c.mu);
-    if (c.idle.empty() && !c.stream) continue;
-    if (c.device >= 0) (void)hipSetDevice(c.device);
-    c.drop_idle();
-    if (c.stream) (void)hipStreamDestroy(c.stream);
-    c.stream = nullptr;
-  }
-}
-
 // Pinned staging for the packed device-to-host copy of rays_hip_trace: two buffers per device,
 // allocated once (pinning is slow) and kept.  `points` = trajectory points one buffer holds.
 struct StagingBuffers {
@@ -1000,19 +804,21 @@ struct StagingBuffers {
   size_t nv = 0;
 };
 // Fixed storage: every device's host thread keeps a pointer into it for the whole copy phase, so
-// the elements must never move (one slot per device ordinal, like g_blocks).
-constexpr int kMaxDevices = 16;
+// the elements must never move (one per slot of the device list, like the block caches).
 static StagingBuffers g_staging[kMaxDevices];
+static void free_staging(StagingBuffers& sb) {
+  for (int b = 0; b < 2; b++) {
+    if (sb.vec[b]) (void)hipHostFree(sb.vec[b]);
+    if (sb.res[b]) (void)hipHostFree(sb.res[b]);
+  }
+  sb = StagingBuffers();
+}
 static StagingBuffers* staging_for_slot(int dev, size_t nv, long long min_points) {
   if (dev < 0 || dev >= kMaxDevices) return nullptr;
   std::lock_guard<std::mutex> lk(g_mu);
   StagingBuffers& sb = g_staging[dev];
   if (sb.points == 0 || sb.nv < nv || sb.points < min_points) {
-    for (int b = 0; b < 2; b++) {
-      if (sb.vec[b]) (void)hipHostFree(sb.vec[b]);
-      if (sb.res[b]) (void)hipHostFree(sb.res[b]);
-      sb.vec[b] = sb.res[b] = nullptr;
-    }
+    free_staging(sb);
     // 1 M points per buffer (8 (nv + 1) MB, e.g. 64 MB for nv = 7), and never less than one whole ray
     const long long pts = std::max(1ll << 20, min_points);
     for (int b = 0; b < 2; b++) {
@@ -1026,6 +832,9 @@ static StagingBuffers* staging_for_slot(int dev, size_t nv, long long min_points
     sb.nv = nv;
   }
   return &sb;
+}
+static void release_staging() {  // caller holds g_mu
+  for (StagingBuffers& sb : g_staging) free_staging(sb);
 }
 
 // ---- the device-resident image of the last rays_hip_trace call (rays_hip_keep_last_result) -------------------------
@@ -1050,27 +859,110 @@ static void drop_kept_result() {  // caller holds no lock
     old.swap(g_kept.blocks);
     g_kept.nray = 0;
   }
+  if (old.empty()) return;
+  CurrentDevice restore;
   for (const KeptBlock& b : old) {
     (void)hipSetDevice(b.device);
-    cached_free(b.slot, b.d_ray_vec);
+    cached_free(b.slot, b.d_ray_vec);  // (freed, not cached, when the slot serves another device by now)
     cached_free(b.slot, b.d_npoints);
   }
+}
+
+// The trajectories of one block of rays_hip_trace: only the recorded points cross PCIe.
+// The device arrays that rays_hip_trace_device fills for a block of n rays.
+struct ResultArrays {
+  double *rv = nullptr, *res = nullptr, *ev = nullptr, *er = nullptr, *mr = nullptr;
+  int32_t *np = nullptr, *sc = nullptr;
+  hipError_t alloc(DeviceBuffers& bufs, size_t n, size_t npt, size_t nv) {
+    hipError_t e = bufs.alloc(&rv, npt * nv * n);
+    if (e == hipSuccess) e = bufs.alloc(&res, npt * n);
+    if (e == hipSuccess) e = bufs.alloc(&np, n);
+    if (e == hipSuccess) e = bufs.alloc(&sc, n);
+    if (e == hipSuccess) e = bufs.alloc(&ev, nv * n);
+    if (e == hipSuccess) e = bufs.alloc(&er, n);
+    return e == hipSuccess ? bufs.alloc(&mr, n) : e;
+  }
+};
+
+// The padded arrays are ~80 % zeros (a ray uses npoints of nstep_max+1 slots; 4.7 GB for the 64k
+// fan, 0.82 GB of it data).  Pack on the device, copy the packed block through two pinned
+// staging buffers, and scatter it into the caller's arrays with host threads while the next
+// chunk is in flight.  Entries past npoints are not written: like the reference's trace_rays,
+// which relies on initialize_ray_results_m having zero-filled the arrays (ray_results_m.f90:
+// 154-164), this entry leaves them as the caller passed them.
+// npoints: the block's counts on the host; ray_vec, residual: the block's slabs of the caller's arrays.
+static int copy_packed_to_host(int slot, const rays_params_t* p, int n, const int32_t* npoints, int32_t* d_np,
+                               double* d_rv, double* d_res, double* ray_vec, double* residual, hipStream_t st) {
+  const size_t npt = (size_t)p->nstep_max + 1, nv = (size_t)p->nv;
+  std::vector<long long> offs((size_t)n + 1);
+  offs[0] = 0;
+  for (int i = 0; i < n; i++) offs[(size_t)i + 1] = offs[i] + (npoints[i] > 0 ? npoints[i] : 0);
+  const long long total = offs[n];
+  DeviceBuffers bufs(slot);
+  long long* d_off = nullptr;
+  double *d_pv = nullptr, *d_pr = nullptr;
+  HIP_TRY_AS("hipMalloc(&d_off)", bufs.alloc(&d_off, (size_t)n + 1));
+  if (total == 0) return 0;
+  const auto failed = [] { return fail("rays_hip_trace: packed device-to-host copy failed (out of memory?)"); };
+  EventPair ev;
+  StagingBuffers* sb = nullptr;
+  if (bufs.alloc(&d_pv, nv * (size_t)total) != hipSuccess || bufs.alloc(&d_pr, (size_t)total) != hipSuccess ||
+      hipMemcpyAsync(d_off, offs.data(), sizeof(long long) * ((size_t)n + 1), hipMemcpyHostToDevice, st) != hipSuccess ||
+      rays::launch_pack(true, n, (int)nv, p->nstep_max, d_np, d_off, d_rv, d_res, d_pv, d_pr, st) != hipSuccess ||
+      !(sb = staging_for_slot(slot, nv, (long long)npt)) || ev.create() != hipSuccess)
+    return failed();
+  struct Chunk { int a, b, buf; };
+  auto scatter = [&](const Chunk& c) {   // host side of one chunk: packed staging -> padded arrays
+    const long long base = offs[c.a];
+    const double* sv = sb->vec[c.buf];
+    const double* sr = sb->res[c.buf];
+    const int nt = 16;
+    std::vector<std::thread> th;
+    for (int t = 0; t < nt; t++)
+      th.emplace_back([&, t]() {
+        for (int i = c.a + t; i < c.b; i += nt) {
+          const long long np_i = offs[(size_t)i + 1] - offs[i];
+          if (np_i <= 0) continue;
+          std::memcpy(ray_vec + npt * nv * (size_t)i, sv + (offs[i] - base) * (long long)nv,
+                      sizeof(double) * nv * (size_t)np_i);
+          std::memcpy(residual + npt * (size_t)i, sr + (offs[i] - base), sizeof(double) * (size_t)np_i);
+        }
+      });
+    for (auto& x : th) x.join();
+  };
+  // chunks of rays whose packed size fits one staging buffer
+  int buf = 0;
+  Chunk pending{0, 0, -1};
+  for (int c0 = 0; c0 < n;) {
+    int c1 = c0;
+    while (c1 < n && offs[(size_t)c1 + 1] - offs[c0] <= sb->points) c1++;
+    if (c1 == c0) return failed();  // a ray has at most nstep_max+1 <= sb->points points (staging_for_slot)
+    const long long pts = offs[c1] - offs[c0];
+    if (pts > 0 &&
+        (hipMemcpyAsync(sb->vec[buf], d_pv + offs[c0] * (long long)nv, sizeof(double) * nv * (size_t)pts,
+                        hipMemcpyDeviceToHost, st) != hipSuccess ||
+         hipMemcpyAsync(sb->res[buf], d_pr + offs[c0], sizeof(double) * (size_t)pts, hipMemcpyDeviceToHost,
+                        st) != hipSuccess ||
+         hipEventRecord(ev[buf], st) != hipSuccess))
+      return failed();
+    if (pending.buf >= 0) scatter(pending);   // overlaps the copy just queued
+    pending.buf = -1;
+    if (pts > 0) {
+      if (hipEventSynchronize(ev[buf]) != hipSuccess) return failed();
+      pending = Chunk{c0, c1, buf};
+      buf ^= 1;
+    }
+    c0 = c1;
+  }
+  if (pending.buf >= 0) scatter(pending);
+  return 0;
 }
 
 // One device's share of rays_hip_trace: rays [r0, r1) -> contiguous slabs of the host arrays.
 static int trace_block_on_device(int slot, int dev, const rays_params_t* p, int r0, int r1, const double* rvec0,
                                  const double* rindex_vec0, double* ray_vec, double* residual,
                                  int32_t* npoints, int32_t* stop_code, double* end_ray_vec,
-                                 double* end_residuals, double* max_residuals, std::string* err) {
-  auto bail = [&](int rc) {
-    *err = g_err;
-    return rc;
-  };
-#define DEV_TRY(call)                                      \
-  do {                                                     \
-    hipError_t e_ = (call);                                \
-    if (e_ != hipSuccess) return bail(hip_fail(e_, #call)); \
-  } while (0)
+                                 double* end_residuals, double* max_residuals) {
   const int n = r1 - r0;
   if (n <= 0) return 0;
   const size_t npt = (size_t)p->nstep_max + 1, nv = (size_t)p->nv;
@@ -1083,153 +975,51 @@ static int trace_block_on_device(int slot, int dev, const rays_params_t* p, int 
                  std::chrono::duration<double, std::milli>(now - t_prev).count());
     t_prev = now;
   };
-  DEV_TRY(hipSetDevice(dev));
+  HIP_TRY(hipSetDevice(dev));
   claim_slot_for_device(slot, dev);
-  hipStream_t st;
-  bool own_stream = false;
-  DEV_TRY(cached_stream(slot, &st, &own_stream));
+  SlotStream stream;
+  HIP_TRY_AS("hipStreamCreate", stream.open(slot));
+  const hipStream_t st = stream.get();
   lap("stream");
-  double *d_r = nullptr, *d_n = nullptr, *d_rv = nullptr, *d_res = nullptr, *d_ev = nullptr, *d_er = nullptr,
-         *d_mr = nullptr;
-  int32_t *d_np = nullptr, *d_sc = nullptr;
-  int rc = 0;
-  do {
-#define DEV_CHK(call)                        \
-  {                                          \
-    hipError_t e_ = (call);                  \
-    if (e_ != hipSuccess) {                  \
-      rc = bail(hip_fail(e_, #call));        \
-      break;                                 \
-    }                                        \
-  }
-    DEV_CHK(cached_malloc(slot, (void**)&d_r, sizeof(double) * 3 * n));
-    DEV_CHK(cached_malloc(slot, (void**)&d_n, sizeof(double) * 3 * n));
-    DEV_CHK(cached_malloc(slot, (void**)&d_rv, sizeof(double) * npt * nv * n));
-    DEV_CHK(cached_malloc(slot, (void**)&d_res, sizeof(double) * npt * n));
-    DEV_CHK(cached_malloc(slot, (void**)&d_np, sizeof(int32_t) * n));
-    DEV_CHK(cached_malloc(slot, (void**)&d_sc, sizeof(int32_t) * n));
-    DEV_CHK(cached_malloc(slot, (void**)&d_ev, sizeof(double) * nv * n));
-    DEV_CHK(cached_malloc(slot, (void**)&d_er, sizeof(double) * n));
-    DEV_CHK(cached_malloc(slot, (void**)&d_mr, sizeof(double) * n));
-    lap("device allocations");
-    DEV_CHK(hipMemcpyAsync(d_r, rvec0 + 3 * (size_t)r0, sizeof(double) * 3 * n, hipMemcpyHostToDevice, st));
-    DEV_CHK(hipMemcpyAsync(d_n, rindex_vec0 + 3 * (size_t)r0, sizeof(double) * 3 * n, hipMemcpyHostToDevice, st));
-    // no zero-fill of the device arrays: only recorded points are read back
-    rc = rays_hip_trace_device(p, n, d_r, d_n, d_rv, d_res, d_np, d_sc, d_ev, d_er, d_mr, st, RAYS_TRACE_NO_ZERO_FILL);
-    if (rc) {
-      bail(rc);
-      break;
-    }
-    // ---- trajectories: only the recorded points cross PCIe ------------------------------------
-    // The padded arrays are ~80 % zeros (a ray uses npoints of nstep_max+1 slots; 4.7 GB for the 64k
-    // fan, 0.82 GB of it data).  Pack on the device, copy the packed block through two pinned
-    // staging buffers, and scatter it into the caller's arrays with host threads while the next
-    // chunk is in flight.  Entries past npoints are not written: like the reference's trace_rays,
-    // which relies on initialize_ray_results_m having zero-filled the arrays (ray_results_m.f90:
-    // 154-164), this entry leaves them as the caller passed them.
-    DEV_CHK(hipMemcpyAsync(npoints + r0, d_np, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
-    DEV_CHK(hipStreamSynchronize(st));
-    lap("inputs + trace kernel");
-    {
-      std::vector<long long> offs((size_t)n + 1);
-      offs[0] = 0;
-      for (int i = 0; i < n; i++) offs[(size_t)i + 1] = offs[i] + (npoints[r0 + i] > 0 ? npoints[r0 + i] : 0);
-      const long long total = offs[n];
-      long long* d_off = nullptr;
-      double *d_pv = nullptr, *d_pr = nullptr;
-      DEV_CHK(cached_malloc(slot, (void**)&d_off, sizeof(long long) * ((size_t)n + 1)));
-      bool ok = true;
-      do {
-        if (total == 0) break;
-        if (cached_malloc(slot, (void**)&d_pv, sizeof(double) * nv * (size_t)total) != hipSuccess ||
-            cached_malloc(slot, (void**)&d_pr, sizeof(double) * (size_t)total) != hipSuccess) { ok = false; break; }
-        if (hipMemcpyAsync(d_off, offs.data(), sizeof(long long) * ((size_t)n + 1), hipMemcpyHostToDevice, st) != hipSuccess) { ok = false; break; }
-        if (rays::launch_pack(true, n, (int)nv, p->nstep_max, d_np, d_off, d_rv, d_res, d_pv, d_pr, st) != hipSuccess) { ok = false; break; }
-        StagingBuffers* sb = staging_for_slot(slot, nv, (long long)npt);
-        if (!sb) { ok = false; break; }
-        // chunks of rays whose packed size fits one staging buffer
-        int c0 = 0, buf = 0;
-        hipEvent_t ev[2];
-        if (hipEventCreate(&ev[0]) != hipSuccess || hipEventCreate(&ev[1]) != hipSuccess) { ok = false; break; }
-        struct Chunk { int a, b, buf; };
-        Chunk pending{0, 0, -1};
-        auto scatter = [&](const Chunk& c) {   // host side of one chunk: packed staging -> padded arrays
-          const long long base = offs[c.a];
-          const double* sv = sb->vec[c.buf];
-          const double* sr = sb->res[c.buf];
-          const int nt = 16;
-          std::vector<std::thread> th;
-          for (int t = 0; t < nt; t++)
-            th.emplace_back([&, t]() {
-              for (int i = c.a + t; i < c.b; i += nt) {
-                const long long np_i = offs[(size_t)i + 1] - offs[i];
-                if (np_i <= 0) continue;
-                std::memcpy(ray_vec + npt * nv * (size_t)(r0 + i), sv + (offs[i] - base) * (long long)nv,
-                            sizeof(double) * nv * (size_t)np_i);
-                std::memcpy(residual + npt * (size_t)(r0 + i), sr + (offs[i] - base), sizeof(double) * (size_t)np_i);
-              }
-            });
-          for (auto& x : th) x.join();
-        };
-        while (c0 < n && ok) {
-          int c1 = c0;
-          while (c1 < n && offs[(size_t)c1 + 1] - offs[c0] <= sb->points) c1++;
-          if (c1 == c0) { ok = false; break; }  // a ray has at most nstep_max+1 <= sb->points points (staging_for_slot)
-          const long long pts = offs[c1] - offs[c0];
-          if (pts > 0) {
-            if (hipMemcpyAsync(sb->vec[buf], d_pv + offs[c0] * (long long)nv, sizeof(double) * nv * (size_t)pts,
-                               hipMemcpyDeviceToHost, st) != hipSuccess ||
-                hipMemcpyAsync(sb->res[buf], d_pr + offs[c0], sizeof(double) * (size_t)pts, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                hipEventRecord(ev[buf], st) != hipSuccess) { ok = false; break; }
-          }
-          if (pending.buf >= 0) scatter(pending);   // overlaps the copy just queued
-          if (pts > 0) {
-            if (hipEventSynchronize(ev[buf]) != hipSuccess) { ok = false; break; }
-            pending = Chunk{c0, c1, buf};
-            buf ^= 1;
-          } else {
-            pending.buf = -1;
-          }
-          c0 = c1;
-        }
-        if (ok && pending.buf >= 0) scatter(pending);
-        (void)hipEventDestroy(ev[0]);
-        (void)hipEventDestroy(ev[1]);
-      } while (0);
-      cached_free(slot, d_off); cached_free(slot, d_pv); cached_free(slot, d_pr);
-      lap("pack + copy + host scatter");
-      if (!ok) {
-        rc = bail(fail("rays_hip_trace: packed device-to-host copy failed (out of memory?)"));
-        break;
-      }
-    }
-    DEV_CHK(hipMemcpyAsync(stop_code + r0, d_sc, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
-    if (end_ray_vec) DEV_CHK(hipMemcpyAsync(end_ray_vec + nv * (size_t)r0, d_ev, sizeof(double) * nv * n, hipMemcpyDeviceToHost, st));
-    if (end_residuals) DEV_CHK(hipMemcpyAsync(end_residuals + r0, d_er, sizeof(double) * n, hipMemcpyDeviceToHost, st));
-    if (max_residuals) DEV_CHK(hipMemcpyAsync(max_residuals + r0, d_mr, sizeof(double) * n, hipMemcpyDeviceToHost, st));
-    DEV_CHK(hipStreamSynchronize(st));
-  } while (0);
+  DeviceBuffers bufs(slot);
+  double *d_r = nullptr, *d_n = nullptr;
+  ResultArrays d;
+  HIP_TRY_AS("hipMalloc(&d_r)", bufs.alloc(&d_r, 3 * (size_t)n));
+  HIP_TRY_AS("hipMalloc(&d_n)", bufs.alloc(&d_n, 3 * (size_t)n));
+  HIP_TRY_AS("hipMalloc (result arrays)", d.alloc(bufs, (size_t)n, npt, nv));
+  lap("device allocations");
+  HIP_TRY(hipMemcpyAsync(d_r, rvec0 + 3 * (size_t)r0, sizeof(double) * 3 * n, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(d_n, rindex_vec0 + 3 * (size_t)r0, sizeof(double) * 3 * n, hipMemcpyHostToDevice, st));
+  // no zero-fill of the device arrays: only recorded points are read back
+  int rc = rays_hip_trace_device(p, n, d_r, d_n, d.rv, d.res, d.np, d.sc, d.ev, d.er, d.mr, st, RAYS_TRACE_NO_ZERO_FILL);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(npoints + r0, d.np, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  lap("inputs + trace kernel");
+  rc = copy_packed_to_host(slot, p, n, npoints + r0, d.np, d.rv, d.res, ray_vec + npt * nv * (size_t)r0,
+                           residual + npt * (size_t)r0, st);
+  lap("pack + copy + host scatter");
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(stop_code + r0, d.sc, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
+  if (end_ray_vec)
+    HIP_TRY(hipMemcpyAsync(end_ray_vec + nv * (size_t)r0, d.ev, sizeof(double) * nv * n, hipMemcpyDeviceToHost, st));
+  if (end_residuals) HIP_TRY(hipMemcpyAsync(end_residuals + r0, d.er, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+  if (max_residuals) HIP_TRY(hipMemcpyAsync(max_residuals + r0, d.mr, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
   lap("summaries");
   {
-    bool kept = false;
-    if (rc == 0) {
-      std::lock_guard<std::mutex> lk(g_mu);
-      if (g_kept.keep) {
-        KeptBlock b;
-        b.slot = slot; b.device = dev; b.r0 = r0; b.r1 = r1; b.d_ray_vec = d_rv; b.d_npoints = d_np;
-        g_kept.blocks.push_back(b);
-        kept = true;
-      }
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (g_kept.keep) {  // the slab and its counts stay on the device: theirs is the kept result now
+      KeptBlock b;
+      b.slot = slot; b.device = dev; b.r0 = r0; b.r1 = r1;
+      b.d_ray_vec = bufs.detach(d.rv);
+      b.d_npoints = bufs.detach(d.np);
+      g_kept.blocks.push_back(b);
     }
-    if (kept) d_rv = nullptr, d_np = nullptr;  // (cached_free ignores null)
   }
-  cached_free(slot, d_r); cached_free(slot, d_n); cached_free(slot, d_rv); cached_free(slot, d_res); cached_free(slot, d_np);
-  cached_free(slot, d_sc); cached_free(slot, d_ev); cached_free(slot, d_er); cached_free(slot, d_mr);
-  if (own_stream) (void)hipStreamDestroy(st);
+  bufs.release();
   lap("device frees");
-  return rc;
-#undef DEV_CHK
-#undef DEV_TRY
+  return 0;
 }
 
 int rays_hip_trace(const rays_params_t* p, int nray, const double* rvec0, const double* rindex_vec0,
@@ -1263,7 +1053,7 @@ int rays_hip_trace(const rays_params_t* p, int nray, const double* rvec0, const 
     }
     int k = (long long)nray >= 32768ll * (long long)devs.size() ? 4 : 1;
     if (const char* e = std::getenv("RAYS_HIP_SLOTS_PER_DEVICE")) k = std::atoi(e);
-    while (k > 1 && (size_t)k * devs.size() > 16) k--;
+    while (k > 1 && (size_t)k * devs.size() > (size_t)kMaxDevices) k--;
     if (!explicit_list && k > 1) {
       std::vector<int> slots;
       for (int d : devs)
@@ -1283,7 +1073,8 @@ int rays_hip_trace(const rays_params_t* p, int nray, const double* rvec0, const 
     const int r0 = std::min(nray, g * per), r1 = std::min(nray, (g + 1) * per);
     th.emplace_back([&, g, r0, r1] {
       rcs[g] = trace_block_on_device(g, devs[g], p, r0, r1, rvec0, rindex_vec0, ray_vec, residual, npoints,
-                                     stop_code, end_ray_vec, end_residuals, max_residuals, &errs[g]);
+                                     stop_code, end_ray_vec, end_residuals, max_residuals);
+      if (rcs[g]) errs[g] = g_err;  // (the message is this worker thread's)
     });
   }
   for (auto& t : th) t.join();
@@ -1341,34 +1132,6 @@ int rays_hip_unpack_device(int nray, int nv, int nstep_max, const int32_t* d_npo
 // Diagnostic entry (tests): evaluate the RHS pieces at n states on the current device.
 // v[n][nv] host; outputs host: cold7[n][7], num7[n][7], dvds[n][nv], resid[n], codes[n][4]
 // (codes: equilibrium err, eqn_ray stop code, check_save flag, check_save stop_ode).
-// rho(psiN) spline table: host copy + lazily uploaded per-device copies (grid[n] then fspl[n][4])
-namespace {
-struct RhoTable {
-  std::vector<double> host;
-  int n = 0;
-  unsigned long long version = 0;
-};
-RhoTable g_rho;
-std::vector<ZfunDevice> g_rho_dev;
-int get_rho_device(const double** out, int* n) {
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lk(g_mu);
-  if (g_rho.n < 2) return fail("Ptotal_rho needs rays_hip_set_rho_table() first");
-  if ((int)g_rho_dev.size() <= dev) g_rho_dev.resize(dev + 1);
-  ZfunDevice& z = g_rho_dev[dev];
-  if (z.version != g_rho.version) {
-    if (z.ptr) (void)hipFree(z.ptr);
-    z.ptr = nullptr;
-    HIP_TRY(hipMalloc(&z.ptr, sizeof(double) * g_rho.host.size()));
-    HIP_TRY(hipMemcpy(z.ptr, g_rho.host.data(), sizeof(double) * g_rho.host.size(), hipMemcpyHostToDevice));
-    z.version = g_rho.version;
-  }
-  *out = z.ptr;
-  *n = g_rho.n;
-  return 0;
-}
-}  // namespace
 
 int rays_hip_set_rho_table(const double* grid, const double* fspl, int n) {
   if (!grid || !fspl || n < 2) return fail("rays_hip_set_rho_table: bad table");
@@ -1430,6 +1193,16 @@ int rays_hip_deposition_device(const rays_params_t* p, int which, int n_bins, in
   return 0;
 }
 
+// The device's work[n_bins][n] as n rows of the reference's work(n_bins, nray) = C [nray][n_bins]
+static hipError_t work_to_host(const double* d_work, int n_bins, int n, double* work_rows, std::vector<double>* wbuf) {
+  wbuf->resize((size_t)n_bins * (size_t)n);
+  const hipError_t e = hipMemcpy(wbuf->data(), d_work, sizeof(double) * wbuf->size(), hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return e;
+  for (int r = 0; r < n; r++)
+    for (int b = 0; b < n_bins; b++) work_rows[(size_t)r * n_bins + b] = (*wbuf)[(size_t)b * n + r];
+  return hipSuccess;
+}
+
 // Host-pointer form of the deposition profiles: what a Fortran post-processor holding the ray_results_m arrays
 // calls instead of calculate_deposition_profiles (deposition_profiles_m.f90:228-260).  Only points 1..maxval(npoints)
 // of every ray cross PCIe (a strided copy); work comes back in the reference's work(n_bins, nray) layout.
@@ -1452,35 +1225,25 @@ int rays_hip_deposition(const rays_params_t* p, int which, int n_bins, int nray,
   const auto t0 = std::chrono::steady_clock::now();
   rays_params_t q = *p;
   q.nstep_max = maxnp - 1;  // the device copy holds maxnp points per ray
+  DeviceBuffers bufs;
   double *d_rv = nullptr, *d_pw = nullptr, *d_work = nullptr, *d_prof = nullptr;
   int32_t* d_np = nullptr;
-  auto release = [&]() { (void)hipFree(d_rv); (void)hipFree(d_pw); (void)hipFree(d_work); (void)hipFree(d_prof); (void)hipFree(d_np); };
-#define DEP_TRY(call)                                                \
-  do {                                                               \
-    hipError_t e_ = (call);                                          \
-    if (e_ != hipSuccess) { release(); return hip_fail(e_, #call); } \
-  } while (0)
-  DEP_TRY(hipMalloc(&d_rv, sizeof(double) * nv * (size_t)maxnp * (size_t)nray));
-  DEP_TRY(hipMalloc(&d_pw, sizeof(double) * (size_t)nray));
-  DEP_TRY(hipMalloc(&d_work, sizeof(double) * (size_t)n_bins * (size_t)nray));
-  DEP_TRY(hipMalloc(&d_prof, sizeof(double) * (size_t)n_bins));
-  DEP_TRY(hipMalloc(&d_np, sizeof(int32_t) * (size_t)nray));
-  DEP_TRY(hipMemcpy2D(d_rv, sizeof(double) * nv * (size_t)maxnp, ray_vec, sizeof(double) * nv * npt,
+  HIP_TRY_AS("hipMalloc(&d_rv)", bufs.alloc(&d_rv, nv * (size_t)maxnp * (size_t)nray));
+  HIP_TRY_AS("hipMalloc(&d_pw)", bufs.alloc(&d_pw, (size_t)nray));
+  HIP_TRY_AS("hipMalloc(&d_work)", bufs.alloc(&d_work, (size_t)n_bins * (size_t)nray));
+  HIP_TRY_AS("hipMalloc(&d_prof)", bufs.alloc(&d_prof, (size_t)n_bins));
+  HIP_TRY_AS("hipMalloc(&d_np)", bufs.alloc(&d_np, (size_t)nray));
+  HIP_TRY(hipMemcpy2D(d_rv, sizeof(double) * nv * (size_t)maxnp, ray_vec, sizeof(double) * nv * npt,
                       sizeof(double) * nv * (size_t)maxnp, (size_t)nray, hipMemcpyHostToDevice));
-  DEP_TRY(hipMemcpy(d_pw, initial_ray_power, sizeof(double) * (size_t)nray, hipMemcpyHostToDevice));
-  DEP_TRY(hipMemcpy(d_np, npoints, sizeof(int32_t) * (size_t)nray, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_pw, initial_ray_power, sizeof(double) * (size_t)nray, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_np, npoints, sizeof(int32_t) * (size_t)nray, hipMemcpyHostToDevice));
   rc = rays_hip_deposition_device(&q, which, n_bins, nray, d_rv, d_np, d_pw, d_work, nullptr, d_prof, nullptr);
-  if (rc) { release(); return rc; }
-  DEP_TRY(hipDeviceSynchronize());
-  DEP_TRY(hipMemcpy(profile, d_prof, sizeof(double) * (size_t)n_bins, hipMemcpyDeviceToHost));
-  if (work) {  // device: [n_bins][nray]  ->  reference work(n_bins, nray) = C [nray][n_bins]
-    std::vector<double> w((size_t)n_bins * (size_t)nray);
-    DEP_TRY(hipMemcpy(w.data(), d_work, sizeof(double) * w.size(), hipMemcpyDeviceToHost));
-    for (int r = 0; r < nray; r++)
-      for (int b = 0; b < n_bins; b++) work[(size_t)r * n_bins + b] = w[(size_t)b * nray + r];
-  }
-#undef DEP_TRY
-  release();
+  if (rc) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(profile, d_prof, sizeof(double) * (size_t)n_bins, hipMemcpyDeviceToHost));
+  std::vector<double> wbuf;
+  if (work) HIP_TRY_AS("hipMemcpy (work)", work_to_host(d_work, n_bins, nray, work, &wbuf));
+  bufs.release();
   if (timing)
     std::fprintf(stderr, "[rays_hip_deposition] %d rays, %.1f MB of trajectories uploaded: %.2f ms\n", nray,
                  1e-6 * sizeof(double) * nv * (double)maxnp * (double)nray,
@@ -1511,37 +1274,26 @@ int rays_hip_deposition_last(const rays_params_t* p, int which, int n_bins, int 
   const auto t0 = std::chrono::steady_clock::now();
   std::vector<double> carry((size_t)n_bins, 0.0), wbuf;
   bool have_carry = false;
+  CurrentDevice restore;
   for (const KeptBlock& b : blocks) {
     const int n = b.r1 - b.r0;
     if (n <= 0) continue;
     HIP_TRY(hipSetDevice(b.device));
+    DeviceBuffers bufs;
     double *d_pw = nullptr, *d_work = nullptr, *d_in = nullptr, *d_out = nullptr;
-    auto release = [&]() { (void)hipFree(d_pw); (void)hipFree(d_work); (void)hipFree(d_in); (void)hipFree(d_out); };
-#define DEPL_TRY(call)                                               \
-  do {                                                               \
-    hipError_t e_ = (call);                                          \
-    if (e_ != hipSuccess) { release(); return hip_fail(e_, #call); } \
-  } while (0)
-    DEPL_TRY(hipMalloc(&d_pw, sizeof(double) * (size_t)n));
-    DEPL_TRY(hipMalloc(&d_work, sizeof(double) * (size_t)n_bins * (size_t)n));
-    DEPL_TRY(hipMalloc(&d_in, sizeof(double) * (size_t)n_bins));
-    DEPL_TRY(hipMalloc(&d_out, sizeof(double) * (size_t)n_bins));
-    DEPL_TRY(hipMemcpy(d_pw, initial_ray_power + b.r0, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
-    if (have_carry) DEPL_TRY(hipMemcpy(d_in, carry.data(), sizeof(double) * (size_t)n_bins, hipMemcpyHostToDevice));
+    HIP_TRY_AS("hipMalloc(&d_pw)", bufs.alloc(&d_pw, (size_t)n));
+    HIP_TRY_AS("hipMalloc(&d_work)", bufs.alloc(&d_work, (size_t)n_bins * (size_t)n));
+    HIP_TRY_AS("hipMalloc(&d_in)", bufs.alloc(&d_in, (size_t)n_bins));
+    HIP_TRY_AS("hipMalloc(&d_out)", bufs.alloc(&d_out, (size_t)n_bins));
+    HIP_TRY(hipMemcpy(d_pw, initial_ray_power + b.r0, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
+    if (have_carry) HIP_TRY(hipMemcpy(d_in, carry.data(), sizeof(double) * (size_t)n_bins, hipMemcpyHostToDevice));
     rc = rays_hip_deposition_device(p, which, n_bins, n, b.d_ray_vec, b.d_npoints, d_pw, d_work, have_carry ? d_in : nullptr,
                                     d_out, nullptr);
-    if (rc) { release(); return rc; }
-    DEPL_TRY(hipDeviceSynchronize());
-    DEPL_TRY(hipMemcpy(carry.data(), d_out, sizeof(double) * (size_t)n_bins, hipMemcpyDeviceToHost));
+    if (rc) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(carry.data(), d_out, sizeof(double) * (size_t)n_bins, hipMemcpyDeviceToHost));
     have_carry = true;
-    if (work) {  // device: [n_bins][n]  ->  reference work(n_bins, nray) = C [nray][n_bins]
-      wbuf.resize((size_t)n_bins * (size_t)n);
-      DEPL_TRY(hipMemcpy(wbuf.data(), d_work, sizeof(double) * wbuf.size(), hipMemcpyDeviceToHost));
-      for (int r = 0; r < n; r++)
-        for (int bb = 0; bb < n_bins; bb++) work[(size_t)(b.r0 + r) * n_bins + bb] = wbuf[(size_t)bb * n + r];
-    }
-#undef DEPL_TRY
-    release();
+    if (work) HIP_TRY_AS("hipMemcpy (work)", work_to_host(d_work, n_bins, n, work + (size_t)b.r0 * n_bins, &wbuf));
   }
   std::memcpy(profile, carry.data(), sizeof(double) * (size_t)n_bins);
   if (timing)
@@ -1571,36 +1323,27 @@ static int ray_init_run(const rays_params_t* p, const rays_fan_t* fan, int nray_
     rc = get_axisym_device(&D);
     if (rc) return rc;
   }
+  DeviceBuffers bufs;
   double *d_launch = nullptr, *d_cand = nullptr;
   int *d_keep = nullptr, *d_bc = nullptr, *d_offs = nullptr, *d_first = nullptr;
-  auto release = [&]() {
-    (void)hipFree(d_launch); (void)hipFree(d_cand); (void)hipFree(d_keep); (void)hipFree(d_bc);
-    (void)hipFree(d_offs); (void)hipFree(d_first);
-  };
-#define INIT_TRY(call)                                   \
-  do {                                                   \
-    hipError_t e_ = (call);                              \
-    if (e_ != hipSuccess) { release(); return hip_fail(e_, #call); } \
-  } while (0)
-  INIT_TRY(hipMalloc(&d_launch, sizeof(double) * launch.size()));
-  INIT_TRY(hipMalloc(&d_cand, sizeof(double) * 3 * (size_t)n_cand));
-  INIT_TRY(hipMalloc(&d_keep, sizeof(int) * (size_t)n_cand));
-  INIT_TRY(hipMalloc(&d_bc, sizeof(int) * (size_t)nb));
-  INIT_TRY(hipMalloc(&d_offs, sizeof(int) * (size_t)(nb + 1)));
-  INIT_TRY(hipMalloc(&d_first, sizeof(int) * (size_t)F.n_launch));
-  INIT_TRY(hipMemcpyAsync(d_launch, launch.data(), sizeof(double) * launch.size(), hipMemcpyHostToDevice, stream));
+  HIP_TRY_AS("hipMalloc(&d_launch)", bufs.alloc(&d_launch, launch.size()));
+  HIP_TRY_AS("hipMalloc(&d_cand)", bufs.alloc(&d_cand, 3 * (size_t)n_cand));
+  HIP_TRY_AS("hipMalloc(&d_keep)", bufs.alloc(&d_keep, (size_t)n_cand));
+  HIP_TRY_AS("hipMalloc(&d_bc)", bufs.alloc(&d_bc, (size_t)nb));
+  HIP_TRY_AS("hipMalloc(&d_offs)", bufs.alloc(&d_offs, (size_t)(nb + 1)));
+  HIP_TRY_AS("hipMalloc(&d_first)", bufs.alloc(&d_first, (size_t)F.n_launch));
+  HIP_TRY(hipMemcpyAsync(d_launch, launch.data(), sizeof(double) * launch.size(), hipMemcpyHostToDevice, stream));
   F.launch = d_launch;
-  INIT_TRY(rays::launch_ray_init(p->equilib_model, p->nspec + 1, D, F, n_cand, d_cand, d_keep, d_bc, d_offs,
-                                 d_first, d_rvec0, d_rindex_vec0, stream));
+  HIP_TRY(rays::launch_ray_init(p->equilib_model, p->nspec + 1, D, F, n_cand, d_cand, d_keep, d_bc, d_offs,
+                                d_first, d_rvec0, d_rindex_vec0, stream));
   int total = 0;
-  INIT_TRY(hipMemcpyAsync(&total, d_offs + nb, sizeof(int), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(&total, d_offs + nb, sizeof(int), hipMemcpyDeviceToHost, stream));
   if (first_of_launch_host) {
     first_of_launch_host->resize(F.n_launch);
-    INIT_TRY(hipMemcpyAsync(first_of_launch_host->data(), d_first, sizeof(int) * F.n_launch, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(first_of_launch_host->data(), d_first, sizeof(int) * F.n_launch, hipMemcpyDeviceToHost,
+                           stream));
   }
-  INIT_TRY(hipStreamSynchronize(stream));
-#undef INIT_TRY
-  release();
+  HIP_TRY(hipStreamSynchronize(stream));
   *nray = total;
   if (total == 0) return fail("No successful ray initializations");  // simple_slab_ray_init_m.f90:172
   return 0;
@@ -1625,40 +1368,34 @@ int rays_hip_ray_init(const rays_params_t* p, const rays_fan_t* fan, int nray_ma
     const char* why = "";
     if (fan_setup(p, fan, nray_max, &F, &launch, &per_r0, &why)) return fail(why);
   }
+  DeviceBuffers bufs;
   double *d_r = nullptr, *d_n = nullptr;
-  HIP_TRY(hipMalloc(&d_r, sizeof(double) * 3 * (size_t)nray_max));
-  if (hipMalloc(&d_n, sizeof(double) * 3 * (size_t)nray_max) != hipSuccess) {
-    (void)hipFree(d_r);
-    return fail("rays_hip_ray_init: out of device memory");
-  }
+  HIP_TRY_AS("hipMalloc(&d_r)", bufs.alloc(&d_r, 3 * (size_t)nray_max));
+  if (bufs.alloc(&d_n, 3 * (size_t)nray_max) != hipSuccess) return fail("rays_hip_ray_init: out of device memory");
   std::vector<int> first;
   int per_r = 0;
   int rc = ray_init_run(p, fan, nray_max, d_r, d_n, nray, nullptr, &first, &per_r);
-  if (rc == 0) {
-    const size_t n = (size_t)*nray;
-    hipError_t e = hipMemcpy(rvec0, d_r, sizeof(double) * 3 * n, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(rindex_vec0, d_n, sizeof(double) * 3 * n, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) rc = hip_fail(e, "hipMemcpy (ray init results)");
-    if (rc == 0 && ray_pwr_wt) {
-      if (fan->model == RAYS_RAY_INIT_SIMPLE_SLAB) {  // :179,182: 1/nray, divided by nray once more
-        for (size_t i = 0; i < n; i++) ray_pwr_wt[i] = 1.0 / (double)n / (double)n;
-      } else if (fan->model == RAYS_RAY_INIT_AXISYM_R_Z_NPHI_NTHETA) {
-        for (size_t i = 0; i < n; i++) ray_pwr_wt[i] = 1.0 / (double)n;
-      } else {
-        // solovev_ray_init_nphi_ntheta_m.f90:196: only ray_pwr_wt(count) = 1. after each r-launch
-        // loop; the other entries are left unset by the reference (zero here)
-        for (size_t i = 0; i < n; i++) ray_pwr_wt[i] = 0.;
-        const int nl = (int)first.size();
-        for (int ir = 0; per_r > 0 && ir < nl / per_r; ir++) {
-          const int end = (ir + 1) * per_r < nl ? first[(ir + 1) * per_r] : (int)n;  // count after this r loop
-          if (end >= 1) ray_pwr_wt[end - 1] = 1.;
-        }
-      }
+  if (rc) return rc;
+  const size_t n = (size_t)*nray;
+  hipError_t e = hipMemcpy(rvec0, d_r, sizeof(double) * 3 * n, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(rindex_vec0, d_n, sizeof(double) * 3 * n, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return hip_fail(e, "hipMemcpy (ray init results)");
+  if (!ray_pwr_wt) return 0;
+  if (fan->model == RAYS_RAY_INIT_SIMPLE_SLAB) {  // :179,182: 1/nray, divided by nray once more
+    for (size_t i = 0; i < n; i++) ray_pwr_wt[i] = 1.0 / (double)n / (double)n;
+  } else if (fan->model == RAYS_RAY_INIT_AXISYM_R_Z_NPHI_NTHETA) {
+    for (size_t i = 0; i < n; i++) ray_pwr_wt[i] = 1.0 / (double)n;
+  } else {
+    // solovev_ray_init_nphi_ntheta_m.f90:196: only ray_pwr_wt(count) = 1. after each r-launch
+    // loop; the other entries are left unset by the reference (zero here)
+    for (size_t i = 0; i < n; i++) ray_pwr_wt[i] = 0.;
+    const int nl = (int)first.size();
+    for (int ir = 0; per_r > 0 && ir < nl / per_r; ir++) {
+      const int end = (ir + 1) * per_r < nl ? first[(ir + 1) * per_r] : (int)n;  // count after this r loop
+      if (end >= 1) ray_pwr_wt[end - 1] = 1.;
     }
   }
-  (void)hipFree(d_r);
-  (void)hipFree(d_n);
-  return rc;
+  return 0;
 }
 
 int rays_hip_probe(const rays_params_t* p, int n, const double* v, double* cold7, double* num7,
@@ -1667,38 +1404,29 @@ int rays_hip_probe(const rays_params_t* p, int n, const double* v, double* cold7
   if (rc) return rc;
   if (n <= 0) return 0;
   const size_t nv = (size_t)p->nv;
+  DeviceBuffers bufs;
   double *d_v = nullptr, *d_c = nullptr, *d_n = nullptr, *d_f = nullptr, *d_r = nullptr;
   int* d_k = nullptr;
-  auto release = [&]() {
-    (void)hipFree(d_v); (void)hipFree(d_c); (void)hipFree(d_n); (void)hipFree(d_f); (void)hipFree(d_r); (void)hipFree(d_k);
-  };
-#define PROBE_TRY(call)                                                  \
-  do {                                                                   \
-    hipError_t e_ = (call);                                              \
-    if (e_ != hipSuccess) { release(); return hip_fail(e_, #call); }     \
-  } while (0)
-  PROBE_TRY(hipMalloc(&d_v, sizeof(double) * nv * n));
-  PROBE_TRY(hipMalloc(&d_c, sizeof(double) * 7 * n));
-  PROBE_TRY(hipMalloc(&d_n, sizeof(double) * 7 * n));
-  PROBE_TRY(hipMalloc(&d_f, sizeof(double) * nv * n));
-  PROBE_TRY(hipMalloc(&d_r, sizeof(double) * n));
-  PROBE_TRY(hipMalloc(&d_k, sizeof(int) * 4 * n));
-  PROBE_TRY(hipMemcpy(d_v, v, sizeof(double) * nv * n, hipMemcpyHostToDevice));
+  HIP_TRY_AS("hipMalloc(&d_v)", bufs.alloc(&d_v, nv * n));
+  HIP_TRY_AS("hipMalloc(&d_c)", bufs.alloc(&d_c, 7 * (size_t)n));
+  HIP_TRY_AS("hipMalloc(&d_n)", bufs.alloc(&d_n, 7 * (size_t)n));
+  HIP_TRY_AS("hipMalloc(&d_f)", bufs.alloc(&d_f, nv * n));
+  HIP_TRY_AS("hipMalloc(&d_r)", bufs.alloc(&d_r, (size_t)n));
+  HIP_TRY_AS("hipMalloc(&d_k)", bufs.alloc(&d_k, 4 * (size_t)n));
+  HIP_TRY(hipMemcpy(d_v, v, sizeof(double) * nv * n, hipMemcpyHostToDevice));
   rays::DevParams D = make_dev_params(*p);
   if (p->equilib_model == RAYS_EQ_AXISYM) {
     rc = get_axisym_device(&D);
-    if (rc) { release(); return rc; }
+    if (rc) return rc;
   }
   hipLaunchKernelGGL(rays::probe_kernel, dim3((n + 63) / 64), dim3(64), 0, 0, D, p->equilib_model,
                      p->nspec + 1, p->nv, n, d_v, d_c, d_n, d_f, d_r, d_k);
-  PROBE_TRY(hipGetLastError());
-  PROBE_TRY(hipMemcpy(cold7, d_c, sizeof(double) * 7 * n, hipMemcpyDeviceToHost));
-  PROBE_TRY(hipMemcpy(num7, d_n, sizeof(double) * 7 * n, hipMemcpyDeviceToHost));
-  PROBE_TRY(hipMemcpy(dvds, d_f, sizeof(double) * nv * n, hipMemcpyDeviceToHost));
-  PROBE_TRY(hipMemcpy(resid, d_r, sizeof(double) * n, hipMemcpyDeviceToHost));
-  PROBE_TRY(hipMemcpy(codes, d_k, sizeof(int) * 4 * n, hipMemcpyDeviceToHost));
-#undef PROBE_TRY
-  release();
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(cold7, d_c, sizeof(double) * 7 * n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(num7, d_n, sizeof(double) * 7 * n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(dvds, d_f, sizeof(double) * nv * n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(resid, d_r, sizeof(double) * n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(codes, d_k, sizeof(int) * 4 * n, hipMemcpyDeviceToHost));
   return 0;
 }
 

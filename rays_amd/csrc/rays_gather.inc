@@ -74,12 +74,15 @@ void rccl_close() {
 
 // One device's share: trace rays [r0, r1) into slabs on that device; peers also pack them.
 struct GatherBlock {
+  explicit GatherBlock(int slot) : bufs(slot) {}
   int dev = 0, r0 = 0, r1 = 0;
+  SlotStream stream;
   hipStream_t st = nullptr;
-  double *d_r = nullptr, *d_n = nullptr, *d_rv = nullptr, *d_res = nullptr, *d_ev = nullptr, *d_er = nullptr, *d_mr = nullptr;
-  int32_t *d_np = nullptr, *d_sc = nullptr;
+  DeviceBuffers bufs;  // everything below but the root's slabs, which are the gathered result's
+  double *d_r = nullptr, *d_n = nullptr;
+  ResultArrays d;
   long long* d_off = nullptr;
-  double *d_pv = nullptr, *d_pr = nullptr;  // packed (peers: send buffers; root: receive buffers per peer)
+  double *d_pv = nullptr, *d_pr = nullptr;  // packed (peers: send buffers)
   std::vector<int32_t> np;                  // host copy of the block's npoints
   std::vector<long long> offs;
   long long total = 0;
@@ -87,7 +90,111 @@ struct GatherBlock {
   std::string err;
 };
 
+// The gathered result: library-owned until the next rays_hip_trace_gather call / rays_hip_finalize
+// (never destroyed: no HIP call may run during static destruction, when the runtime may be gone already)
+DeviceBuffers& g_gathered = *new DeviceBuffers(kResultSlot);
+
+// Phase 1 on one device (its own host thread): trace block g, slot g of the block cache.
+int gather_trace_block(int g, GatherBlock& b, const ResultArrays& A, const rays_params_t* p, int nray,
+                       const double* rvec0, const double* rindex_vec0) {
+  const size_t npt = (size_t)p->nstep_max + 1, nv = (size_t)p->nv;
+  const int n = b.r1 - b.r0;
+  HIP_TRY(hipSetDevice(b.dev));
+  claim_slot_for_device(g, b.dev);  // slot g may hold another device's stream and blocks (rays_hip_trace: slots per device)
+  HIP_TRY_AS("hipStreamCreate", b.stream.open(g));
+  b.st = b.stream.get();
+  if (n <= 0) return 0;
+  HIP_TRY_AS("hipMalloc(&b.d_r)", b.bufs.alloc(&b.d_r, 3 * (size_t)n));
+  HIP_TRY_AS("hipMalloc(&b.d_n)", b.bufs.alloc(&b.d_n, 3 * (size_t)n));
+  if (g == 0) {  // the root traces straight into its slab of the global arrays
+    b.d = A;
+    HIP_TRY(hipMemsetAsync(A.rv, 0, sizeof(double) * npt * nv * (size_t)nray, b.st));  // ray_results_m.f90:154-164
+    HIP_TRY(hipMemsetAsync(A.res, 0, sizeof(double) * npt * (size_t)nray, b.st));
+  } else {
+    HIP_TRY_AS("hipMalloc (result arrays)", b.d.alloc(b.bufs, (size_t)n, npt, nv));
+  }
+  HIP_TRY(hipMemcpyAsync(b.d_r, rvec0 + 3 * (size_t)b.r0, sizeof(double) * 3 * n, hipMemcpyHostToDevice, b.st));
+  HIP_TRY(hipMemcpyAsync(b.d_n, rindex_vec0 + 3 * (size_t)b.r0, sizeof(double) * 3 * n, hipMemcpyHostToDevice, b.st));
+  const int rc = rays_hip_trace_device(p, n, b.d_r, b.d_n, b.d.rv, b.d.res, b.d.np, b.d.sc, b.d.ev, b.d.er, b.d.mr, b.st,
+                                       RAYS_TRACE_NO_ZERO_FILL);
+  if (rc || g == 0) return rc;
+  // pack: the block's points back to back
+  b.np.resize(n);
+  HIP_TRY(hipMemcpyAsync(b.np.data(), b.d.np, sizeof(int32_t) * n, hipMemcpyDeviceToHost, b.st));
+  HIP_TRY(hipStreamSynchronize(b.st));
+  b.offs.resize((size_t)n + 1);
+  b.offs[0] = 0;
+  for (int i = 0; i < n; i++) b.offs[(size_t)i + 1] = b.offs[i] + (b.np[i] > 0 ? b.np[i] : 0);
+  b.total = b.offs[n];
+  HIP_TRY_AS("hipMalloc(&b.d_off)", b.bufs.alloc(&b.d_off, (size_t)n + 1));
+  HIP_TRY_AS("hipMalloc(&b.d_pv)", b.bufs.alloc(&b.d_pv, nv * (size_t)std::max(b.total, 1ll)));
+  HIP_TRY_AS("hipMalloc(&b.d_pr)", b.bufs.alloc(&b.d_pr, (size_t)std::max(b.total, 1ll)));
+  HIP_TRY(hipMemcpyAsync(b.d_off, b.offs.data(), sizeof(long long) * ((size_t)n + 1), hipMemcpyHostToDevice, b.st));
+  HIP_TRY(rays::launch_pack(true, n, (int)nv, p->nstep_max, b.d.np, b.d_off, b.d.rv, b.d.res, b.d_pv, b.d_pr, b.st));
+  return 0;
+}
+
+// Phase 2, the gather.  One grouped batch: peer g sends on its stream, the root receives on its own (rs) into rx's
+// buffers and unpacks them into the peers' slabs of the global arrays.  Asynchronous: the caller drains the streams.
+int gather_to_root(const std::deque<GatherBlock>& blk, const ResultArrays& A, const rays_params_t* p, int root,
+                   DeviceBuffers& rx) {
+  const int G = (int)blk.size();
+  const size_t npt = (size_t)p->nstep_max + 1, nv = (size_t)p->nv;
+  const hipStream_t rs = blk[0].st;
+  std::vector<double*> rx_pv(G, nullptr), rx_pr(G, nullptr);
+  std::vector<long long*> rx_off(G, nullptr);
+  if (hipSetDevice(root) != hipSuccess) return fail("rays_hip_trace_gather: hipSetDevice(root)");
+  for (int g = 1; g < G; g++) {
+    const GatherBlock& b = blk[g];
+    const int n = b.r1 - b.r0;
+    if (n <= 0) continue;
+    if (rx.alloc(&rx_pv[g], nv * (size_t)std::max(b.total, 1ll)) != hipSuccess ||
+        rx.alloc(&rx_pr[g], (size_t)std::max(b.total, 1ll)) != hipSuccess ||
+        rx.alloc(&rx_off[g], (size_t)n + 1) != hipSuccess ||
+        hipMemcpyAsync(rx_off[g], b.offs.data(), sizeof(long long) * ((size_t)n + 1), hipMemcpyHostToDevice,
+                       rs) != hipSuccess)
+      return fail("rays_hip_trace_gather: out of device memory on the root");
+  }
+  int r = g_rccl.GroupStart();
+  for (int g = 1; g < G && r == 0; g++) {
+    const GatherBlock& b = blk[g];
+    const size_t n = (size_t)(b.r1 - b.r0);
+    if (n == 0) continue;
+    // peer g -> root: summaries straight into the global arrays, trajectories packed
+    r = g_rccl.Send(b.d.np, n, kNcclInt32, 0, g_rccl.comms[g], b.st);
+    if (!r) r = g_rccl.Recv(A.np + b.r0, n, kNcclInt32, g, g_rccl.comms[0], rs);
+    if (!r) r = g_rccl.Send(b.d.sc, n, kNcclInt32, 0, g_rccl.comms[g], b.st);
+    if (!r) r = g_rccl.Recv(A.sc + b.r0, n, kNcclInt32, g, g_rccl.comms[0], rs);
+    if (!r) r = g_rccl.Send(b.d.ev, n * nv, kNcclDouble, 0, g_rccl.comms[g], b.st);
+    if (!r) r = g_rccl.Recv(A.ev + nv * (size_t)b.r0, n * nv, kNcclDouble, g, g_rccl.comms[0], rs);
+    if (!r) r = g_rccl.Send(b.d.er, n, kNcclDouble, 0, g_rccl.comms[g], b.st);
+    if (!r) r = g_rccl.Recv(A.er + b.r0, n, kNcclDouble, g, g_rccl.comms[0], rs);
+    if (!r) r = g_rccl.Send(b.d.mr, n, kNcclDouble, 0, g_rccl.comms[g], b.st);
+    if (!r) r = g_rccl.Recv(A.mr + b.r0, n, kNcclDouble, g, g_rccl.comms[0], rs);
+    if (b.total > 0) {
+      if (!r) r = g_rccl.Send(b.d_pv, (size_t)b.total * nv, kNcclDouble, 0, g_rccl.comms[g], b.st);
+      if (!r) r = g_rccl.Recv(rx_pv[g], (size_t)b.total * nv, kNcclDouble, g, g_rccl.comms[0], rs);
+      if (!r) r = g_rccl.Send(b.d_pr, (size_t)b.total, kNcclDouble, 0, g_rccl.comms[g], b.st);
+      if (!r) r = g_rccl.Recv(rx_pr[g], (size_t)b.total, kNcclDouble, g, g_rccl.comms[0], rs);
+    }
+  }
+  const int r2 = g_rccl.GroupEnd();
+  if (r || r2) return rccl_fail(r ? r : r2, "grouped ncclSend/ncclRecv");
+  // unpack every peer's block into its slab of the global arrays (zero-filled in phase 1)
+  for (int g = 1; g < G; g++) {
+    const GatherBlock& b = blk[g];
+    const int n = b.r1 - b.r0;
+    if (n <= 0 || b.total == 0) continue;
+    if (rays::launch_pack(false, n, (int)nv, p->nstep_max, A.np + b.r0, rx_off[g], A.rv + npt * nv * (size_t)b.r0,
+                          A.res + npt * (size_t)b.r0, rx_pv[g], rx_pr[g], rs) != hipSuccess)
+      return fail("rays_hip_trace_gather: unpack kernel launch failed");
+  }
+  return 0;
+}
+
 }  // namespace
+
+static void drop_gathered_result() { g_gathered.release(); }
 
 extern "C" int rays_hip_trace_gather(const rays_params_t* p, int nray, const double* rvec0, const double* rindex_vec0,
                                      rays_device_result_t* out) {
@@ -119,170 +226,38 @@ extern "C" int rays_hip_trace_gather(const rays_params_t* p, int nray, const dou
     rc = rccl_open(devs);
     if (rc) return rc;
   }
-  // ---- the root's global arrays (library-owned until the next call / rays_hip_finalize) -----------------------
-#define G_TRY(call)                                          \
-  do {                                                       \
-    hipError_t e_ = (call);                                  \
-    if (e_ != hipSuccess) return hip_fail(e_, #call);        \
-  } while (0)
-  G_TRY(hipSetDevice(root));
-  static const int kResultSlot = 16;  // buffer cache slot of the gathered result (slots 0..15: the blocks)
-  static void* held[7] = {nullptr};   // the previous call's result: valid until now
-  for (void*& h : held) {
-    cached_free(kResultSlot, h);
-    h = nullptr;
-  }
+  // ---- the root's global arrays: the previous call's result is valid until now ---------------------------------
+  HIP_TRY(hipSetDevice(root));
+  g_gathered.release();
   claim_slot_for_device(kResultSlot, root);
-  double *g_rv = nullptr, *g_res = nullptr, *g_ev = nullptr, *g_er = nullptr, *g_mr = nullptr;
-  int32_t *g_np = nullptr, *g_sc = nullptr;
-  G_TRY(cached_malloc(kResultSlot, (void**)&g_rv, sizeof(double) * npt * nv * (size_t)nray));
-  G_TRY(cached_malloc(kResultSlot, (void**)&g_res, sizeof(double) * npt * (size_t)nray));
-  G_TRY(cached_malloc(kResultSlot, (void**)&g_np, sizeof(int32_t) * (size_t)nray));
-  G_TRY(cached_malloc(kResultSlot, (void**)&g_sc, sizeof(int32_t) * (size_t)nray));
-  G_TRY(cached_malloc(kResultSlot, (void**)&g_ev, sizeof(double) * nv * (size_t)nray));
-  G_TRY(cached_malloc(kResultSlot, (void**)&g_er, sizeof(double) * (size_t)nray));
-  G_TRY(cached_malloc(kResultSlot, (void**)&g_mr, sizeof(double) * (size_t)nray));
-  {
-    void* now[7] = {g_rv, g_res, g_np, g_sc, g_ev, g_er, g_mr};
-    std::memcpy(held, now, sizeof held);
-  }
+  ResultArrays A;
+  HIP_TRY_AS("hipMalloc (result arrays)", A.alloc(g_gathered, (size_t)nray, npt, nv));
   // ---- phase 1: every device traces its block (one host thread per device) ------------------------------------
+  // (blk and rx give their buffers back to the cache when this call returns: after the streams are drained below)
   const int per = (nray + G - 1) / G;
-  std::vector<GatherBlock> blk(G);
+  std::deque<GatherBlock> blk;
+  DeviceBuffers rx(0);  // the root's receive buffers, from the root block's slot
   std::vector<std::thread> th;
   for (int g = 0; g < G; g++) {
-    GatherBlock& b = blk[g];
-    b.dev = devs[g];
-    b.r0 = std::min(nray, g * per);
-    b.r1 = std::min(nray, (g + 1) * per);
+    blk.emplace_back(g);
+    blk[g].dev = devs[g];
+    blk[g].r0 = std::min(nray, g * per);
+    blk[g].r1 = std::min(nray, (g + 1) * per);
+  }
+  for (int g = 0; g < G; g++)
     th.emplace_back([&, g] {
       GatherBlock& b = blk[g];
-      const int n = b.r1 - b.r0;
-      auto bad = [&](hipError_t e, const char* what) {
-        b.rc = hip_fail(e, what);
-        b.err = g_err;
-      };
-#define B_TRY(call)                                   \
-  {                                                   \
-    hipError_t e_ = (call);                           \
-    if (e_ != hipSuccess) { bad(e_, #call); return; } \
-  }
-      B_TRY(hipSetDevice(b.dev));
-      claim_slot_for_device(g, b.dev);  // slot g may hold another device's stream and blocks (rays_hip_trace: slots per device)
-      bool own = false;
-      B_TRY(cached_stream(g, &b.st, &own));
-      if (n <= 0) return;
-      const bool is_root = g == 0;
-      B_TRY(cached_malloc(g, (void**)&b.d_r, sizeof(double) * 3 * n));
-      B_TRY(cached_malloc(g, (void**)&b.d_n, sizeof(double) * 3 * n));
-      if (is_root) {  // the root traces straight into its slab of the global arrays
-        b.d_rv = g_rv; b.d_res = g_res; b.d_np = g_np; b.d_sc = g_sc; b.d_ev = g_ev; b.d_er = g_er; b.d_mr = g_mr;
-        B_TRY(hipMemsetAsync(g_rv, 0, sizeof(double) * npt * nv * (size_t)nray, b.st));  // ray_results_m.f90:154-164
-        B_TRY(hipMemsetAsync(g_res, 0, sizeof(double) * npt * (size_t)nray, b.st));
-      } else {
-        B_TRY(cached_malloc(g, (void**)&b.d_rv, sizeof(double) * npt * nv * n));
-        B_TRY(cached_malloc(g, (void**)&b.d_res, sizeof(double) * npt * n));
-        B_TRY(cached_malloc(g, (void**)&b.d_np, sizeof(int32_t) * n));
-        B_TRY(cached_malloc(g, (void**)&b.d_sc, sizeof(int32_t) * n));
-        B_TRY(cached_malloc(g, (void**)&b.d_ev, sizeof(double) * nv * n));
-        B_TRY(cached_malloc(g, (void**)&b.d_er, sizeof(double) * n));
-        B_TRY(cached_malloc(g, (void**)&b.d_mr, sizeof(double) * n));
-      }
-      B_TRY(hipMemcpyAsync(b.d_r, rvec0 + 3 * (size_t)b.r0, sizeof(double) * 3 * n, hipMemcpyHostToDevice, b.st));
-      B_TRY(hipMemcpyAsync(b.d_n, rindex_vec0 + 3 * (size_t)b.r0, sizeof(double) * 3 * n, hipMemcpyHostToDevice, b.st));
-      b.rc = rays_hip_trace_device(p, n, b.d_r, b.d_n, b.d_rv, b.d_res, b.d_np, b.d_sc, b.d_ev, b.d_er, b.d_mr, b.st,
-                                   RAYS_TRACE_NO_ZERO_FILL);
-      if (b.rc) { b.err = g_err; return; }
-      if (!is_root) {  // pack: the block's points back to back
-        b.np.resize(n);
-        B_TRY(hipMemcpyAsync(b.np.data(), b.d_np, sizeof(int32_t) * n, hipMemcpyDeviceToHost, b.st));
-        B_TRY(hipStreamSynchronize(b.st));
-        b.offs.resize((size_t)n + 1);
-        b.offs[0] = 0;
-        for (int i = 0; i < n; i++) b.offs[(size_t)i + 1] = b.offs[i] + (b.np[i] > 0 ? b.np[i] : 0);
-        b.total = b.offs[n];
-        B_TRY(cached_malloc(g, (void**)&b.d_off, sizeof(long long) * ((size_t)n + 1)));
-        B_TRY(cached_malloc(g, (void**)&b.d_pv, sizeof(double) * nv * (size_t)std::max(b.total, 1ll)));
-        B_TRY(cached_malloc(g, (void**)&b.d_pr, sizeof(double) * (size_t)std::max(b.total, 1ll)));
-        B_TRY(hipMemcpyAsync(b.d_off, b.offs.data(), sizeof(long long) * ((size_t)n + 1), hipMemcpyHostToDevice, b.st));
-        B_TRY(rays::launch_pack(true, n, (int)nv, p->nstep_max, b.d_np, b.d_off, b.d_rv, b.d_res, b.d_pv, b.d_pr, b.st));
-      }
-#undef B_TRY
+      b.rc = gather_trace_block(g, b, A, p, nray, rvec0, rindex_vec0);
+      if (b.rc) b.err = g_err;  // (the message is this worker thread's)
     });
-  }
   for (auto& t : th) t.join();
-  auto release_blocks = [&]() {
-    for (int g = 0; g < G; g++) {
-      GatherBlock& b = blk[g];
-      cached_free(g, b.d_r); cached_free(g, b.d_n); cached_free(g, b.d_off); cached_free(g, b.d_pv); cached_free(g, b.d_pr);
-      if (g > 0) {
-        cached_free(g, b.d_rv); cached_free(g, b.d_res); cached_free(g, b.d_np); cached_free(g, b.d_sc);
-        cached_free(g, b.d_ev); cached_free(g, b.d_er); cached_free(g, b.d_mr);
-      }
-    }
-  };
   for (int g = 0; g < G; g++)
     if (blk[g].rc) {
       g_err = blk[g].err;
-      release_blocks();
       return blk[g].rc;
     }
-  // ---- phase 2: the gather.  One grouped batch: peer g sends on its stream, the root receives on its own ------
-  std::vector<double*> rx_pv(G, nullptr), rx_pr(G, nullptr);
-  std::vector<long long*> rx_off(G, nullptr);
-  hipStream_t rs = blk[0].st;
-  int result = 0;
-  do {
-    if (G == 1) break;
-    if (hipSetDevice(root) != hipSuccess) { result = fail("rays_hip_trace_gather: hipSetDevice(root)"); break; }
-    bool ok = true;
-    for (int g = 1; g < G && ok; g++) {
-      const GatherBlock& b = blk[g];
-      const int n = b.r1 - b.r0;
-      if (n <= 0) continue;
-      ok = cached_malloc(0, (void**)&rx_pv[g], sizeof(double) * nv * (size_t)std::max(b.total, 1ll)) == hipSuccess &&
-           cached_malloc(0, (void**)&rx_pr[g], sizeof(double) * (size_t)std::max(b.total, 1ll)) == hipSuccess &&
-           cached_malloc(0, (void**)&rx_off[g], sizeof(long long) * ((size_t)n + 1)) == hipSuccess &&
-           hipMemcpyAsync(rx_off[g], b.offs.data(), sizeof(long long) * ((size_t)n + 1), hipMemcpyHostToDevice, rs) == hipSuccess;
-    }
-    if (!ok) { result = fail("rays_hip_trace_gather: out of device memory on the root"); break; }
-    int r = g_rccl.GroupStart();
-    for (int g = 1; g < G && r == 0; g++) {
-      const GatherBlock& b = blk[g];
-      const size_t n = (size_t)(b.r1 - b.r0);
-      if (n == 0) continue;
-      // peer g -> root: summaries straight into the global arrays, trajectories packed
-      r = g_rccl.Send(b.d_np, n, kNcclInt32, 0, g_rccl.comms[g], b.st);
-      if (!r) r = g_rccl.Recv(g_np + b.r0, n, kNcclInt32, g, g_rccl.comms[0], rs);
-      if (!r) r = g_rccl.Send(b.d_sc, n, kNcclInt32, 0, g_rccl.comms[g], b.st);
-      if (!r) r = g_rccl.Recv(g_sc + b.r0, n, kNcclInt32, g, g_rccl.comms[0], rs);
-      if (!r) r = g_rccl.Send(b.d_ev, n * nv, kNcclDouble, 0, g_rccl.comms[g], b.st);
-      if (!r) r = g_rccl.Recv(g_ev + nv * (size_t)b.r0, n * nv, kNcclDouble, g, g_rccl.comms[0], rs);
-      if (!r) r = g_rccl.Send(b.d_er, n, kNcclDouble, 0, g_rccl.comms[g], b.st);
-      if (!r) r = g_rccl.Recv(g_er + b.r0, n, kNcclDouble, g, g_rccl.comms[0], rs);
-      if (!r) r = g_rccl.Send(b.d_mr, n, kNcclDouble, 0, g_rccl.comms[g], b.st);
-      if (!r) r = g_rccl.Recv(g_mr + b.r0, n, kNcclDouble, g, g_rccl.comms[0], rs);
-      if (b.total > 0) {
-        if (!r) r = g_rccl.Send(b.d_pv, (size_t)b.total * nv, kNcclDouble, 0, g_rccl.comms[g], b.st);
-        if (!r) r = g_rccl.Recv(rx_pv[g], (size_t)b.total * nv, kNcclDouble, g, g_rccl.comms[0], rs);
-        if (!r) r = g_rccl.Send(b.d_pr, (size_t)b.total, kNcclDouble, 0, g_rccl.comms[g], b.st);
-        if (!r) r = g_rccl.Recv(rx_pr[g], (size_t)b.total, kNcclDouble, g, g_rccl.comms[0], rs);
-      }
-    }
-    const int r2 = g_rccl.GroupEnd();
-    if (r || r2) { result = rccl_fail(r ? r : r2, "grouped ncclSend/ncclRecv"); break; }
-    // unpack every peer's block into its slab of the global arrays (zero-filled above)
-    for (int g = 1; g < G; g++) {
-      const GatherBlock& b = blk[g];
-      const int n = b.r1 - b.r0;
-      if (n <= 0 || b.total == 0) continue;
-      if (rays::launch_pack(false, n, (int)nv, p->nstep_max, g_np + b.r0, rx_off[g], g_rv + npt * nv * (size_t)b.r0,
-                            g_res + npt * (size_t)b.r0, rx_pv[g], rx_pr[g], rs) != hipSuccess) {
-        result = fail("rays_hip_trace_gather: unpack kernel launch failed");
-        break;
-      }
-    }
-  } while (0);
+  // ---- phase 2: the gather ---------------------------------------------------------------------------------------
+  int result = G > 1 ? gather_to_root(blk, A, p, root, rx) : 0;
   // ---- completion: every stream drained before the buffers go back to the cache ---------------------------------
   for (int g = 0; g < G; g++) {
     if (!blk[g].st) continue;
@@ -290,13 +265,10 @@ extern "C" int rays_hip_trace_gather(const rays_params_t* p, int nray, const dou
       result = fail("rays_hip_trace_gather: stream synchronisation failed");
   }
   (void)hipSetDevice(root);
-  for (int g = 1; g < G; g++) { cached_free(0, rx_pv[g]); cached_free(0, rx_pr[g]); cached_free(0, rx_off[g]); }
-  release_blocks();
   if (result) return result;
-  out->ray_vec = g_rv; out->residual = g_res; out->npoints = g_np; out->stop_code = g_sc;
-  out->end_ray_vec = g_ev; out->end_residuals = g_er; out->max_residuals = g_mr;
+  out->ray_vec = A.rv; out->residual = A.res; out->npoints = A.np; out->stop_code = A.sc;
+  out->end_ray_vec = A.ev; out->end_residuals = A.er; out->max_residuals = A.mr;
   return 0;
-#undef G_TRY
 }
 
 // Copies a gathered result (or any device-resident result on `device`) into host arrays: the

@@ -277,6 +277,12 @@ def init_devices(device_ids):
         raise RaysHipError("rays_hip_init_devices: " + last_error())
 
 
+def finalize():
+    """rays_hip_finalize: everything the library holds on the devices and in pinned memory goes back to the driver.
+    The tables and settings stay; the next call initialises again as the first one did."""
+    _check(load().rays_hip_finalize(), "rays_hip_finalize")
+
+
 def deposition_host(p: RaysParams, which: str, n_bins: int, ray_vec, npoints, initial_ray_power):
     """rays_hip_deposition: host arrays in (the ray_results_m image), (work[nray][n_bins], profile[n_bins]) out."""
     ray_vec = np.ascontiguousarray(ray_vec, dtype=np.float64)

@@ -29,3 +29,10 @@ extern "C" void rays_emul_runtime_stats(long long* launches, long long* wrong_de
   std::lock_guard<std::mutex> lk(s.mu);
   *launches = s.launches; *wrong_device = s.wrong_device; *live_allocations = (long long)s.allocs.size();
 }
+// what rays_hip_finalize has to bring to zero besides the device allocations
+extern "C" void rays_emul_runtime_live(long long* pinned, long long* streams, long long* events) {
+  hip_emul::State& s = hip_emul::state();
+  *pinned = s.live_pinned; *streams = s.live_streams; *events = s.live_events;
+}
+// the calling thread's current device
+extern "C" int rays_emul_current_device() { return hip_emul::current(); }

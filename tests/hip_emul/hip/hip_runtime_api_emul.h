@@ -13,6 +13,7 @@
 //   * kernels run at once on the calling thread, block by block and lane by lane (one lane per wave, as in
 //     emul_trace.cpp); streams are therefore always idle and events always complete.
 #pragma once
+#include <atomic>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -44,6 +45,7 @@ struct State {
   std::map<const char*, Alloc> allocs;   // device memory: base -> (size, owner)
   std::map<int, emul_stream> null_stream;
   long long launches = 0, wrong_device = 0;
+  std::atomic<long long> live_pinned{0}, live_streams{0}, live_events{0};   // created and not yet destroyed
 };
 inline State& state() { static State s; return s; }
 inline int& current() { static thread_local int d = 0; return d; }
@@ -133,16 +135,30 @@ inline hipError_t hipFree(void* p) {
 }
 inline hipError_t hipHostMalloc(void** out, size_t bytes, unsigned) {
   *out = std::malloc(bytes ? bytes : 1);
-  return *out ? hipSuccess : hip_emul::set(hipErrorOutOfMemory);
+  if (!*out) return hip_emul::set(hipErrorOutOfMemory);
+  hip_emul::state().live_pinned++;
+  return hipSuccess;
 }
-inline hipError_t hipHostFree(void* p) { std::free(p); return hipSuccess; }
+inline hipError_t hipHostFree(void* p) {
+  if (p) hip_emul::state().live_pinned--;
+  std::free(p);
+  return hipSuccess;
+}
 
-inline hipError_t hipStreamCreate(hipStream_t* st) { *st = new emul_stream{hip_emul::current()}; return hipSuccess; }
-inline hipError_t hipStreamDestroy(hipStream_t st) { delete st; return hipSuccess; }
+inline hipError_t hipStreamCreate(hipStream_t* st) {
+  *st = new emul_stream{hip_emul::current()};
+  hip_emul::state().live_streams++;
+  return hipSuccess;
+}
+inline hipError_t hipStreamDestroy(hipStream_t st) { if (st) hip_emul::state().live_streams--; delete st; return hipSuccess; }
 inline hipError_t hipStreamSynchronize(hipStream_t st) { return hip_emul::set(hip_emul::check(st, nullptr, 0, "hipStreamSynchronize")); }
-inline hipError_t hipEventCreate(hipEvent_t* e) { *e = new emul_event{hip_emul::current()}; return hipSuccess; }
+inline hipError_t hipEventCreate(hipEvent_t* e) {
+  *e = new emul_event{hip_emul::current()};
+  hip_emul::state().live_events++;
+  return hipSuccess;
+}
 inline hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { return hipEventCreate(e); }
-inline hipError_t hipEventDestroy(hipEvent_t e) { delete e; return hipSuccess; }
+inline hipError_t hipEventDestroy(hipEvent_t e) { if (e) hip_emul::state().live_events--; delete e; return hipSuccess; }
 inline hipError_t hipEventRecord(hipEvent_t, hipStream_t st) { return hip_emul::set(hip_emul::check(st, nullptr, 0, "hipEventRecord")); }
 inline hipError_t hipEventSynchronize(hipEvent_t) { return hipSuccess; }
 inline hipError_t hipEventQuery(hipEvent_t) { return hipSuccess; }
