@@ -5,18 +5,20 @@
 //   RK4_ode      RK4_ode_m.f90:59-94      (4 stages, early return leaves v untouched)
 //   eqn_ray / check_save                  (rays_device.hpp)
 //
-// The integrator is a 4-state machine around ONE RHS evaluation per wave-loop trip:
-//   stage 0,1,2 : evaluate f at w (= v + ds*f1/2, v + ds*f2/2, v + ds*f3)  -> f2, f3, f4
+// One iteration of the wave loop is one RK4 STEP: a counted loop over the four RHS evaluations, in the order
 //   stage 3     : w = v + ds*(f1 + 2 f2 + 2 f3 + f4)/6 ; check_save(w) fused with the next step's
 //                 f1 = eqn_ray(w) (same equilibrium + dispersion derivatives, evaluated once)
+//   stage 0,1,2 : evaluate f at w (= v + ds*f1/2, v + ds*f2/2, v + ds*f3)  -> f2, f3, f4
 // A new ray starts in stage 3 with w = v0 (`first`), which is exactly the reference's initial
 // check_save call (ray_tracing.f90:100) and also yields the first step's f1.
-// The stage belongs to the WAVE: a lane under way advances by one stage on every trip, and a wave starts
-// rays only when no lane is under way or when the lanes under way are about to run stage 3, so all lanes
-// under way are at the same stage on every trip.  The stage is a scalar (one SGPR, never assigned under
-// lane-divergent control), the state machine a scalar switch with one region of lanes under way per arm,
-// check_save's share of the evaluation is skipped by a scalar branch on three trips of four, and whether
-// a pass is due is only asked on the trip that stage 3 follows (rays_rk4_body.inc).
+// A lane under way runs one stage per evaluation and a wave starts rays only between two iterations, so every
+// lane under way is at the stage of the copy of the loop body it is in: the stage is no variable.  The
+// one-wave-per-SIMD kernel unrolls the stage loop -- the stage and do_check are compile-time constants of each
+// copy, check_save's share, the record path and the next step's preparation exist once, in the stage-3 copy,
+// and the other three copies hold the light arm alone.  Whether a pass is due is asked once per step; when no
+// lane is under way after a stage, a scalar branch leaves the step (rays_rk4_body.inc).  The two-waves-per-SIMD
+// kernel runs ONE evaluation per iteration with the stage in a wave-uniform scalar (as a rolled stage loop it
+// needed 12 more registers and the 1 M-ray slab fan ran 2 % slower).
 //
 // Recorded points: the one-wave-per-SIMD kernel with nv = 7 passes them through a per-lane LDS window
 // and writes whole 64-byte sectors (PointWindow, rays_trace.hpp: HBM write traffic 1.06x the
@@ -114,9 +116,30 @@ rk4_resume_kernel(const DevParams P, const TraceArgs A) {
 }
 
 #if defined(RAYS_HOST_EMUL) && defined(RAYS_EMUL_CHECK_UNIFORM_STAGE)
-// Host emulation only: the trace bodies report a lane under way whose own stage differs from its wave's (or a lane whose
-// copy of the wave's stage differs from lane 0's) here -- on stderr, and counted for the test that built this.
+// Host emulation only: the trace bodies report a lane under way whose own stage differs from the stage of the copy of the
+// loop body it is in (two-waves body: from its wave's stage, and a lane whose copy of that scalar differs from lane 0's)
+// here -- on stderr, and counted for the test that built this.
 extern "C" __attribute__((visibility("default"), used)) inline int* rays_emul_uniform_stage_violations() {
+  static int n = 0;
+  return &n;
+}
+// ... and what the batching threshold sees each time a step asks it (lane 0 of the wave records): the step's alive_sum,
+// `occupied` and idle_acc after the step is settled.  [0] = number of entries asked for, then three ints per entry.
+extern "C" __attribute__((visibility("default"), used)) inline int* rays_emul_threshold_log(int reset) {
+  static int log[1 + 3 * 4096];
+  if (reset) log[0] = 0;
+  return log;
+}
+inline void threshold_asked(int alive_sum, int occupied, int idle_acc) {
+  int* log = rays_emul_threshold_log(0);
+  if (log[0] < 4096) {
+    int* e = log + 1 + 3 * log[0];
+    e[0] = alive_sum, e[1] = occupied, e[2] = idle_acc;
+  }
+  log[0]++;
+}
+// ... and the steps a wave left before their last stage because no lane was under way any more
+extern "C" __attribute__((visibility("default"), used)) inline int* rays_emul_early_step_exits() {
   static int n = 0;
   return &n;
 }

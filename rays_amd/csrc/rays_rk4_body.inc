@@ -20,6 +20,15 @@
     P.zf_xmin = in_vgpr(P_kernarg.zf_xmin);
     P.zf_xmax = in_vgpr(P_kernarg.zf_xmax);
   }
+#if RAYS_RK4_LONG_FIRST
+  // check_save's residual limit and the factor of dD/dw (deriv_cold): otherwise scalar re-loads from the kernarg segment
+  // inside the evaluation (~30 ns each for a lone wave) or two more scalar registers held across the unrolled step.  No
+  // gain on the Solovev headline (2.019 against 2.033 ms), but without them the axisym kernel of cfg 5b, which spills
+  // scalar registers, is 3.5 % SLOWER than before the step loop (2.113 -> 2.188 ms) and with them 1.6 % faster (2.083):
+  // profiles/r05/measurements/rk4_step_loop_ab.txt.  The one-wave-per-SIMD kernel has the vector registers.
+  P.resid_limit = in_vgpr(P_kernarg.resid_limit);
+  P.m1_over_omgrf = in_vgpr(P_kernarg.m1_over_omgrf);
+#endif
 #endif
 
   const unsigned total_lanes = gridDim.x * blockDim.x;
@@ -39,14 +48,27 @@
     ray = (int)r;
   }
 #endif
-  // The stage of the WAVE, not of a lane: a ray starts at stage 3, a lane under way advances by one stage per trip and
-  // never sits a trip out, and a pass starts rays only when no lane is under way or the lanes under way are about to
-  // run stage 3 -- so all lanes under way are at the same stage on every trip.  It is never assigned under
-  // lane-divergent control (it advances once per trip, a pass sets it to 3), so it lives in a scalar register, the
-  // state machine below is a scalar switch and check_save's share of rhs_eval is skipped by a scalar branch.
+  // One-wave-per-SIMD kernel (RAYS_RK4_LONG_FIRST): one iteration of the inner loop is one RK4 STEP of the wave, a counted
+  // loop over the four evaluations in the order stage 3, 0, 1, 2.  A ray starts at stage 3 -- the first evaluation of an
+  // iteration -- a lane under way runs one stage per evaluation and never sits one out, and a pass starts rays only
+  // between two iterations: so every lane under way is at the stage of the loop's copy it is in, and the stage is no
+  // variable of the kernel at all.  The stage loop is unrolled: the stage and do_check are compile-time constants of each
+  // copy (check_save's share, the record path and the next step's preparation exist in the stage-3 copy only; `acc = f`
+  // and `v = w` are renames), and the test "is a pass due" runs once per step.  Headline 2.35 -> 2.02 ms.
+  // The two-waves-per-SIMD kernel keeps one evaluation per iteration and the stage as a wave-uniform scalar `jw` (see its
+  // loop head below): the same invariant, checked trip by trip.
   // (-DRAYS_EMUL_CHECK_UNIFORM_STAGE, host emulation only: every lane also keeps the stage it would have on its own,
-  // and a lane under way that disagrees with the wave is reported -- rays_rk4.hpp: uniform_stage_violation.)
-  int jw = 3;
+  // and a lane under way that disagrees with the copy it is in is reported -- rays_rk4.hpp: uniform_stage_violation.)
+  // Unrolled where the four copies of the evaluation stay a few thousand instructions (the analytic derivatives, up to
+  // two species).  The larger evaluations (finite differences, multi-species damping, more species) run the same loop
+  // rolled: four copies of them pass the compiler's limit for a requested unroll (it then leaves the loop rolled and
+  // warns) and the 64 KB instruction cache.  That form is not measured on a GPU (no BASELINE config runs it; DESIGN.md 4.1).
+  constexpr bool kUnrollStages =
+      RAYS_RK4_LONG_FIRST && DERIV == RAYS_DERIV_COLD && (EQ & kEqMultiSpec) == 0 && NS <= 2;
+  [[maybe_unused]] constexpr int kStageUnroll = kUnrollStages ? 4 : 1;
+#if !RAYS_RK4_LONG_FIRST
+  int jw = 3;  // the two-waves kernel's stage: wave-uniform, never assigned under lane-divergent control (see its loop)
+#endif
 #if defined(RAYS_HOST_EMUL) && defined(RAYS_EMUL_CHECK_UNIFORM_STAGE)
   int j_lane = 3;
 #endif
@@ -144,12 +166,13 @@
   // travels in the value -- a lane mask of its own across the wave loop cost 23 spilled SGPRs)
   double dddw_f1 = 0.;
   bool can_refill = (unsigned)A_hot.nray > total_lanes;  // wave-uniform: the counter may still hand out a ray
-  // Idle lane-trips since the last pass (wave-uniform).  A pass can only become due on a trip that is followed by stage
-  // 3, so the sum is only needed there, every fourth trip.  Between two passes the lanes that hold a ray or want one
-  // (`occupied`, counted by the pass) stay the same and lanes only go from under way to parked, so the idle lanes of a
-  // trip are occupied minus the lanes under way: the common trip adds its count of lanes under way to alive_sum -- the
-  // count that also tells whether any lane is left -- and the fourth settles: idle_acc += 4 * occupied - alive_sum.
-  // Trip for trip the sum the threshold sees is what a ballot of the parked lanes on every trip gave.
+  // Idle lane-trips since the last pass (wave-uniform).  A pass can only fall between two steps, so the sum is settled
+  // once per step (by the two-waves kernel: on the trip that stage 3 follows).  Between two passes the lanes that hold a
+  // ray or want one (`occupied`, counted by the pass) stay the same and lanes only go from under way to parked, so the
+  // idle lanes of a trip are occupied minus the lanes under way: every stage adds its count of lanes under way to
+  // alive_sum -- the count that also tells whether any lane is left -- and the step settles:
+  // idle_acc += 4 * occupied - alive_sum.  Step for step the sum the threshold sees is what a ballot of the parked lanes
+  // on every trip gave.
   int idle_acc = 0, alive_sum = 0, occupied = 0;
   // RAYS_RK4_LONG_FIRST (the one-wave-per-SIMD kernel): two loops -- the outer one is the pass (cold: a handful of
   // times per wave), the inner one the trips between two passes (hot) -- and the rays are handed out "long rays first"
@@ -167,8 +190,12 @@
       continue;  // lanes that found their probe budget spent ask again
     }
     bool fire;
-    do {  // ---- the trips until the next pass is due ----
+    do {  // ---- the steps until the next pass is due ----
+      int n_alive = 0;
 #else
+  // The two-waves-per-SIMD kernel keeps ONE evaluation per iteration and the stage as a wave-uniform scalar, advanced
+  // once per trip and set to 3 by the pass: as a rolled stage loop it needed 238 registers for 226 and the 1 M-ray slab fan
+  // of cfg 4 ran 2.2 % slower (29.21 -> 29.85 ms, profiles/r05/measurements/rk4_step_loop_ab.txt).
   for (;;) {
     const int n_alive = (int)__popcll(__ballot(alive));
     bool fire = false;
@@ -179,6 +206,9 @@
       if (jw == 3) {  // the lanes under way are about to run stage 3: fresh rays can join them in step
         if (can_refill && occupied > n_alive) {
           idle_acc += 4 * occupied - alive_sum;
+#if defined(RAYS_HOST_EMUL) && defined(RAYS_EMUL_CHECK_UNIFORM_STAGE)
+          if ((threadIdx.x & 63u) == 0) threshold_asked(alive_sum, occupied, idle_acc);
+#endif
           fire = idle_acc >= RAYS_REFILL_EVENT_COST;
         }
         alive_sum = 0;
@@ -191,16 +221,28 @@
     {
 #endif
 
-    // ---- the one RHS evaluation of this trip -------------------------------------------------
+    // ---- one RK4 step: the evaluations of stage 3 (check_save + the step's first stage), 0, 1, 2 -----------------------
+#if RAYS_RK4_LONG_FIRST
+#pragma unroll kStageUnroll
+    for (int k = 0; k < 4; k++) {
+    const int jw = (k + 3) & 3;
+#else
+    {
+#endif
+    // ---- the RHS evaluation of this stage ----------------------------------------------------
     double f[NV], resid = 0.;
     int code = 0, cs_flag = 0;
     bool cs_stop = false;
-    // ---- the trip of the lanes under way: ONE region -- the evaluation, then the integrator's state machine as scalar
-    // branches on the wave's stage.  (A lane whose ray ends is parked until the wave's next pass over its idle lanes: its
-    // stop code goes into `first`.)
+    // ---- the lanes under way: ONE region -- the evaluation, then the arm of the stage.  Unrolled, the stage is a constant
+    // of this copy and only its own arm is left; rolled (and in the two-waves kernel) the arms are scalar branches on the
+    // wave's stage.  (A lane whose ray ends is parked until the wave's next pass over its idle lanes: its stop code goes
+    // into `first`.)
 #if defined(RAYS_HOST_EMUL) && defined(RAYS_EMUL_CHECK_UNIFORM_STAGE)
-    const int jw_lane0 = __shfl(jw, 0);  // (every lane of the emulated wave keeps its own copy of the wave's stage)
-    if (jw_lane0 != jw || (alive && j_lane != jw)) uniform_stage_violation(ray, alive ? j_lane : -1, jw);
+#if !RAYS_RK4_LONG_FIRST
+    // (the stage is a variable here: every lane of the emulated wave keeps its own copy, which must be lane 0's)
+    if (__shfl(jw, 0) != jw) uniform_stage_violation(ray, alive ? j_lane : -1, jw);
+#endif
+    if (alive && j_lane != jw) uniform_stage_violation(ray, j_lane, jw);
     j_lane = (j_lane + 1) & 3;
 #endif
     if (alive) {
@@ -216,10 +258,11 @@
       // The two arms are two if-then regions in sequence, not an if / else: as an if / else the compiler's structured
       // control flow runs the second arm behind a guard AFTER the first, keeps the first arm's inputs alive for it and
       // joins the arms' results by copies (33 64-bit moves per stage-3 trip, 8 per other trip); in sequence each arm
-      // updates acc, w and v in place.  Hence the second, opaque copy of the stage for the second test.
+      // updates acc, w and v in place.  Hence, where the stage loop is rolled, the second, opaque copy of the stage for the
+      // second test (unrolled, each copy holds the arm of its stage alone and the tests fold away).
       int jw_again = jw;
 #ifndef RAYS_HOST_EMUL
-      asm volatile("" : "+s"(jw_again));
+      if constexpr (!kUnrollStages) asm volatile("" : "+s"(jw_again));
 #endif
       if (jw != 3) {
         // Stages 0, 1, 2: acc += c f (c = 2, 2, 1) and w = v + (ds f)/2, v + ds f, v + (ds acc)/6.  The products by the
@@ -332,17 +375,30 @@
         }
       }
     }
+#if RAYS_RK4_LONG_FIRST
+    // the lanes still under way: what the step's idle lane-trips are settled with, and nobody left ends the step early
+    n_alive = (int)__popcll(__ballot(alive));
+    alive_sum += n_alive;
+#if defined(RAYS_HOST_EMUL) && defined(RAYS_EMUL_CHECK_UNIFORM_STAGE)
+    if (n_alive == 0 && k < 3 && (threadIdx.x & 63u) == 0) ++*rays_emul_early_step_exits();
+#endif
+    if (n_alive == 0) break;  // wave-uniform
+    }
+#else
     jw = (jw + 1) & 3;
+    }
+#endif
 #if RAYS_RK4_LONG_FIRST
     // ---- is a pass due? ------------------------------------------------------------------------------------------------
-    // A fresh ray joins the lanes under way at stage 3 (its first evaluation is the initial check_save): only a trip that
-    // is followed by stage 3 asks the threshold; the other three count their lanes under way and go on.
-    const int n_alive = (int)__popcll(__ballot(alive));
-    alive_sum += n_alive;
+    // A fresh ray joins the lanes under way at stage 3 (its first evaluation is the initial check_save), the first
+    // evaluation of a step: the threshold is asked once per step.
     fire = n_alive == 0;
-    if (jw == 3 && !fire) {  // wave-uniform
+    if (!fire) {  // wave-uniform
       if (can_refill && occupied > n_alive) {
         idle_acc += 4 * occupied - alive_sum;
+#if defined(RAYS_HOST_EMUL) && defined(RAYS_EMUL_CHECK_UNIFORM_STAGE)
+        if ((threadIdx.x & 63u) == 0) threshold_asked(alive_sum, occupied, idle_acc);
+#endif
         fire = idle_acc >= RAYS_REFILL_EVENT_COST;
       }
       alive_sum = 0;

@@ -78,7 +78,9 @@
       need_init = false;
       alive = true;
     }
-    // A pass runs when no lane is under way or when the lanes under way are about to run stage 3, and the rays it has
-    // just started begin there: the wave's stage (wave-uniform, assigned outside every lane-divergent region).
-    jw = 3;
+    // A pass runs between two steps of the wave -- when no lane is under way or when the lanes under way are about to run
+    // stage 3 -- and the rays it has just started begin there, with the step's first evaluation.
+#if !RAYS_RK4_LONG_FIRST
+    jw = 3;  // (the two-waves kernel's stage: wave-uniform, assigned outside every lane-divergent region)
+#endif
     occupied = (int)__popcll(__ballot(alive || pending || hungry));  // constant until the next pass
