@@ -245,6 +245,43 @@
           integer(c_int), value :: flags
        end function rays_hip_scan_device
 
+       ! Summary-only tracing (include/rays_hip.h): the per-ray rows of ray_results_m without ray_vec(:,:,:) and
+       ! residual(:,:) -- what scanner_m's aggregate_run_data keeps of a run.  Always the exact kernels.  The device
+       ! forms are asynchronous on hip_stream; d_start_ray_vec may be c_null_ptr.
+       integer(c_int) function rays_hip_trace_summary_device(p, nray, d_rvec0, d_rindex_vec0, d_npoints, d_stop_code, &
+                    & d_start_ray_vec, d_end_ray_vec, d_end_residuals, d_max_residuals, hip_stream) &
+                    & bind(C, name='rays_hip_trace_summary_device')
+          import :: c_int, c_ptr, rays_params_t
+          type(rays_params_t), intent(in) :: p
+          integer(c_int), value :: nray
+          type(c_ptr), value :: d_rvec0, d_rindex_vec0, d_npoints, d_stop_code, d_start_ray_vec
+          type(c_ptr), value :: d_end_ray_vec, d_end_residuals, d_max_residuals, hip_stream
+       end function rays_hip_trace_summary_device
+
+       ! outputs with a leading (slowest) run dimension: npoints(nray, n_runs), end_ray_vec(nv, nray, n_runs), ...
+       integer(c_int) function rays_hip_scan_summary_device(p, n_runs, d_ds_values, nray, d_rvec0, d_rindex_vec0, &
+                    & d_npoints, d_stop_code, d_start_ray_vec, d_end_ray_vec, d_end_residuals, d_max_residuals, &
+                    & hip_stream) bind(C, name='rays_hip_scan_summary_device')
+          import :: c_int, c_ptr, rays_params_t
+          type(rays_params_t), intent(in) :: p
+          integer(c_int), value :: n_runs, nray
+          type(c_ptr), value :: d_ds_values, d_rvec0, d_rindex_vec0, d_npoints, d_stop_code, d_start_ray_vec
+          type(c_ptr), value :: d_end_ray_vec, d_end_residuals, d_max_residuals, hip_stream
+       end function rays_hip_scan_summary_device
+
+       ! Blocking, host arrays: rays_hip_trace without the trajectories (only the summaries cross PCIe).
+       integer(c_int) function rays_hip_trace_summary(p, nray, rvec0, rindex_vec0, npoints, stop_code, &
+                    & start_ray_vec, end_ray_vec, end_residuals, max_residuals, elapsed_s) &
+                    & bind(C, name='rays_hip_trace_summary')
+          import :: c_int, c_int32_t, c_double, rays_params_t
+          type(rays_params_t), intent(in) :: p
+          integer(c_int), value :: nray
+          real(c_double), intent(in) :: rvec0(3,*), rindex_vec0(3,*)
+          integer(c_int32_t), intent(inout) :: npoints(*), stop_code(*)
+          real(c_double), intent(inout) :: start_ray_vec(*), end_ray_vec(*), end_residuals(*), max_residuals(*)
+          real(c_double), intent(out) :: elapsed_s
+       end function rays_hip_trace_summary
+
        ! ASYNCHRONOUS on hip_stream (blocking before round 3): synchronise the stream before d_v1 / d_resid /
        ! d_stop_code are read on the host or from another stream; one caller thread per (device, stream).
        integer(c_int) function rays_hip_ode_step_device(p, n, d_v0, d_s0, d_v1, d_resid, d_stop_code, hip_stream) &

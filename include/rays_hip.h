@@ -307,6 +307,46 @@ int rays_hip_scan_device(const rays_params_t* p, int n_runs, const double* d_ds_
                          double* d_end_ray_vec, double* d_end_residuals, double* d_max_residuals,
                          void* hip_stream, int flags);
 
+/* ---- summary-only tracing: ray ends and residual statistics, no trajectories --------------------
+ * For callers that never look at a trajectory -- the reference's own ray_scan, which keeps six things per run
+ * (scanner_m.f90:213-227, :236-284: end_ray_parameter, end_residuals, max_residuals, start_ray_vec, end_ray_vec,
+ * ray_stop_flag), aiming and absorbed-fraction surveys (end_ray_vec(8)), a Fortran host that would otherwise pull
+ * every recorded point over PCIe.  The same rays, steps and stop logic as rays_hip_trace_device, from kernels compiled
+ * without the recording path (EQ + 32 in their names): ray_vec(:,:,:) and residual(:,:) do not exist, on the device
+ * or anywhere else, and the library allocates nothing that scales with nstep_max.  Per ray:
+ *   npoints[nray], stop_code[nray], end_ray_vec[nray][nv], end_residuals[nray], max_residuals[nray]
+ *                            exactly what rays_hip_trace_device puts there, bit for bit (all required)
+ *   start_ray_vec[nray][nv]  ray_vec(:, 1, iray) of the full trace (ray_tracing.f90:259) -- also for a ray the initial
+ *                            check_save refuses; may be NULL
+ *   end_ray_parameter is end_ray_vec(7, iray); a ray's steps are npoints - 1.
+ * NUMERICS: these entries always run the EXACT kernels, whatever rays_hip_set_numerics says.  The tolerance setting
+ * is a permission, and exact results satisfy it; a tolerance variant would need recorded points both to evidence its
+ * per-step bar and for its hand-over, which reads residual(:).
+ * Built for every shape the library traces (the same lists; all of them under make FULL=1); another is refused by
+ * the message of rays_hip_check_params.  Refused by name: a null required pointer, nray < 0, n_runs * nray > 2^31 - 1.
+ * The device forms are asynchronous on hip_stream like rays_hip_trace_device. */
+int rays_hip_trace_summary_device(const rays_params_t* p, int nray, const double* d_rvec0,
+                                  const double* d_rindex_vec0, int32_t* d_npoints, int32_t* d_stop_code,
+                                  double* d_start_ray_vec /* may be NULL */, double* d_end_ray_vec,
+                                  double* d_end_residuals, double* d_max_residuals, void* hip_stream);
+/* The fused scan of rays_hip_scan_device, summary-only: outputs with a leading run dimension, npoints[n_runs][nray],
+ * start_ray_vec[n_runs][nray][nv], ...; each run equals a stand-alone summary trace with its ds. */
+int rays_hip_scan_summary_device(const rays_params_t* p, int n_runs, const double* d_ds_values, int nray,
+                                 const double* d_rvec0, const double* d_rindex_vec0, int32_t* d_npoints,
+                                 int32_t* d_stop_code, double* d_start_ray_vec /* may be NULL */,
+                                 double* d_end_ray_vec, double* d_end_residuals, double* d_max_residuals,
+                                 void* hip_stream);
+/* Host pointers, blocking.  Shards the rays over the devices of rays_hip_init[_devices] exactly as rays_hip_trace
+ * does (contiguous blocks, one host thread per device) with that entry's resource owners, and copies only the
+ * summaries: 16 + 8 (2 nv + 2) bytes per ray.  A device image kept by rays_hip_keep_last_result is dropped (it is not
+ * this call's result) and none is left. */
+int rays_hip_trace_summary(const rays_params_t* p, int nray, const double* rvec0, const double* rindex_vec0,
+                           int32_t* npoints, int32_t* stop_code, double* start_ray_vec /* may be NULL */,
+                           double* end_ray_vec, double* end_residuals, double* max_residuals,
+                           double* elapsed_s /* may be NULL */);
+/* Name of the kernel the summary entries launch for a fan of nray rays ("" when p is refused). */
+const char* rays_hip_summary_kernel_name_for(const rays_params_t* p, int nray);
+
 /* ---- one output step from arbitrary states: the ode_m interface --------------------------------
  * Batched image of `call ode_solver(eqn_ray, nv, v, s, sout, ray_stop)` (ode_m.f90:218-254, with
  * sout = s + ds and, for SG_ODE, ray_stop%rel_err/abs_err at rel_err0/abs_err0 as after

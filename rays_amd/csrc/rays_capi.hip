@@ -49,6 +49,27 @@ RAYS_DECL_ENTRIES(1, 1, 0)
 RAYS_DECL_ENTRIES(1, 1, 1)
 RAYS_DECL_ENTRIES(1, 2, 0)
 RAYS_DECL_ENTRIES(1, 2, 1)
+#undef RAYS_DECL_ENTRIES
+// the summary-only variants (rays_device.hpp: kEqNoTraj) of the same groups.  Weak: librays_hip.so holds all of them
+// (Makefile: SUM_OBJS); a library linked from this file and a few groups only -- the CPU tier's emulated C ABI --
+// finds the others null, and find_kernel then reports no summary kernel for them.
+#define RAYS_DECL_ENTRIES(s, e, d) \
+  __attribute__((weak)) const KernelEntry* rays_entries_sum_##s##_##e##_##d##_0_0(int* n); \
+  __attribute__((weak)) const KernelEntry* rays_entries_sum_##s##_##e##_##d##_1_0(int* n); \
+  __attribute__((weak)) const KernelEntry* rays_entries_sum_##s##_##e##_##d##_0_1(int* n); \
+  __attribute__((weak)) const KernelEntry* rays_entries_sum_##s##_##e##_##d##_1_1(int* n);
+RAYS_DECL_ENTRIES(0, 0, 0)
+RAYS_DECL_ENTRIES(0, 0, 1)
+RAYS_DECL_ENTRIES(0, 1, 0)
+RAYS_DECL_ENTRIES(0, 1, 1)
+RAYS_DECL_ENTRIES(0, 2, 0)
+RAYS_DECL_ENTRIES(0, 2, 1)
+RAYS_DECL_ENTRIES(1, 0, 0)
+RAYS_DECL_ENTRIES(1, 0, 1)
+RAYS_DECL_ENTRIES(1, 1, 0)
+RAYS_DECL_ENTRIES(1, 1, 1)
+RAYS_DECL_ENTRIES(1, 2, 0)
+RAYS_DECL_ENTRIES(1, 2, 1)
 #define RAYS_DECL_TOL(e) \
   const KernelEntry* rays_entries_tol_0_##e##_0_0_0(int* n); \
   const KernelEntry* rays_entries_tol_0_##e##_0_1_0(int* n);
@@ -142,7 +163,11 @@ std::atomic<int> g_numerics{initial_numerics()};
 // (no coalescence; surveyed on 32.8 M steps) and every other equilibrium may.
 // force_exact: the exact twin of a tolerance kernel, whose resume kernel takes the handed-over steps: always the
 // one-wave-per-SIMD entry (the only one that carries a resume kernel), whatever the fan size or the developer switch.
-const rays::KernelEntry* find_kernel(const rays_params_t& p, long long nray = 0, bool force_exact = false) {
+// summary: the summary-only variant of the exact kernel (always exact: the numerics setting is a permission, and the
+// tolerance kernels' hand-over reads residual(:)).  Its objects hold the same shapes as the recording ones
+// (rays_inst.hip), so a configuration is traced summary-only exactly when it is traced at all.
+const rays::KernelEntry* find_kernel(const rays_params_t& p, long long nray = 0, bool force_exact = false,
+                                     bool summary = false) {
   using namespace rays;
   typedef const KernelEntry* (*Getter)(int*);
   // [solver][equilibrium][derivative][unit exponents][multi_spec_damping]
@@ -152,16 +177,24 @@ const rays::KernelEntry* find_kernel(const rays_params_t& p, long long nray = 0,
       {{RAYS_G(0, 0, 0), RAYS_G(0, 0, 1)}, {RAYS_G(0, 1, 0), RAYS_G(0, 1, 1)}, {RAYS_G(0, 2, 0), RAYS_G(0, 2, 1)}},
       {{RAYS_G(1, 0, 0), RAYS_G(1, 0, 1)}, {RAYS_G(1, 1, 0), RAYS_G(1, 1, 1)}, {RAYS_G(1, 2, 0), RAYS_G(1, 2, 1)}}};
 #undef RAYS_G
+#define RAYS_G(s, e, d) {{rays_entries_sum_##s##_##e##_##d##_0_0, rays_entries_sum_##s##_##e##_##d##_0_1}, \
+                         {rays_entries_sum_##s##_##e##_##d##_1_0, rays_entries_sum_##s##_##e##_##d##_1_1}}
+  static const Getter sum_getters[2][3][2][2][2] = {
+      {{RAYS_G(0, 0, 0), RAYS_G(0, 0, 1)}, {RAYS_G(0, 1, 0), RAYS_G(0, 1, 1)}, {RAYS_G(0, 2, 0), RAYS_G(0, 2, 1)}},
+      {{RAYS_G(1, 0, 0), RAYS_G(1, 0, 1)}, {RAYS_G(1, 1, 0), RAYS_G(1, 1, 1)}, {RAYS_G(1, 2, 0), RAYS_G(1, 2, 1)}}};
+#undef RAYS_G
   // tolerance flavour of the cold RK4 groups [equilibrium][unit exponents]
   static const Getter tol_getters[3][2] = {{rays_entries_tol_0_0_0_0_0, rays_entries_tol_0_0_0_1_0},
                                            {rays_entries_tol_0_1_0_0_0, rays_entries_tol_0_1_0_1_0},
                                            {rays_entries_tol_0_2_0_0_0, rays_entries_tol_0_2_0_1_0}};
   int n = 0;
-  const bool tol = !force_exact && g_numerics.load() == RAYS_NUMERICS_TOLERANCE && p.ode_solver == RAYS_ODE_RK4 &&
+  const bool tol = !force_exact && !summary && g_numerics.load() == RAYS_NUMERICS_TOLERANCE && p.ode_solver == RAYS_ODE_RK4 &&
                    p.ray_deriv == RAYS_DERIV_COLD && !p.multi_spec_damping;
-  const KernelEntry* e = tol ? tol_getters[p.equilib_model][unit_exponents(p) ? 1 : 0](&n)
-                             : getters[p.ode_solver][p.equilib_model][p.ray_deriv][unit_exponents(p) ? 1 : 0]
-                                      [p.multi_spec_damping ? 1 : 0](&n);
+  const Getter getter = tol ? tol_getters[p.equilib_model][unit_exponents(p) ? 1 : 0]
+                            : (summary ? sum_getters : getters)[p.ode_solver][p.equilib_model][p.ray_deriv]
+                                  [unit_exponents(p) ? 1 : 0][p.multi_spec_damping ? 1 : 0];
+  if (!getter) return nullptr;  // (a summary group this library was linked without)
+  const KernelEntry* e = getter(&n);
   int ncu = 256;
   {
     int dev = 0;
@@ -557,6 +590,12 @@ const char* rays_hip_kernel_name_for(const rays_params_t* p, int nray) {
   return find_kernel(*p, nray)->name;
 }
 
+const char* rays_hip_summary_kernel_name_for(const rays_params_t* p, int nray) {
+  if (!p || rays_hip_check_params(p)) return "";
+  const rays::KernelEntry* k = find_kernel(*p, nray, false, true);
+  return k ? k->name : "";
+}
+
 // Common launcher of the trace kernels: `extra` carries the optional per-ray starting conditions and the
 // per-run steps of a fused scan (rays_trace.hpp: TraceArgs).
 namespace {
@@ -593,13 +632,16 @@ struct TraceExtras {
   const double* s0 = nullptr;
   const double* ds_run = nullptr;
   int rays_per_run = 0;
+  // summary-only launch (rays_hip_trace_summary_device): no trajectory arrays, the summary-only kernel
+  bool summary = false;
+  double* start_ray_vec = nullptr;
 };
 int launch_trace(const rays_params_t* p, int nray, const double* d_rvec0, const double* d_rindex_vec0,
                  double* d_ray_vec, double* d_residual, int32_t* d_npoints, int32_t* d_stop_code,
                  double* d_end_ray_vec, double* d_end_residuals, double* d_max_residuals, hipStream_t stream,
                  int flags, const TraceExtras& extra) {
   const size_t npt = (size_t)p->nstep_max + 1;
-  if (!(flags & RAYS_TRACE_NO_ZERO_FILL)) {  // ray_results_m.f90:154-164
+  if (!extra.summary && !(flags & RAYS_TRACE_NO_ZERO_FILL)) {  // ray_results_m.f90:154-164
     HIP_TRY(hipMemsetAsync(d_ray_vec, 0, sizeof(double) * npt * (size_t)p->nv * (size_t)nray, stream));
     HIP_TRY(hipMemsetAsync(d_residual, 0, sizeof(double) * npt * (size_t)nray, stream));
   }
@@ -628,7 +670,9 @@ int launch_trace(const rays_params_t* p, int nray, const double* d_rvec0, const 
   A.sg_far_lanes = 0;
   A.sched = nullptr;
   A.sched_stride = 0;
-  const rays::KernelEntry* kernel = find_kernel(*p, nray);
+  A.set_start_ray_vec(extra.start_ray_vec);
+  const rays::KernelEntry* kernel = find_kernel(*p, nray, false, extra.summary);
+  if (!kernel) return fail("rays_hip: the summary-only kernel of this configuration is not in this build");
   const int stride = kernel->solver == RAYS_ODE_RK4 ? sched_stride() : 0;
   if (stride > 1) {
     // more rays than one wave per SIMD holds (the kernel decides with the lanes it is launched with)
@@ -736,6 +780,47 @@ int rays_hip_scan_device(const rays_params_t* p, int n_runs, const double* d_ds_
   x.rays_per_run = nray;
   return launch_trace(p, n_runs * nray, d_rvec0, d_rindex_vec0, d_ray_vec, d_residual, d_npoints, d_stop_code,
                       d_end_ray_vec, d_end_residuals, d_max_residuals, (hipStream_t)hip_stream, flags, x);
+}
+
+// ---- summary-only tracing: ray ends and residual statistics, no trajectories (include/rays_hip.h) --------------------
+int rays_hip_trace_summary_device(const rays_params_t* p, int nray, const double* d_rvec0, const double* d_rindex_vec0,
+                                  int32_t* d_npoints, int32_t* d_stop_code, double* d_start_ray_vec,
+                                  double* d_end_ray_vec, double* d_end_residuals, double* d_max_residuals,
+                                  void* hip_stream) {
+  int rc = rays_hip_check_params(p);
+  if (rc) return rc;
+  if (nray < 0) return fail("rays_hip_trace_summary_device: nray < 0");
+  if (nray == 0) return 0;
+  if (!d_rvec0 || !d_rindex_vec0 || !d_npoints || !d_stop_code || !d_end_ray_vec || !d_end_residuals || !d_max_residuals)
+    return fail("rays_hip_trace_summary_device: null device pointer");
+  TraceExtras x;
+  x.summary = true;
+  x.start_ray_vec = d_start_ray_vec;
+  return launch_trace(p, nray, d_rvec0, d_rindex_vec0, nullptr, nullptr, d_npoints, d_stop_code, d_end_ray_vec,
+                      d_end_residuals, d_max_residuals, (hipStream_t)hip_stream, RAYS_TRACE_NO_ZERO_FILL, x);
+}
+
+int rays_hip_scan_summary_device(const rays_params_t* p, int n_runs, const double* d_ds_values, int nray,
+                                 const double* d_rvec0, const double* d_rindex_vec0, int32_t* d_npoints,
+                                 int32_t* d_stop_code, double* d_start_ray_vec, double* d_end_ray_vec,
+                                 double* d_end_residuals, double* d_max_residuals, void* hip_stream) {
+  int rc = rays_hip_check_params(p);
+  if (rc) return rc;
+  if (n_runs < 0 || nray < 0) return fail("rays_hip_scan_summary_device: n_runs, nray < 0");
+  if (n_runs == 0 || nray == 0) return 0;
+  if ((long long)n_runs * nray > 0x7fffffffll)
+    return fail("rays_hip_scan_summary_device: n_runs * nray exceeds 2^31 - 1");
+  if (!d_ds_values || !d_rvec0 || !d_rindex_vec0 || !d_npoints || !d_stop_code || !d_end_ray_vec || !d_end_residuals ||
+      !d_max_residuals)
+    return fail("rays_hip_scan_summary_device: null device pointer");
+  TraceExtras x;
+  x.ds_run = d_ds_values;
+  x.rays_per_run = nray;
+  x.summary = true;
+  x.start_ray_vec = d_start_ray_vec;
+  return launch_trace(p, n_runs * nray, d_rvec0, d_rindex_vec0, nullptr, nullptr, d_npoints, d_stop_code,
+                      d_end_ray_vec, d_end_residuals, d_max_residuals, (hipStream_t)hip_stream,
+                      RAYS_TRACE_NO_ZERO_FILL, x);
 }
 
 // Batched `call ode_solver(eqn_ray, nv, v, s, sout, ray_stop)` (ode_m.f90:218-254) + the check_save that
@@ -1093,6 +1178,92 @@ int rays_hip_trace(const rays_params_t* p, int nray, const double* rvec0, const 
       g_kept.nstep_max = p->nstep_max;
     }
   }
+  if (elapsed_s)
+    *elapsed_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  return 0;
+}
+
+// One device's share of rays_hip_trace_summary: rays [r0, r1); only the summaries exist on the device and cross PCIe.
+static int summary_block_on_device(int slot, int dev, const rays_params_t* p, int r0, int r1, const double* rvec0,
+                                   const double* rindex_vec0, int32_t* npoints, int32_t* stop_code,
+                                   double* start_ray_vec, double* end_ray_vec, double* end_residuals,
+                                   double* max_residuals) {
+  const int n = r1 - r0;
+  if (n <= 0) return 0;
+  const size_t nv = (size_t)p->nv, N = (size_t)n;
+  HIP_TRY(hipSetDevice(dev));
+  claim_slot_for_device(slot, dev);
+  SlotStream stream;
+  HIP_TRY_AS("hipStreamCreate", stream.open(slot));
+  const hipStream_t st = stream.get();
+  DeviceBuffers bufs(slot);
+  double *d_r = nullptr, *d_n = nullptr, *d_sv = nullptr, *d_ev = nullptr, *d_er = nullptr, *d_mr = nullptr;
+  int32_t *d_np = nullptr, *d_sc = nullptr;
+  HIP_TRY_AS("hipMalloc(&d_r)", bufs.alloc(&d_r, 3 * N));
+  HIP_TRY_AS("hipMalloc(&d_n)", bufs.alloc(&d_n, 3 * N));
+  HIP_TRY_AS("hipMalloc(&d_np)", bufs.alloc(&d_np, N));
+  HIP_TRY_AS("hipMalloc(&d_sc)", bufs.alloc(&d_sc, N));
+  if (start_ray_vec) HIP_TRY_AS("hipMalloc(&d_sv)", bufs.alloc(&d_sv, nv * N));
+  HIP_TRY_AS("hipMalloc(&d_ev)", bufs.alloc(&d_ev, nv * N));
+  HIP_TRY_AS("hipMalloc(&d_er)", bufs.alloc(&d_er, N));
+  HIP_TRY_AS("hipMalloc(&d_mr)", bufs.alloc(&d_mr, N));
+  HIP_TRY(hipMemcpyAsync(d_r, rvec0 + 3 * (size_t)r0, sizeof(double) * 3 * N, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(d_n, rindex_vec0 + 3 * (size_t)r0, sizeof(double) * 3 * N, hipMemcpyHostToDevice, st));
+  int rc = rays_hip_trace_summary_device(p, n, d_r, d_n, d_np, d_sc, d_sv, d_ev, d_er, d_mr, st);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(npoints + r0, d_np, sizeof(int32_t) * N, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(stop_code + r0, d_sc, sizeof(int32_t) * N, hipMemcpyDeviceToHost, st));
+  if (start_ray_vec)
+    HIP_TRY(hipMemcpyAsync(start_ray_vec + nv * (size_t)r0, d_sv, sizeof(double) * nv * N, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(end_ray_vec + nv * (size_t)r0, d_ev, sizeof(double) * nv * N, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(end_residuals + r0, d_er, sizeof(double) * N, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(max_residuals + r0, d_mr, sizeof(double) * N, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  bufs.release();
+  return 0;
+}
+
+// The host form of summary-only tracing: sharded like rays_hip_trace (contiguous blocks, one thread per device of
+// rays_hip_init[_devices]; one slot per device -- there is no large copy for further slots to overlap).
+int rays_hip_trace_summary(const rays_params_t* p, int nray, const double* rvec0, const double* rindex_vec0,
+                           int32_t* npoints, int32_t* stop_code, double* start_ray_vec, double* end_ray_vec,
+                           double* end_residuals, double* max_residuals, double* elapsed_s) {
+  int rc = rays_hip_check_params(p);
+  if (rc) return rc;
+  if (nray < 0) return fail("rays_hip_trace_summary: nray < 0");
+  if (nray > 0 && (!rvec0 || !rindex_vec0 || !npoints || !stop_code || !end_ray_vec || !end_residuals || !max_residuals))
+    return fail("rays_hip_trace_summary: null array argument");
+  std::vector<int> devs;
+  {
+    std::lock_guard<std::mutex> lk(g_mu);
+    devs = g_devices;
+  }
+  if (devs.empty()) {
+    if (rays_hip_init(0) < 0) return 3;
+    std::lock_guard<std::mutex> lk(g_mu);
+    devs = g_devices;
+  }
+  drop_kept_result();  // the image of an earlier rays_hip_trace (if any) is not this call's result: it goes back
+  const auto t0 = std::chrono::steady_clock::now();
+  const int G = (int)devs.size();
+  const int per = (nray + G - 1) / G;
+  std::vector<int> rcs(G, 0);
+  std::vector<std::string> errs(G);
+  std::vector<std::thread> th;
+  for (int g = 0; g < G; g++) {
+    const int r0 = std::min(nray, g * per), r1 = std::min(nray, (g + 1) * per);
+    th.emplace_back([&, g, r0, r1] {
+      rcs[g] = summary_block_on_device(g, devs[g], p, r0, r1, rvec0, rindex_vec0, npoints, stop_code, start_ray_vec,
+                                       end_ray_vec, end_residuals, max_residuals);
+      if (rcs[g]) errs[g] = g_err;  // (the message is this worker thread's)
+    });
+  }
+  for (auto& t : th) t.join();
+  for (int g = 0; g < G; g++)
+    if (rcs[g]) {
+      g_err = errs[g];
+      return rcs[g];
+    }
   if (elapsed_s)
     *elapsed_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   return 0;

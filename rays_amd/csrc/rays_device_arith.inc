@@ -23,6 +23,11 @@ constexpr int kEqMultiSpec = 8;
 // Tolerance flavour of a kernel (see fdiv / fsqrt below): same source, compiled in its own translation unit
 // with -DRAYS_TOL_FLAVOUR -ffp-contract=fast; the bit only gives the kernel another name.
 constexpr int kEqTol = 16;
+// Summary-only variant of a trace kernel (rays_trace.hpp: TraceArgs::start_ray_vec): no trajectory point is recorded
+// -- TraceArgs::ray_vec and ::residual are null and never touched -- and the RK4 kernels hold no point window.  The
+// ray's arithmetic, its step counting and its per-ray summaries are those of the recording kernel.  Own translation
+// units (Makefile: sum_*.o), exact arithmetic only.
+constexpr int kEqNoTraj = 32;
 // Layout of the ODE vector (ode_m.f90:160-173, initialize_ode_vector.f90:25-54):
 //   v(1:6) = (r, k), v(7) = s, [v(8) = total absorbed power, [v(9:9+nspec) per species]], [5 gradient rows]
 template <bool MULTI, int NS, int NV>

@@ -1,7 +1,10 @@
 // rays_inst.hip -- kernel instantiations.  Compiled once per (solver, equilibrium, derivative,
 // unit-exponent) group:
 //   -DRAYS_INST_SOLVER={0,1} -DRAYS_INST_EQ={0,1,2} -DRAYS_INST_DERIV={0,1} -DRAYS_INST_UE={0,1} -DRAYS_INST_MS={0,1}
-//   -DRAYS_INST_EQT=<EQ + 4 UE + 8 MS + 16 TOL>  (the kernels' EQ template argument as a literal, for the kernel names)
+//   -DRAYS_INST_EQT=<EQ + 4 UE + 8 MS + 16 TOL + 32 NOTRAJ>  (the kernels' EQ template argument as a literal, for the
+//   kernel names)
+//   -DRAYS_INST_NOTRAJ=1: the summary-only variant of an exact group (rays_device.hpp: kEqNoTraj; no trajectory point
+//   is recorded).  The same shape lists below apply, so whatever the library traces it also traces summary-only.
 //   -DRAYS_INST_TOL=1 -DRAYS_TOL_FLAVOUR -ffp-contract=fast: the tolerance flavour of a cold RK4 group
 //   (rays_device.hpp: kEqTol; 1e-10 relative per step instead of bit-identity)
 // `make FULL=1` (-DRAYS_INST_FULL): each group instantiates the species counts NS = 1..6 (nspec = 0..5,
@@ -27,6 +30,12 @@
 #ifndef RAYS_INST_TOL
 #define RAYS_INST_TOL 0
 #endif
+#ifndef RAYS_INST_NOTRAJ
+#define RAYS_INST_NOTRAJ 0
+#endif
+#if RAYS_INST_NOTRAJ && RAYS_INST_TOL
+#error "the summary-only variant exists in the exact arithmetic only"
+#endif
 #if RAYS_INST_TOL && !(defined(RAYS_TOL_FLAVOUR) && RAYS_INST_SOLVER == 0 && RAYS_INST_DERIV == 0 && RAYS_INST_MS == 0)
 #error "the tolerance flavour exists for the cold RK4 kernels only, compiled with -DRAYS_TOL_FLAVOUR"
 #endif
@@ -37,7 +46,7 @@
 #define RAYS_CAT(a, b, c, d, e, f) RAYS_CAT_(a, b, c, d, e, f)
 // the kernels' EQ template argument, as a literal (it appears in the kernel names rocprof prints)
 #ifndef RAYS_INST_EQT
-#error "pass -DRAYS_INST_EQT=<RAYS_INST_EQ + 4 RAYS_INST_UE + 8 RAYS_INST_MS + 16 RAYS_INST_TOL>"
+#error "pass -DRAYS_INST_EQT=<RAYS_INST_EQ + 4 RAYS_INST_UE + 8 RAYS_INST_MS + 16 RAYS_INST_TOL + 32 RAYS_INST_NOTRAJ>"
 #endif
 #define RAYS_STR_(x) #x
 #define RAYS_STR(x) RAYS_STR_(x)
@@ -47,7 +56,7 @@ namespace rays {
 namespace {
 constexpr int EQ = RAYS_INST_EQT;
 static_assert(EQ == (RAYS_INST_EQ | (RAYS_INST_UE ? kEqUnitExp : 0) | (RAYS_INST_MS ? kEqMultiSpec : 0) |
-                     (RAYS_INST_TOL ? kEqTol : 0)), "EQ encoding");
+                     (RAYS_INST_TOL ? kEqTol : 0) | (RAYS_INST_NOTRAJ ? kEqNoTraj : 0)), "EQ encoding");
 constexpr int DERIV = RAYS_INST_DERIV;
 
 template <int NS, int NV, int OCC = 1>
@@ -59,7 +68,7 @@ hipError_t launch_one(const DevParams& P, const TraceArgs& A, hipStream_t stream
 #ifdef RAYS_RK4_W2_DIRECT_STORES
     constexpr size_t lds2 = 0;
 #else
-    constexpr size_t lds2 = PointWindow<NV, true>::kLdsBytes;  // residual(:) only
+    constexpr size_t lds2 = (EQ & kEqNoTraj) ? 0 : PointWindow<NV, true>::kLdsBytes;  // residual(:) only
 #endif
     return launch_persistent(rk4_trace_kernel_w2<EQ, NS, DERIV, NV>, lds2, P, A, stream, grid_blocks);
   } else
@@ -69,7 +78,7 @@ hipError_t launch_one(const DevParams& P, const TraceArgs& A, hipStream_t stream
     constexpr size_t lds = 0;
 #else
     // rays_trace.hpp: the point window (0 unless nv = 7 | 8) + the eqdsk 1-D tables where there is room
-    constexpr size_t lds = PointWindow<NV>::kLdsBytes + eq_tab_lds_bytes<EQ, NV>() + zf_tab_lds_bytes<EQ, NS, NV>();
+    constexpr size_t lds = window_lds_bytes<EQ, NV>() + eq_tab_lds_bytes<EQ, NV>() + zf_tab_lds_bytes<EQ, NS, NV>();
 #endif
     return launch_persistent(rk4_trace_kernel<EQ, NS, DERIV, NV>, lds, P, A, stream, grid_blocks);
   }
@@ -80,7 +89,8 @@ hipError_t launch_one(const DevParams& P, const TraceArgs& A, hipStream_t stream
 #endif
 }
 
-#if RAYS_INST_SOLVER == 0 && RAYS_INST_DERIV == 0 && !RAYS_INST_TOL && !RAYS_INST_MS
+#if RAYS_INST_SOLVER == 0 && RAYS_INST_DERIV == 0 && !RAYS_INST_TOL && !RAYS_INST_MS && !RAYS_INST_NOTRAJ
+// (not in a summary-only object: the hand-over reads residual(:))
 // the continuation of rays the tolerance twin of this shape hands over (rays_rk4.hpp: rk4_resume_kernel)
 template <int NS, int NV>
 hipError_t resume_one(const DevParams& P, const TraceArgs& A, hipStream_t stream) {
@@ -192,6 +202,8 @@ extern "C" int RAYS_CAT(rays_debug_sg_profile, RAYS_INST_SOLVER, RAYS_INST_EQ, R
 
 #if RAYS_INST_TOL
 #define RAYS_ENTRIES_NAME rays_entries_tol
+#elif RAYS_INST_NOTRAJ
+#define RAYS_ENTRIES_NAME rays_entries_sum
 #else
 #define RAYS_ENTRIES_NAME rays_entries
 #endif

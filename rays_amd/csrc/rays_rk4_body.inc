@@ -84,7 +84,8 @@
 
   const Recip R6 = const_recip(6.0, 1.0 / 6.0);  // RN(1/6); div() = the correctly rounded quotient
   typedef PointWindow<NV, RAYS_RK4_USE_WINDOW == 2> Window;  // rays_trace.hpp (2: residual(:) only)
-  constexpr bool kWindow = RAYS_RK4_USE_WINDOW && Window::kAny;
+  constexpr bool kNoTraj = (EQ & kEqNoTraj) != 0;  // summary-only variant: no point is recorded, no window exists
+  constexpr bool kWindow = RAYS_RK4_USE_WINDOW && Window::kAny && !kNoTraj;
   extern __shared__ double lds[];
   Window win;
   if constexpr (kWindow) win.attach(lds, threadIdx.x);
@@ -93,7 +94,7 @@
     // damping: the Z-function spline table into LDS (behind the window and the eqdsk tables)
     const int n = 4 * P.zf_nx;
     if (P.damping_model && n > 0 && (size_t)n * sizeof(double) + 64 <= kZfTabBytes) {
-      double* tab = lds + (PointWindow<NV>::kLdsBytes + eq_tab_lds_bytes<EQ, NV>() + 64) / sizeof(double);
+      double* tab = lds + (window_lds_bytes<EQ, NV>() + eq_tab_lds_bytes<EQ, NV>() + 64) / sizeof(double);
       for (int i = threadIdx.x; i < n; i += blockDim.x) tab[i] = P.zf_fspl[i];
       __syncthreads();
       P.zf_lds = (unsigned)(unsigned long long)(trace_lds_ptr)tab;
@@ -103,7 +104,7 @@
     // eqdsk equilibrium: the 1-D spline tables (RBphi(R), n(psi), Te(psi), Ti(psi): a few KB) into LDS
     const int n = P.a_tab1d_doubles, nrz = P.a_nr + P.a_nz;
     if (n > 0 && (size_t)(n + nrz) * sizeof(double) <= kEqTabBytes) {
-      double* tab = lds + (PointWindow<NV>::kLdsBytes + kEqTabPad) / sizeof(double);
+      double* tab = lds + (window_lds_bytes<EQ, NV>() + kEqTabPad) / sizeof(double);
       for (int i = threadIdx.x; i < n; i += blockDim.x) tab[i] = P.a_rb_grid[i];
       for (int i = threadIdx.x; i < P.a_nr; i += blockDim.x) tab[n + i] = P.a_r_grid[i];
       for (int i = threadIdx.x; i < P.a_nz; i += blockDim.x) tab[n + P.a_nr + i] = P.a_z_grid[i];
@@ -299,7 +300,13 @@
         // stage 3: w is the new state; check_save decides whether the step is recorded
         if (first) {
           // ray_tracing.f90:92-112: point 1 = initial state, residual(1) = 0
-          if constexpr (kWindow) {
+          if constexpr (kNoTraj) {  // ... of which the summaries keep the state: start_ray_vec (ray_tracing.f90:259)
+            const TraceArgs& A = cold_args(A_hot);
+            double* const start = A.start_ray_vec();
+            if (start)
+#pragma unroll
+              for (int i = 0; i < NV; i++) start[(long long)ray * NV + i] = v[i];
+          } else if constexpr (kWindow) {
             int pv, pr;
             Window::phases(A_hot, ray, npt, pv, pr);
             win.put(A_hot, (long long)ray * npt, 0, pv, pr, v, 0.);
@@ -332,7 +339,9 @@
             done = 1;
           } else {  // :237-243
             nstep = nstep + 1;
-            if constexpr (kWindow) {
+            if constexpr (kNoTraj) {
+              // the point is counted, not stored
+            } else if constexpr (kWindow) {
               int pv, pr;
               Window::phases(A_hot, ray, npt, pv, pr);
               win.put(A_hot, (long long)ray * npt, nstep, pv, pr, v, resid);

@@ -595,7 +595,15 @@ sg_trace_kernel(const DevParams P_kernarg, const TraceArgs A_hot) {
       if (pc == PC_CHECK) {
         seg = SEG_DE_BEGIN;
         if (RAYS_RARE(fl & FL_FIRST)) {  // ray_tracing.f90:92-112
-          record_point<NV>(cold_args(A_hot), (long long)ray * npt, yy, 0.);
+          if constexpr ((EQ & kEqNoTraj) != 0) {  // summary-only: point 1 is kept as start_ray_vec (ray_tracing.f90:259)
+            const TraceArgs& A = cold_args(A_hot);
+            double* const start = A.start_ray_vec();
+            if (start)
+#pragma unroll
+              for (int i = 0; i < NV; i++) start[(long long)ray * NV + i] = yy[i];
+          } else {
+            record_point<NV>(cold_args(A_hot), (long long)ray * npt, yy, 0.);
+          }
           fl &= ~FL_FIRST;
           if (RAYS_RARE(cs_stop)) {
             const TraceArgs& A = cold_args(A_hot);
@@ -617,7 +625,7 @@ sg_trace_kernel(const DevParams P_kernarg, const TraceArgs A_hot) {
             seg = SEG_STOP;
           } else {
             nstep = nstep + 1;
-            record_point<NV>(cold_args(A_hot), (long long)ray * npt + nstep, yy, resid);
+            if constexpr ((EQ & kEqNoTraj) == 0) record_point<NV>(cold_args(A_hot), (long long)ray * npt + nstep, yy, resid);
             if (fabs(last_resid) > maxr) maxr = fabs(last_resid);
             prev_resid = last_resid;
             last_resid = resid;

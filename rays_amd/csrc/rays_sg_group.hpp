@@ -747,10 +747,17 @@ void sg_group_kernel(const DevParams P_kernarg, const TraceArgs A_hot)
         seg = SEG_DE_BEGIN;
         if (RAYS_RARE(fl & FL_FIRST)) {  // ray_tracing.f90:92-112
           const TraceArgs& A = cold_args(A_hot);
+          if constexpr ((EQ & kEqNoTraj) != 0) {  // summary-only: point 1 is kept as start_ray_vec (ray_tracing.f90:259)
+            double* const start = A.start_ray_vec();
 #pragma unroll
-          for (int c = 0; c < C; c++)
-            if (valid[c]) A.ray_vec[(long long)ray * npt * NV + gl + G * c] = yy[c];
-          if (gl == 0) A.residual[(long long)ray * npt] = 0.;
+            for (int c = 0; c < C; c++)
+              if (valid[c] && start) start[(long long)ray * NV + gl + G * c] = yy[c];
+          } else {
+#pragma unroll
+            for (int c = 0; c < C; c++)
+              if (valid[c]) A.ray_vec[(long long)ray * npt * NV + gl + G * c] = yy[c];
+            if (gl == 0) A.residual[(long long)ray * npt] = 0.;
+          }
           fl &= ~FL_FIRST;
           if (RAYS_RARE(cs_stop)) {
 #pragma unroll
@@ -772,12 +779,14 @@ void sg_group_kernel(const DevParams P_kernarg, const TraceArgs A_hot)
             seg = SEG_STOP;
           } else {  // :237-243
             nstep = nstep + 1;
-            const TraceArgs& A = cold_args(A_hot);
-            const long long pt = (long long)ray * npt + nstep;
+            if constexpr ((EQ & kEqNoTraj) == 0) {
+              const TraceArgs& A = cold_args(A_hot);
+              const long long pt = (long long)ray * npt + nstep;
 #pragma unroll
-            for (int c = 0; c < C; c++)
-              if (valid[c]) A.ray_vec[pt * NV + gl + G * c] = yy[c];
-            if (gl == 0) A.residual[pt] = resid;
+              for (int c = 0; c < C; c++)
+                if (valid[c]) A.ray_vec[pt * NV + gl + G * c] = yy[c];
+              if (gl == 0) A.residual[pt] = resid;
+            }
             if (fabs(last_resid) > maxr) maxr = fabs(last_resid);
             prev_resid = last_resid;
             last_resid = resid;

@@ -27,6 +27,7 @@ constexpr int kStopResumeExact = 1000;
 
 struct TraceArgs {
   int nray;
+  unsigned start_ray_vec_lo;               // start_ray_vec(), low half (see there)
   const double* __restrict__ rvec0;        // [nray][3]
   const double* __restrict__ rindex_vec0;  // [nray][3]
   double* __restrict__ ray_vec;            // [nray][nstep_max+1][nv]
@@ -44,6 +45,7 @@ struct TraceArgs {
   // with step ds_run[r]; rays_per_run = 0: one run, ds from the parameter block.
   const double* __restrict__ ds_run;       // [nrun]
   int rays_per_run;
+  unsigned start_ray_vec_hi;               // start_ray_vec(), high half
   // SG kernels: workspace for the integrator's rarely used upper storage tiers (rays_sg.hpp), [doubles per
   // lane][sg_far_lanes]; the launcher never starts more lanes than sg_far_lanes
   double* __restrict__ sg_far;
@@ -53,7 +55,20 @@ struct TraceArgs {
   // the launch; 0: rays are handed out in index order by next_ray alone.
   unsigned int* __restrict__ sched;
   int sched_stride;
+  // Summary-only kernels (kEqNoTraj; ray_vec and residual are null for them): where the recording kernels write point 1,
+  // they store the ray's starting vector here -- start_ray_vec(:, iray) = ray_vec(:, 1, iray), ray_tracing.f90:259.
+  // [nray][nv]; may be null.  The pointer travels in the two 4-byte holes the block has behind nray and rays_per_run:
+  // as a member of its own it makes the block 8 bytes longer, which moves the hidden kernel arguments behind it and with
+  // them an immediate in every existing kernel -- and those are to come out of the compiler exactly as they were.
+  __host__ __device__ double* start_ray_vec() const {
+    return reinterpret_cast<double*>(((unsigned long long)start_ray_vec_hi << 32) | (unsigned long long)start_ray_vec_lo);
+  }
+  __host__ __device__ void set_start_ray_vec(double* p) {
+    start_ray_vec_lo = (unsigned)((unsigned long long)p & 0xffffffffull);
+    start_ray_vec_hi = (unsigned)((unsigned long long)p >> 32);
+  }
 };
+static_assert(sizeof(TraceArgs) == 19 * 8, "TraceArgs: the layout the kernels' cold_args() offsets were compiled for");
 
 // ---- which ray a free lane traces next ---------------------------------------------------------------------------
 // With more rays than lanes the pass ends when the last ray does, so the rays handed out last should be the short
@@ -318,13 +333,19 @@ struct PointWindow {
   }
 };
 
+// The window's share of an RK4 kernel's LDS: none in the summary-only variant (kEqNoTraj), which records no point.
+template <int EQ, int NV>
+constexpr size_t window_lds_bytes() {
+  return (EQ & kEqNoTraj) ? 0 : PointWindow<NV>::kLdsBytes;
+}
+
 // LDS for the staged 1-D spline tables of the eqdsk equilibrium (DevParams::a_lds_tab), behind the point
 // window: kernels whose window leaves room (nv = 8: residual(:) only; nv = 12 | 13: none) get 32 KB (+ a pad that
 // keeps the block off LDS address 0, which means "not staged").
 constexpr size_t kEqTabPad = 64, kEqTabBytes = 32768;
 template <int EQ, int NV>
 constexpr size_t eq_tab_lds_bytes() {
-  return ((EQ & 3) == RAYS_EQ_AXISYM && PointWindow<NV>::kLdsBytes + kEqTabPad + kEqTabBytes <= 160 * 1024)
+  return ((EQ & 3) == RAYS_EQ_AXISYM && window_lds_bytes<EQ, NV>() + kEqTabPad + kEqTabBytes <= 160 * 1024)
              ? kEqTabPad + kEqTabBytes : 0;
 }
 // ... and for the Z-function spline table of the damping (DevParams::zf_lds; 2001 x 4 doubles = 64 KB in RAYS):
@@ -333,7 +354,7 @@ constexpr size_t kZfTabBytes = 65536 + 64;
 template <int EQ, int NS, int NV>
 constexpr size_t zf_tab_lds_bytes() {
   return (RayVec<(EQ & kEqMultiSpec) != 0, NS, NV>::DAMP &&
-          PointWindow<NV>::kLdsBytes + eq_tab_lds_bytes<EQ, NV>() + kZfTabBytes <= 160 * 1024) ? kZfTabBytes : 0;
+          window_lds_bytes<EQ, NV>() + eq_tab_lds_bytes<EQ, NV>() + kZfTabBytes <= 160 * 1024) ? kZfTabBytes : 0;
 }
 
 }  // namespace rays

@@ -34,6 +34,8 @@ EXPORTED_SYMBOLS = (
     "rays_hip_set_numerics", "rays_hip_get_numerics",
     "rays_hip_ray_diagnostics_device", "rays_hip_ray_diagnostics",
     "rays_hip_point_offsets_device", "rays_hip_ray_diagnostics_packed_device",
+    "rays_hip_trace_summary_device", "rays_hip_scan_summary_device", "rays_hip_trace_summary",
+    "rays_hip_summary_kernel_name_for",
 )
 
 _lib = None
@@ -100,6 +102,17 @@ def load():
     lib.rays_hip_trace_device.argtypes = [pp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int]
     lib.rays_hip_scan_device.restype = C.c_int
     lib.rays_hip_scan_device.argtypes = [pp, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int]
+    # (a library given through RAYS_HIP_LIB may predate the summary-only entries -- tools/summary_trace_bench.py times
+    # the parent commit's library next to this one; calling them there raises)
+    if hasattr(lib, "rays_hip_trace_summary_device"):
+        lib.rays_hip_trace_summary_device.restype = C.c_int
+        lib.rays_hip_trace_summary_device.argtypes = [pp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        lib.rays_hip_scan_summary_device.restype = C.c_int
+        lib.rays_hip_scan_summary_device.argtypes = [pp, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        lib.rays_hip_trace_summary.restype = C.c_int
+        lib.rays_hip_trace_summary.argtypes = [pp, C.c_int, dp, dp, ip, ip, dp, dp, dp, dp, dp]
+        lib.rays_hip_summary_kernel_name_for.restype = C.c_char_p
+        lib.rays_hip_summary_kernel_name_for.argtypes = [pp, C.c_int]
     lib.rays_hip_ode_step_device.restype = C.c_int
     lib.rays_hip_ode_step_device.argtypes = [pp, C.c_int, vp, vp, vp, vp, vp, vp]
     lib.rays_hip_pack_device.restype = C.c_int
@@ -220,6 +233,15 @@ def kernel_name(p: RaysParams, nray: int = 0) -> str:
     if not name:   # refused parameters or a shape the library was not built with (make FULL=1): never a silent ""
         check_params(p)
         raise RaysHipError("rays_hip_kernel_name: no kernel for this configuration")
+    return name
+
+
+def summary_kernel_name(p: RaysParams, nray: int = 0) -> str:
+    """Kernel specialisation a summary-only trace of `nray` rays would launch (always an exact kernel)."""
+    name = load().rays_hip_summary_kernel_name_for(C.byref(p), int(nray)).decode()
+    if not name:
+        check_params(p)
+        raise RaysHipError("rays_hip_summary_kernel_name_for: no summary-only kernel for this configuration")
     return name
 
 
@@ -535,6 +557,52 @@ def scan_device(p: RaysParams, n_runs: int, d_ds_values: int, nray: int, d_rvec0
         d_npoints, d_stop_code, d_end_ray_vec or None, d_end_residuals or None, d_max_residuals or None,
         stream or None, 0 if zero_fill else 1)
     _check(rc, "rays_hip_scan_device")
+
+
+def trace_summary_host(p: RaysParams, rvec0, rindex_vec0, ngpu: int = 0) -> dict:
+    """rays_hip_trace_summary: host numpy arrays in, the per-ray summaries out -- no trajectory exists anywhere.
+    ngpu as for trace_host (None: keep the init_devices() selection)."""
+    lib = load()
+    rvec0 = np.ascontiguousarray(rvec0, dtype=np.float64)
+    rindex_vec0 = np.ascontiguousarray(rindex_vec0, dtype=np.float64)
+    nray, nv = len(rvec0), p.nv
+    if ngpu is not None and lib.rays_hip_init(int(ngpu)) < 0:
+        raise RaysHipError("rays_hip_init: " + last_error())
+    ensure_tables(p)
+    out = dict(npoints=np.zeros(nray, dtype=np.int32), stop_code=np.zeros(nray, dtype=np.int32),
+               start_ray_vec=np.zeros((nray, nv)), end_ray_vec=np.zeros((nray, nv)), end_residuals=np.zeros(nray),
+               max_residuals=np.zeros(nray))
+    el = C.c_double(0.0)
+    rc = lib.rays_hip_trace_summary(C.byref(p), nray, _dp(rvec0), _dp(rindex_vec0), _ip(out["npoints"]),
+                                    _ip(out["stop_code"]), _dp(out["start_ray_vec"]), _dp(out["end_ray_vec"]),
+                                    _dp(out["end_residuals"]), _dp(out["max_residuals"]), C.byref(el))
+    _check(rc, "rays_hip_trace_summary")
+    out["elapsed_s"] = el.value
+    return out
+
+
+def trace_summary_device(p: RaysParams, nray: int, d_rvec0: int, d_rindex_vec0: int, d_npoints: int, d_stop_code: int,
+                         d_start_ray_vec: int, d_end_ray_vec: int, d_end_residuals: int, d_max_residuals: int,
+                         stream: int = 0):
+    """rays_hip_trace_summary_device: raw device pointers (ints; d_start_ray_vec may be 0), asynchronous on `stream`."""
+    ensure_tables(p)
+    rc = load().rays_hip_trace_summary_device(
+        C.byref(p), int(nray), d_rvec0 or None, d_rindex_vec0 or None, d_npoints or None, d_stop_code or None,
+        d_start_ray_vec or None, d_end_ray_vec or None, d_end_residuals or None, d_max_residuals or None,
+        stream or None)
+    _check(rc, "rays_hip_trace_summary_device")
+
+
+def scan_summary_device(p: RaysParams, n_runs: int, d_ds_values: int, nray: int, d_rvec0: int, d_rindex_vec0: int,
+                        d_npoints: int, d_stop_code: int, d_start_ray_vec: int, d_end_ray_vec: int,
+                        d_end_residuals: int, d_max_residuals: int, stream: int = 0):
+    """rays_hip_scan_summary_device: all runs of a `ds` scan in ONE summary-only launch (leading run dimension)."""
+    ensure_tables(p)
+    rc = load().rays_hip_scan_summary_device(
+        C.byref(p), int(n_runs), d_ds_values or None, int(nray), d_rvec0 or None, d_rindex_vec0 or None,
+        d_npoints or None, d_stop_code or None, d_start_ray_vec or None, d_end_ray_vec or None,
+        d_end_residuals or None, d_max_residuals or None, stream or None)
+    _check(rc, "rays_hip_scan_summary_device")
 
 
 def ode_step(p: RaysParams, v0, s0=None):

@@ -15,7 +15,7 @@ import numpy as np
 
 from .params import ConfigError, RaysParams, copy_params
 
-from .trace import DeviceTrace, RayResults
+from .trace import DeviceTrace, RayResults, RaySummaries
 
 
 def scan_values(scan_algorithm: str, n_runs: int, p_start: float = 0.0, p_incr: float = 0.0, p_max: float = 0.0,
@@ -36,10 +36,12 @@ def scan_values(scan_algorithm: str, n_runs: int, p_start: float = 0.0, p_incr: 
 
 
 class RayScan:
-    """All runs of a `ds` scan in one launch; outputs carry a leading run dimension."""
+    """All runs of a `ds` scan in one launch; outputs carry a leading run dimension.
+    trajectories=False: summary-only (rays_hip_scan_summary_device) -- what scanner_m's aggregate_run_data keeps of a
+    run, no trajectory tensor; results() returns one RaySummaries per run."""
 
     def __init__(self, params: RaysParams, rvec0, rindex_vec0, ds_values: Sequence[float],
-                 scan_parameter: str = "ds", device=None):
+                 scan_parameter: str = "ds", device=None, trajectories: bool = True):
         import torch
 
         from . import hip
@@ -55,12 +57,17 @@ class RayScan:
         nv, npt = params.nv, params.nstep_max + 1
         f64, i32 = torch.float64, torch.int32
         R, N = self.n_runs, self.nray
+        self.trajectories = bool(trajectories)
+        self.ray_vec = self.residual = self.start_ray_vec = None
         with torch.cuda.device(self.device):
             self.ds = torch.as_tensor(self.ds_values).to(self.device)
             self.rvec0 = torch.as_tensor(np.ascontiguousarray(rvec0), dtype=f64).to(self.device)
             self.rindex_vec0 = torch.as_tensor(np.ascontiguousarray(rindex_vec0), dtype=f64).to(self.device)
-            self.ray_vec = torch.zeros((R, N, npt, nv), dtype=f64, device=self.device)
-            self.residual = torch.zeros((R, N, npt), dtype=f64, device=self.device)
+            if self.trajectories:
+                self.ray_vec = torch.zeros((R, N, npt, nv), dtype=f64, device=self.device)
+                self.residual = torch.zeros((R, N, npt), dtype=f64, device=self.device)
+            else:
+                self.start_ray_vec = torch.zeros((R, N, nv), dtype=f64, device=self.device)
             self.npoints = torch.zeros((R, N), dtype=i32, device=self.device)
             self.stop_code = torch.zeros((R, N), dtype=i32, device=self.device)
             self.end_ray_vec = torch.zeros((R, N, nv), dtype=f64, device=self.device)
@@ -69,6 +76,12 @@ class RayScan:
 
     def launch(self, zero_fill: bool = True):
         stream = self.torch.cuda.current_stream(self.device).cuda_stream
+        if not self.trajectories:
+            self.hip.scan_summary_device(self.params, self.n_runs, self.ds.data_ptr(), self.nray, self.rvec0.data_ptr(),
+                                         self.rindex_vec0.data_ptr(), self.npoints.data_ptr(), self.stop_code.data_ptr(),
+                                         self.start_ray_vec.data_ptr(), self.end_ray_vec.data_ptr(),
+                                         self.end_residuals.data_ptr(), self.max_residuals.data_ptr(), stream=stream)
+            return
         self.hip.scan_device(self.params, self.n_runs, self.ds.data_ptr(), self.nray, self.rvec0.data_ptr(),
                              self.rindex_vec0.data_ptr(), self.ray_vec.data_ptr(), self.residual.data_ptr(),
                              self.npoints.data_ptr(), self.stop_code.data_ptr(), self.end_ray_vec.data_ptr(),
@@ -78,9 +91,13 @@ class RayScan:
     def synchronize(self):
         self.torch.cuda.synchronize(self.device)
 
-    def results(self) -> List[RayResults]:
+    def results(self):
         self.synchronize()
         c = lambda x: x.cpu().numpy()
+        if not self.trajectories:
+            arrays = [c(a) for a in (self.npoints, self.stop_code, self.start_ray_vec, self.end_ray_vec,
+                                     self.end_residuals, self.max_residuals)]
+            return [RaySummaries(*(a[r] for a in arrays)) for r in range(self.n_runs)]
         arrays = [c(a) for a in (self.ray_vec, self.residual, self.npoints, self.stop_code, self.end_ray_vec,
                                  self.end_residuals, self.max_residuals)]
         return [RayResults(*(a[r] for a in arrays)) for r in range(self.n_runs)]

@@ -95,6 +95,33 @@ class RayResults:
         return res
 
 
+@dataclasses.dataclass
+class RaySummaries:
+    """What a summary-only trace keeps of every ray (rays_hip_trace_summary*): the per-ray rows of ray_results_m
+    without ray_vec(:,:,:) and residual(:,:) -- the six things the reference's ray_scan aggregates per run
+    (scanner_m.f90:213-227).  Always from the exact kernels (include/rays_hip.h)."""
+
+    npoints: np.ndarray          # [nray]
+    stop_code: np.ndarray        # [nray]   integer image of ray_stop_flag
+    start_ray_vec: np.ndarray    # [nray][nv]   ray_vec(:, 1, iray)
+    end_ray_vec: np.ndarray      # [nray][nv]
+    end_residuals: np.ndarray    # [nray]
+    max_residuals: np.ndarray    # [nray]
+    elapsed_s: float = 0.0
+
+    @property
+    def ray_stop_flag(self):
+        return [hip.stop_flag_text(int(c)) for c in self.stop_code]
+
+    @property
+    def end_ray_parameter(self):  # ray_tracing.f90:257
+        return self.end_ray_vec[:, 6]
+
+    @property
+    def total_steps(self) -> int:
+        return int(np.maximum(self.npoints.astype(np.int64) - 1, 0).sum())
+
+
 def load_axisym_tables(namelist_path: str, nml: Dict[str, Dict[str, Any]]) -> Optional[Dict[str, Any]]:
     """Host-built spline tables of an eqdsk equilibrium: `<eqdsk_file_name>.tables.npz` next to the
     namelist (None for the analytic equilibria)."""
@@ -156,7 +183,10 @@ class RaysRun:
     def nray(self) -> int:
         return len(self.rvec0)
 
-    def trace_rays(self, ngpu: int = 1) -> RayResults:
+    def trace_rays(self, ngpu: int = 1, trajectories: bool = True):
+        """trajectories=False: the summary-only trace (RaySummaries; no trajectory array on the device or the host)."""
+        if not trajectories:
+            return RaySummaries(**hip.trace_summary_host(self.params, self.rvec0, self.rindex_vec0, ngpu=ngpu))
         out = hip.trace_host(self.params, self.rvec0, self.rindex_vec0, ngpu=ngpu)
         return RayResults(**out)
 
@@ -179,9 +209,11 @@ class RaysRun:
 
 class DeviceTrace:
     """Device-resident trace: inputs/outputs are torch CUDA tensors, launches are asynchronous on
-    the current torch stream (used by bench.py and by multi-GPU runs)."""
+    the current torch stream (used by bench.py and by multi-GPU runs).
+    trajectories=False: summary-only (rays_hip_trace_summary_device) -- ray_vec and residual are None, no trajectory
+    tensor is allocated, start_ray_vec exists instead, results() returns a RaySummaries."""
 
-    def __init__(self, params: RaysParams, rvec0, rindex_vec0, device=None):
+    def __init__(self, params: RaysParams, rvec0, rindex_vec0, device=None, trajectories: bool = True):
         import torch
 
         self.torch = torch
@@ -189,14 +221,19 @@ class DeviceTrace:
         hip.check_params(params)
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
         self.nray = len(rvec0)
+        self.trajectories = bool(trajectories)
         nv, npt = params.nv, params.nstep_max + 1
         f64, i32 = torch.float64, torch.int32
+        self.ray_vec = self.residual = self.start_ray_vec = None
         with torch.cuda.device(self.device):
             self.rvec0 = torch.as_tensor(np.ascontiguousarray(rvec0), dtype=f64).to(self.device)
             self.rindex_vec0 = torch.as_tensor(np.ascontiguousarray(rindex_vec0), dtype=f64).to(self.device)
-            # zero-filled once, like initialize_ray_results_m (ray_results_m.f90:154-164)
-            self.ray_vec = torch.zeros((self.nray, npt, nv), dtype=f64, device=self.device)
-            self.residual = torch.zeros((self.nray, npt), dtype=f64, device=self.device)
+            if self.trajectories:
+                # zero-filled once, like initialize_ray_results_m (ray_results_m.f90:154-164)
+                self.ray_vec = torch.zeros((self.nray, npt, nv), dtype=f64, device=self.device)
+                self.residual = torch.zeros((self.nray, npt), dtype=f64, device=self.device)
+            else:
+                self.start_ray_vec = torch.zeros((self.nray, nv), dtype=f64, device=self.device)
             self.npoints = torch.zeros(self.nray, dtype=i32, device=self.device)
             self.stop_code = torch.zeros(self.nray, dtype=i32, device=self.device)
             self.end_ray_vec = torch.zeros((self.nray, nv), dtype=f64, device=self.device)
@@ -206,6 +243,12 @@ class DeviceTrace:
     def launch(self, zero_fill: bool = True):
         t = self.torch
         stream = t.cuda.current_stream(self.device).cuda_stream
+        if not self.trajectories:
+            hip.trace_summary_device(self.params, self.nray, self.rvec0.data_ptr(), self.rindex_vec0.data_ptr(),
+                                     self.npoints.data_ptr(), self.stop_code.data_ptr(), self.start_ray_vec.data_ptr(),
+                                     self.end_ray_vec.data_ptr(), self.end_residuals.data_ptr(),
+                                     self.max_residuals.data_ptr(), stream=stream)
+            return
         hip.trace_device(self.params, self.nray, self.rvec0.data_ptr(), self.rindex_vec0.data_ptr(),
                          self.ray_vec.data_ptr(), self.residual.data_ptr(), self.npoints.data_ptr(),
                          self.stop_code.data_ptr(), self.end_ray_vec.data_ptr(),
@@ -222,6 +265,9 @@ class DeviceTrace:
         allocate k * total doubles instead of k * nray * (nstep_max + 1) it reads offsets[nray] once before
         allocating: ONE 8-BYTE SYNCHRONISING COPY behind launch(); the diagnostics kernel itself is asynchronous."""
         t = self.torch
+        if not self.trajectories:
+            raise RuntimeError("DeviceTrace.diagnostics: this trace is summary-only (trajectories=False) -- the per-point "
+                               "diagnostics need the recorded points; trace with trajectories=True")
         _, names = hip.diag_field_mask(fields)
         if packed:
             with t.cuda.device(self.device):
@@ -251,8 +297,11 @@ class DeviceTrace:
         res["first_bad_point"] = bad
         return res
 
-    def results(self) -> RayResults:
+    def results(self):
         self.torch.cuda.synchronize(self.device)
         c = lambda x: x.cpu().numpy()
+        if not self.trajectories:
+            return RaySummaries(c(self.npoints), c(self.stop_code), c(self.start_ray_vec), c(self.end_ray_vec),
+                                c(self.end_residuals), c(self.max_residuals))
         return RayResults(c(self.ray_vec), c(self.residual), c(self.npoints), c(self.stop_code),
                           c(self.end_ray_vec), c(self.end_residuals), c(self.max_residuals))
