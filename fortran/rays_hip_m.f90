@@ -282,6 +282,39 @@
           real(c_double), intent(out) :: elapsed_s
        end function rays_hip_trace_summary
 
+       ! Fused trace and deposition (include/rays_hip.h): the summary-only trace that also bins every accepted point, so
+       ! the absorbed-power profile exists without ray_vec(:,:,:).  Device pointers, asynchronous on hip_stream; d_work is
+       ! work(nray, n_bins) in Fortran order (bin-major), zeroed by the call; the profile continues d_profile_in
+       ! (c_null_ptr: from zero).  which: RAYS_DEP_PTOTAL_PSI = 0 | _RHO = 1 | _X = 2.
+       integer(c_int) function rays_hip_trace_deposition_device(p, nray, d_rvec0, d_rindex_vec0, d_initial_ray_power, &
+                    & which, n_bins, d_npoints, d_stop_code, d_start_ray_vec, d_end_ray_vec, d_end_residuals, &
+                    & d_max_residuals, d_work, d_profile_in, d_profile_out, hip_stream) &
+                    & bind(C, name='rays_hip_trace_deposition_device')
+          import :: c_int, c_ptr, rays_params_t
+          type(rays_params_t), intent(in) :: p
+          integer(c_int), value :: nray, which, n_bins
+          type(c_ptr), value :: d_rvec0, d_rindex_vec0, d_initial_ray_power, d_npoints, d_stop_code, d_start_ray_vec
+          type(c_ptr), value :: d_end_ray_vec, d_end_residuals, d_max_residuals, d_work, d_profile_in, d_profile_out
+          type(c_ptr), value :: hip_stream
+       end function rays_hip_trace_deposition_device
+
+       ! Blocking, host arrays: what `call trace_rays` followed by calculate_deposition_profiles gives for ONE profile --
+       ! the per-ray summaries, work(n_bins, nray) (the reference's layout) and profile(n_bins) -- without the
+       ! trajectories.  work is a type(c_ptr) so that c_null_ptr can stand for "not wanted" (else c_loc(work)).
+       integer(c_int) function rays_hip_trace_deposition(p, nray, rvec0, rindex_vec0, initial_ray_power, which, n_bins, &
+                    & npoints, stop_code, start_ray_vec, end_ray_vec, end_residuals, max_residuals, work, profile, &
+                    & elapsed_s) bind(C, name='rays_hip_trace_deposition')
+          import :: c_int, c_int32_t, c_double, c_ptr, rays_params_t
+          type(rays_params_t), intent(in) :: p
+          integer(c_int), value :: nray, which, n_bins
+          real(c_double), intent(in) :: rvec0(3,*), rindex_vec0(3,*), initial_ray_power(*)
+          integer(c_int32_t), intent(inout) :: npoints(*), stop_code(*)
+          real(c_double), intent(inout) :: start_ray_vec(*), end_ray_vec(*), end_residuals(*), max_residuals(*)
+          type(c_ptr), value :: work
+          real(c_double), intent(inout) :: profile(*)
+          real(c_double), intent(out) :: elapsed_s
+       end function rays_hip_trace_deposition
+
        ! ASYNCHRONOUS on hip_stream (blocking before round 3): synchronise the stream before d_v1 / d_resid /
        ! d_stop_code are read on the host or from another stream; one caller thread per (device, stream).
        integer(c_int) function rays_hip_ode_step_device(p, n, d_v0, d_s0, d_v1, d_resid, d_stop_code, hip_stream) &

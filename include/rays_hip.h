@@ -347,6 +347,51 @@ int rays_hip_trace_summary(const rays_params_t* p, int nray, const double* rvec0
 /* Name of the kernel the summary entries launch for a fan of nray rays ("" when p is refused). */
 const char* rays_hip_summary_kernel_name_for(const rays_params_t* p, int nray);
 
+/* ---- fused trace and deposition: the absorbed-power profile without trajectories ---------------------------------
+ * A heating run needs one thing from a fan of damped rays: the deposition profile.  These entries trace the rays with
+ * the summary-only kernels' twins that ALSO bin every accepted point (EQ + 96 in their names: the summary-only bit 32
+ * and the deposition bit 64): the binner reads the grid value of a point (psiN, rho(psiN) or x) and ray_vec(8) *
+ * initial_ray_power at two consecutive recorded points, and both are in the lane's registers when check_save accepts a
+ * point.  The statements are the post-processor's own (one device function shared with rays_hip_deposition_device), a
+ * step check_save refuses is neither recorded nor binned, and a ray refused at its initial check has one point and no
+ * segment.  So:
+ *   npoints, stop_code, start_ray_vec, end_ray_vec, end_residuals, max_residuals
+ *                            exactly those of rays_hip_trace_summary_device, bit for bit
+ *   work[n_bins][nray], profile[n_bins]
+ *                            exactly those of rays_hip_trace_device followed by rays_hip_deposition_device, bit for bit
+ * and nothing that scales with nstep_max is allocated anywhere.
+ * Device form: asynchronous on hip_stream.  d_work (required: it is the kernels' accumulator, bin-major like
+ * rays_hip_deposition_device's) is zeroed by the call; the profile is the ray-ordered sum over d_work continued from
+ * d_profile_in (NULL = from zero), so consecutive ray blocks chain bit for bit.  d_profile_in == d_profile_out is allowed.
+ * One caller thread per (device, stream), as for rays_hip_ode_step_device (a 64-byte argument block per stream is kept
+ * and released by rays_hip_finalize).
+ * NUMERICS: always the EXACT kernels, whatever rays_hip_set_numerics says (see the summary entries).
+ * Refused by name, before anything is allocated or launched: damping_model = no_damp or nv without the absorbed-power
+ * row; equilib_model = solovev; Ptotal_psi / Ptotal_rho on a slab, Ptotal_x on axisym_toroid; Ptotal_rho without
+ * rays_hip_set_rho_table or for the two magnetics models without rho; n_bins outside 1..RAYS_DEP_MAX_BINS; a null
+ * required pointer; nray < 0; a shape that is not built (the message of rays_hip_check_params).
+ * OUT OF SCOPE here: several profiles in one pass, the fused ds scan, a tolerance variant, more than
+ * RAYS_DEP_MAX_BINS (320) bins. */
+int rays_hip_trace_deposition_device(const rays_params_t* p, int nray, const double* d_rvec0,
+                                     const double* d_rindex_vec0, const double* d_initial_ray_power, int which,
+                                     int n_bins, int32_t* d_npoints, int32_t* d_stop_code,
+                                     double* d_start_ray_vec /* may be NULL */, double* d_end_ray_vec,
+                                     double* d_end_residuals, double* d_max_residuals,
+                                     double* d_work /* [n_bins][nray] */, const double* d_profile_in /* may be NULL */,
+                                     double* d_profile_out, void* hip_stream);
+/* Host pointers, blocking.  Shards the rays like rays_hip_trace_summary (the devices of rays_hip_init[_devices],
+ * contiguous blocks, that entry's resource owners), carries the running sums from block to block in ray order as
+ * rays_hip_deposition_last does -- the profile is the single-block result bit for bit, whatever the device list -- and
+ * copies the summaries, profile[n_bins] and, if asked, work in the reference's layout work(n_bins, nray) =
+ * C [nray][n_bins] (may be NULL).  A device image kept by rays_hip_keep_last_result is dropped and none is left. */
+int rays_hip_trace_deposition(const rays_params_t* p, int nray, const double* rvec0, const double* rindex_vec0,
+                              const double* initial_ray_power, int which, int n_bins, int32_t* npoints,
+                              int32_t* stop_code, double* start_ray_vec /* may be NULL */, double* end_ray_vec,
+                              double* end_residuals, double* max_residuals, double* work /* may be NULL */,
+                              double* profile, double* elapsed_s /* may be NULL */);
+/* Name of the kernel the fused entries launch for a fan of nray rays ("" when p is refused or has no such kernel). */
+const char* rays_hip_deposition_kernel_name_for(const rays_params_t* p, int nray);
+
 /* ---- one output step from arbitrary states: the ode_m interface --------------------------------
  * Batched image of `call ode_solver(eqn_ray, nv, v, s, sout, ray_stop)` (ode_m.f90:218-254, with
  * sout = s + ds and, for SG_ODE, ray_stop%rel_err/abs_err at rel_err0/abs_err0 as after

@@ -19,6 +19,7 @@
 #include <cstring>
 #include <deque>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -70,6 +71,23 @@ RAYS_DECL_ENTRIES(1, 1, 0)
 RAYS_DECL_ENTRIES(1, 1, 1)
 RAYS_DECL_ENTRIES(1, 2, 0)
 RAYS_DECL_ENTRIES(1, 2, 1)
+#undef RAYS_DECL_ENTRIES
+// the fused deposition variants (rays_device_arith.inc: kEqDeposit) of the slab and axisym_toroid groups (Makefile:
+// DEP_OBJS).  Weak for the same reason.
+#define RAYS_DECL_ENTRIES(s, e, d) \
+  __attribute__((weak)) const KernelEntry* rays_entries_dep_##s##_##e##_##d##_0_0(int* n); \
+  __attribute__((weak)) const KernelEntry* rays_entries_dep_##s##_##e##_##d##_1_0(int* n); \
+  __attribute__((weak)) const KernelEntry* rays_entries_dep_##s##_##e##_##d##_0_1(int* n); \
+  __attribute__((weak)) const KernelEntry* rays_entries_dep_##s##_##e##_##d##_1_1(int* n);
+RAYS_DECL_ENTRIES(0, 0, 0)
+RAYS_DECL_ENTRIES(0, 0, 1)
+RAYS_DECL_ENTRIES(0, 2, 0)
+RAYS_DECL_ENTRIES(0, 2, 1)
+RAYS_DECL_ENTRIES(1, 0, 0)
+RAYS_DECL_ENTRIES(1, 0, 1)
+RAYS_DECL_ENTRIES(1, 2, 0)
+RAYS_DECL_ENTRIES(1, 2, 1)
+#undef RAYS_DECL_ENTRIES
 #define RAYS_DECL_TOL(e) \
   const KernelEntry* rays_entries_tol_0_##e##_0_0_0(int* n); \
   const KernelEntry* rays_entries_tol_0_##e##_0_1_0(int* n);
@@ -81,6 +99,11 @@ hipError_t launch_pack(bool pack, int nray, int nv, int nstep_max, const int32_t
                        double* packed_res, hipStream_t stream);
 hipError_t launch_deposition(const DevParams& P, const DepArgs& D, const double* carry, double* profile,
                              hipStream_t s);
+// (rays_deposition.hip; weak like the fused kernels' entry lists: a library linked without them refuses the fused
+// entries by name)
+__attribute__((weak)) hipError_t launch_dep_trace_args(const DepTraceArgs& T, DepTraceArgs* d_out, hipStream_t s);
+__attribute__((weak)) hipError_t launch_profile_sum(int n_bins, int nray, const double* work, const double* carry,
+                                                    double* profile, hipStream_t s);
 struct FanArgs;
 hipError_t launch_ray_init(int eq_model, int ns, const DevParams& P, const FanArgs& F, int n_cand, double* cand,
                            int* keep, int* block_count, int* offs, int* first_of_launch, double* rvec0,
@@ -166,8 +189,9 @@ std::atomic<int> g_numerics{initial_numerics()};
 // summary: the summary-only variant of the exact kernel (always exact: the numerics setting is a permission, and the
 // tolerance kernels' hand-over reads residual(:)).  Its objects hold the same shapes as the recording ones
 // (rays_inst.hip), so a configuration is traced summary-only exactly when it is traced at all.
+// deposit (with summary): the fused deposition variant of the summary-only kernel (slab and axisym_toroid groups).
 const rays::KernelEntry* find_kernel(const rays_params_t& p, long long nray = 0, bool force_exact = false,
-                                     bool summary = false) {
+                                     bool summary = false, bool deposit = false) {
   using namespace rays;
   typedef const KernelEntry* (*Getter)(int*);
   // [solver][equilibrium][derivative][unit exponents][multi_spec_damping]
@@ -183,6 +207,14 @@ const rays::KernelEntry* find_kernel(const rays_params_t& p, long long nray = 0,
       {{RAYS_G(0, 0, 0), RAYS_G(0, 0, 1)}, {RAYS_G(0, 1, 0), RAYS_G(0, 1, 1)}, {RAYS_G(0, 2, 0), RAYS_G(0, 2, 1)}},
       {{RAYS_G(1, 0, 0), RAYS_G(1, 0, 1)}, {RAYS_G(1, 1, 0), RAYS_G(1, 1, 1)}, {RAYS_G(1, 2, 0), RAYS_G(1, 2, 1)}}};
 #undef RAYS_G
+#define RAYS_G(s, e, d) {{rays_entries_dep_##s##_##e##_##d##_0_0, rays_entries_dep_##s##_##e##_##d##_0_1}, \
+                         {rays_entries_dep_##s##_##e##_##d##_1_0, rays_entries_dep_##s##_##e##_##d##_1_1}}
+#define RAYS_G0 {{nullptr, nullptr}, {nullptr, nullptr}}
+  static const Getter dep_getters[2][3][2][2][2] = {
+      {{RAYS_G(0, 0, 0), RAYS_G(0, 0, 1)}, {RAYS_G0, RAYS_G0}, {RAYS_G(0, 2, 0), RAYS_G(0, 2, 1)}},
+      {{RAYS_G(1, 0, 0), RAYS_G(1, 0, 1)}, {RAYS_G0, RAYS_G0}, {RAYS_G(1, 2, 0), RAYS_G(1, 2, 1)}}};
+#undef RAYS_G0
+#undef RAYS_G
   // tolerance flavour of the cold RK4 groups [equilibrium][unit exponents]
   static const Getter tol_getters[3][2] = {{rays_entries_tol_0_0_0_0_0, rays_entries_tol_0_0_0_1_0},
                                            {rays_entries_tol_0_1_0_0_0, rays_entries_tol_0_1_0_1_0},
@@ -191,7 +223,7 @@ const rays::KernelEntry* find_kernel(const rays_params_t& p, long long nray = 0,
   const bool tol = !force_exact && !summary && g_numerics.load() == RAYS_NUMERICS_TOLERANCE && p.ode_solver == RAYS_ODE_RK4 &&
                    p.ray_deriv == RAYS_DERIV_COLD && !p.multi_spec_damping;
   const Getter getter = tol ? tol_getters[p.equilib_model][unit_exponents(p) ? 1 : 0]
-                            : (summary ? sum_getters : getters)[p.ode_solver][p.equilib_model][p.ray_deriv]
+                            : (summary ? (deposit ? dep_getters : sum_getters) : getters)[p.ode_solver][p.equilib_model][p.ray_deriv]
                                   [unit_exponents(p) ? 1 : 0][p.multi_spec_damping ? 1 : 0];
   if (!getter) return nullptr;  // (a summary group this library was linked without)
   const KernelEntry* e = getter(&n);
@@ -341,6 +373,11 @@ StreamWorkspace g_sched_ws;  // state of the "long rays first" hand-out order of
 // scratch of rays_hip_ode_step_device (a host that calls the entry per time step would otherwise pay four hipMalloc /
 // hipFree per call)
 StreamWorkspace g_step_ws;
+// the DepTraceArgs block of a fused deposition launch (rays_deposition.hpp).  Like g_sg_ws it is keyed by (device, stream
+// handle): the 64 bytes of a stream that claim_slot_for_device has destroyed stay under the stale handle until
+// rays_hip_finalize, and a new stream that gets the same handle value takes the block over -- harmless, the block is
+// rewritten on the stream before every launch that reads it.
+StreamWorkspace g_dep_ws;
 // Neighbourhood size of that order: every second row of 64 rays is traced first (cfg 5b: 4.05 | 3.26 | 3.34 | 3.42 ms for
 // index order | 2 | 4 | 8; the model of tools/refill_model.py agrees: the more pilots, the better the later half is
 // ordered).  RAYS_HIP_RAY_ORDER=index hands the rays out in index order instead (for A/B measurements; the results
@@ -507,7 +544,7 @@ int rays_hip_finalize(void) {
         if (e) (void)hipEventDestroy(e);
       g_ws[d] = DeviceWorkspace();
     }
-  for (StreamWorkspace* w : {&g_sg_ws, &g_sched_ws, &g_step_ws}) w->release_all();
+  for (StreamWorkspace* w : {&g_sg_ws, &g_sched_ws, &g_step_ws, &g_dep_ws}) w->release_all();
   for (DeviceTable* t : std::initializer_list<DeviceTable*>{&g_zfun, &g_axi, &g_rho}) t->release_all();
   release_staging();
   release_cached_device_blocks();
@@ -635,6 +672,8 @@ struct TraceExtras {
   // summary-only launch (rays_hip_trace_summary_device): no trajectory arrays, the summary-only kernel
   bool summary = false;
   double* start_ray_vec = nullptr;
+  // fused deposition launch (with summary): the device block the kernel reads its binning arguments from
+  const rays::DepTraceArgs* dep = nullptr;
 };
 int launch_trace(const rays_params_t* p, int nray, const double* d_rvec0, const double* d_rindex_vec0,
                  double* d_ray_vec, double* d_residual, int32_t* d_npoints, int32_t* d_stop_code,
@@ -671,8 +710,11 @@ int launch_trace(const rays_params_t* p, int nray, const double* d_rvec0, const 
   A.sched = nullptr;
   A.sched_stride = 0;
   A.set_start_ray_vec(extra.start_ray_vec);
-  const rays::KernelEntry* kernel = find_kernel(*p, nray, false, extra.summary);
-  if (!kernel) return fail("rays_hip: the summary-only kernel of this configuration is not in this build");
+  if (extra.dep) A.set_dep(extra.dep);
+  const rays::KernelEntry* kernel = find_kernel(*p, nray, false, extra.summary, extra.dep != nullptr);
+  if (!kernel)
+    return fail(extra.dep ? "rays_hip: the fused deposition kernel of this configuration is not in this build"
+                          : "rays_hip: the summary-only kernel of this configuration is not in this build");
   const int stride = kernel->solver == RAYS_ODE_RK4 ? sched_stride() : 0;
   if (stride > 1) {
     // more rays than one wave per SIMD holds (the kernel decides with the lanes it is launched with)
@@ -1470,6 +1512,245 @@ int rays_hip_deposition_last(const rays_params_t* p, int which, int n_bins, int 
   if (timing)
     std::fprintf(stderr, "[rays_hip_deposition_last] %d rays in %zu device-resident block(s), no trajectory upload: %.2f ms\n",
                  nray, blocks.size(), std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+  return 0;
+}
+
+// ---- fused trace and deposition: the absorbed-power profile without trajectories (include/rays_hip.h) ---------------
+// What the entries refuse before anything is allocated or launched; `who` names the entry in the messages of its own.
+static int refuse_trace_deposition(const char* who, const rays_params_t* p, int nray, int which, int n_bins) {
+  int rc = rays_hip_check_params(p);
+  if (rc) return rc;
+  const std::string w(who);
+  if (nray < 0) return fail(w + ": nray < 0");
+  if (p->equilib_model != RAYS_EQ_AXISYM && p->equilib_model != RAYS_EQ_SLAB)  // deposition_profiles_m.f90:129-222
+    return fail("initialize_deposition_profiles: unimplemented equilib_model");
+  if (p->nv < 8 || p->damping_model == RAYS_DAMP_NONE)
+    return fail(w + ": needs a run with damping (ray_vec(8) = absorbed power fraction)");
+  if (p->equilib_model == RAYS_EQ_AXISYM && p->axisym.magnetics_model != RAYS_AXI_MAG_EQDSK_SPLINE && which == RAYS_DEP_PTOTAL_RHO)
+    return fail("axisym_toroid_rho: rho is only implemented for eqdsk_magnetics_spline_interp");  // axisym_toroid_eq_m.f90:398-430
+  if (p->equilib_model == RAYS_EQ_SLAB ? which != RAYS_DEP_PTOTAL_X
+                                       : (which != RAYS_DEP_PTOTAL_PSI && which != RAYS_DEP_PTOTAL_RHO))
+    return fail("initialize_deposition_profiles: unimplemented profile for this equilib_model");  // :162-169, 204-212
+  if (n_bins < 1 || n_bins > RAYS_DEP_MAX_BINS)
+    return fail(w + ": n_bins = " + std::to_string(n_bins) + " is outside 1.." + std::to_string(RAYS_DEP_MAX_BINS) +
+                " (RAYS_DEP_MAX_BINS)");
+  if (which == RAYS_DEP_PTOTAL_RHO) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (g_rho.n < 2) return fail("Ptotal_rho needs rays_hip_set_rho_table() first");
+  }
+  if (!find_kernel(*p, nray, false, true, true) || !rays::launch_dep_trace_args || !rays::launch_profile_sum)
+    return fail(w + ": the fused deposition kernel of this configuration is not in this build");
+  return 0;
+}
+
+// zero work, the DepTraceArgs block, the fused trace; `sum`: + the ray-ordered profile sum.  Arguments already checked.
+static int trace_deposition_launch(const rays_params_t* p, int nray, const double* d_rvec0, const double* d_rindex_vec0,
+                                   const double* d_power, int which, int n_bins, int32_t* d_npoints, int32_t* d_stop_code,
+                                   double* d_start_ray_vec, double* d_end_ray_vec, double* d_end_residuals,
+                                   double* d_max_residuals, double* d_work, const double* d_profile_in,
+                                   double* d_profile_out, hipStream_t stream, bool sum) {
+  rays::DepTraceArgs T;
+  T.which = which;
+  T.n_bins = n_bins;
+  T.grid_min = 0.0; T.grid_max = 1.0;  // deposition_profiles_m.f90:176-177
+  if (which == RAYS_DEP_PTOTAL_X) { T.grid_min = p->slab.xmin; T.grid_max = p->slab.xmax; }  // :136-137
+  T.power = d_power;
+  T.work = d_work;
+  T.rho_grid = nullptr; T.rho_fspl = nullptr; T.n_rho = 0; T.pad_ = 0;
+  if (which == RAYS_DEP_PTOTAL_RHO) {
+    const double* t = nullptr;
+    int n = 0;
+    int rc = get_rho_device(&t, &n);
+    if (rc) return rc;
+    T.rho_grid = t; T.rho_fspl = t + n; T.n_rho = n;
+  }
+  rays::DepTraceArgs* d_T = nullptr;
+  HIP_TRY_AS("hipMalloc (deposition arguments)", g_dep_ws.get(stream, sizeof(rays::DepTraceArgs), (void**)&d_T));
+  HIP_TRY(hipMemsetAsync(d_work, 0, sizeof(double) * (size_t)n_bins * (size_t)nray, stream));
+  hipError_t e = rays::launch_dep_trace_args(T, d_T, stream);
+  if (e != hipSuccess) return hip_fail(e, "deposition arguments kernel");
+  TraceExtras x;
+  x.summary = true;
+  x.start_ray_vec = d_start_ray_vec;
+  x.dep = d_T;
+  int rc = launch_trace(p, nray, d_rvec0, d_rindex_vec0, nullptr, nullptr, d_npoints, d_stop_code, d_end_ray_vec,
+                        d_end_residuals, d_max_residuals, stream, RAYS_TRACE_NO_ZERO_FILL, x);
+  if (rc || !sum) return rc;
+  e = rays::launch_profile_sum(n_bins, nray, d_work, d_profile_in, d_profile_out, stream);
+  if (e != hipSuccess) return hip_fail(e, "profile sum kernel");
+  return 0;
+}
+
+int rays_hip_trace_deposition_device(const rays_params_t* p, int nray, const double* d_rvec0, const double* d_rindex_vec0,
+                                     const double* d_initial_ray_power, int which, int n_bins, int32_t* d_npoints,
+                                     int32_t* d_stop_code, double* d_start_ray_vec, double* d_end_ray_vec,
+                                     double* d_end_residuals, double* d_max_residuals, double* d_work,
+                                     const double* d_profile_in, double* d_profile_out, void* hip_stream) {
+  if (!p) return fail("rays_hip_trace_deposition_device: null parameter block");
+  int rc = refuse_trace_deposition("rays_hip_trace_deposition_device", p, nray, which, n_bins);
+  if (rc) return rc;
+  if (!d_profile_out) return fail("rays_hip_trace_deposition_device: null device pointer");
+  const hipStream_t stream = (hipStream_t)hip_stream;
+  if (nray == 0) {  // the sum over no rays: the carried profile, or zeros
+    if (d_profile_in) {
+      if (d_profile_in != d_profile_out)
+        HIP_TRY(hipMemcpyAsync(d_profile_out, d_profile_in, sizeof(double) * (size_t)n_bins, hipMemcpyDeviceToDevice, stream));
+    } else {
+      HIP_TRY(hipMemsetAsync(d_profile_out, 0, sizeof(double) * (size_t)n_bins, stream));
+    }
+    return 0;
+  }
+  if (!d_rvec0 || !d_rindex_vec0 || !d_initial_ray_power || !d_npoints || !d_stop_code || !d_end_ray_vec ||
+      !d_end_residuals || !d_max_residuals || !d_work)
+    return fail("rays_hip_trace_deposition_device: null device pointer");
+  return trace_deposition_launch(p, nray, d_rvec0, d_rindex_vec0, d_initial_ray_power, which, n_bins, d_npoints,
+                                 d_stop_code, d_start_ray_vec, d_end_ray_vec, d_end_residuals, d_max_residuals, d_work,
+                                 d_profile_in, d_profile_out, stream, true);
+}
+
+const char* rays_hip_deposition_kernel_name_for(const rays_params_t* p, int nray) {
+  if (!p || rays_hip_check_params(p)) return "";
+  const rays::KernelEntry* k = find_kernel(*p, nray, false, true, true);
+  return k ? k->name : "";
+}
+
+namespace {
+// One device's share of rays_hip_trace_deposition: rays [r0, r1) traced and binned; the summaries go to the caller's
+// arrays, work stays on the device (owned by `bufs`) until the blocks' profiles have been chained in ray order.
+struct DepositionBlock {
+  int slot = 0, dev = 0, r0 = 0, r1 = 0;
+  DeviceBuffers bufs;
+  double *d_work = nullptr, *d_in = nullptr, *d_out = nullptr;
+  hipStream_t st = nullptr;
+  explicit DepositionBlock(int s) : slot(s), bufs(s) {}
+  // however the call ends -- another block's worker failed, a copy of the chaining phase failed -- nothing of this block
+  // is still in flight when its buffers go back to the slot's cache (bufs is destroyed after this body)
+  ~DepositionBlock() {
+    if (!st) return;
+    CurrentDevice restore;
+    if (hipSetDevice(dev) == hipSuccess) (void)hipStreamSynchronize(st);
+  }
+};
+int deposition_block_on_device(DepositionBlock& B, const rays_params_t* p, const double* rvec0, const double* rindex_vec0,
+                               const double* power, int which, int n_bins, int32_t* npoints, int32_t* stop_code,
+                               double* start_ray_vec, double* end_ray_vec, double* end_residuals, double* max_residuals) {
+  const int r0 = B.r0, n = B.r1 - B.r0;
+  if (n <= 0) return 0;
+  const size_t nv = (size_t)p->nv, N = (size_t)n;
+  HIP_TRY(hipSetDevice(B.dev));
+  claim_slot_for_device(B.slot, B.dev);
+  SlotStream stream;
+  HIP_TRY_AS("hipStreamCreate", stream.open(B.slot));
+  const hipStream_t st = stream.get();
+  B.st = st;
+  double *d_r = nullptr, *d_n = nullptr, *d_pw = nullptr, *d_sv = nullptr, *d_ev = nullptr, *d_er = nullptr, *d_mr = nullptr;
+  int32_t *d_np = nullptr, *d_sc = nullptr;
+  HIP_TRY_AS("hipMalloc(&d_r)", B.bufs.alloc(&d_r, 3 * N));
+  HIP_TRY_AS("hipMalloc(&d_n)", B.bufs.alloc(&d_n, 3 * N));
+  HIP_TRY_AS("hipMalloc(&d_pw)", B.bufs.alloc(&d_pw, N));
+  HIP_TRY_AS("hipMalloc(&d_np)", B.bufs.alloc(&d_np, N));
+  HIP_TRY_AS("hipMalloc(&d_sc)", B.bufs.alloc(&d_sc, N));
+  if (start_ray_vec) HIP_TRY_AS("hipMalloc(&d_sv)", B.bufs.alloc(&d_sv, nv * N));
+  HIP_TRY_AS("hipMalloc(&d_ev)", B.bufs.alloc(&d_ev, nv * N));
+  HIP_TRY_AS("hipMalloc(&d_er)", B.bufs.alloc(&d_er, N));
+  HIP_TRY_AS("hipMalloc(&d_mr)", B.bufs.alloc(&d_mr, N));
+  HIP_TRY_AS("hipMalloc(&d_work)", B.bufs.alloc(&B.d_work, (size_t)n_bins * N));
+  HIP_TRY_AS("hipMalloc(&d_in)", B.bufs.alloc(&B.d_in, (size_t)n_bins));
+  HIP_TRY_AS("hipMalloc(&d_out)", B.bufs.alloc(&B.d_out, (size_t)n_bins));
+  HIP_TRY(hipMemcpyAsync(d_r, rvec0 + 3 * (size_t)r0, sizeof(double) * 3 * N, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(d_n, rindex_vec0 + 3 * (size_t)r0, sizeof(double) * 3 * N, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(d_pw, power + r0, sizeof(double) * N, hipMemcpyHostToDevice, st));
+  int rc = trace_deposition_launch(p, n, d_r, d_n, d_pw, which, n_bins, d_np, d_sc, d_sv, d_ev, d_er, d_mr, B.d_work,
+                                   nullptr, nullptr, st, false);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(npoints + r0, d_np, sizeof(int32_t) * N, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(stop_code + r0, d_sc, sizeof(int32_t) * N, hipMemcpyDeviceToHost, st));
+  if (start_ray_vec)
+    HIP_TRY(hipMemcpyAsync(start_ray_vec + nv * (size_t)r0, d_sv, sizeof(double) * nv * N, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(end_ray_vec + nv * (size_t)r0, d_ev, sizeof(double) * nv * N, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(end_residuals + r0, d_er, sizeof(double) * N, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(max_residuals + r0, d_mr, sizeof(double) * N, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return 0;
+}
+}  // namespace
+
+// The host form: sharded like rays_hip_trace_summary (the devices of rays_hip_init[_devices], contiguous blocks, one
+// thread per device, that entry's resource owners); then the blocks' rows are summed in ray order, each block continuing
+// the running sums of the one before it, as rays_hip_deposition_last does.
+int rays_hip_trace_deposition(const rays_params_t* p, int nray, const double* rvec0, const double* rindex_vec0,
+                              const double* initial_ray_power, int which, int n_bins, int32_t* npoints,
+                              int32_t* stop_code, double* start_ray_vec, double* end_ray_vec, double* end_residuals,
+                              double* max_residuals, double* work, double* profile, double* elapsed_s) {
+  if (!p) return fail("rays_hip_trace_deposition: null parameter block");
+  int rc = refuse_trace_deposition("rays_hip_trace_deposition", p, nray, which, n_bins);
+  if (rc) return rc;
+  if (!profile) return fail("rays_hip_trace_deposition: null array argument");
+  if (nray > 0 && (!rvec0 || !rindex_vec0 || !initial_ray_power || !npoints || !stop_code || !end_ray_vec ||
+                   !end_residuals || !max_residuals))
+    return fail("rays_hip_trace_deposition: null array argument");
+  std::vector<int> devs;
+  {
+    std::lock_guard<std::mutex> lk(g_mu);
+    devs = g_devices;
+  }
+  if (devs.empty()) {
+    if (rays_hip_init(0) < 0) return 3;
+    std::lock_guard<std::mutex> lk(g_mu);
+    devs = g_devices;
+  }
+  drop_kept_result();  // the image of an earlier rays_hip_trace (if any) is not this call's result: it goes back
+  const auto t0 = std::chrono::steady_clock::now();
+  const int G = (int)devs.size();
+  const int per = (nray + G - 1) / G;
+  std::vector<int> rcs(G, 0);
+  std::vector<std::string> errs(G);
+  std::vector<std::unique_ptr<DepositionBlock>> blocks;
+  for (int g = 0; g < G; g++) {
+    blocks.emplace_back(new DepositionBlock(g));
+    blocks[g]->dev = devs[g];
+    blocks[g]->r0 = std::min(nray, g * per);
+    blocks[g]->r1 = std::min(nray, (g + 1) * per);
+  }
+  {
+    std::vector<std::thread> th;
+    for (int g = 0; g < G; g++)
+      th.emplace_back([&, g] {
+        rcs[g] = deposition_block_on_device(*blocks[g], p, rvec0, rindex_vec0, initial_ray_power, which, n_bins, npoints,
+                                            stop_code, start_ray_vec, end_ray_vec, end_residuals, max_residuals);
+        if (rcs[g]) errs[g] = g_err;  // (the message is this worker thread's)
+      });
+    for (auto& t : th) t.join();
+  }
+  for (int g = 0; g < G; g++)
+    if (rcs[g]) {
+      g_err = errs[g];
+      return rcs[g];
+    }
+  // the ray-ordered sums, block after block
+  std::vector<double> carry((size_t)n_bins, 0.0), wbuf;
+  bool have_carry = false;
+  {
+    CurrentDevice restore;
+    for (int g = 0; g < G; g++) {
+      DepositionBlock& B = *blocks[g];
+      const int n = B.r1 - B.r0;
+      if (n <= 0) continue;
+      HIP_TRY(hipSetDevice(B.dev));
+      if (have_carry)
+        HIP_TRY(hipMemcpyAsync(B.d_in, carry.data(), sizeof(double) * (size_t)n_bins, hipMemcpyHostToDevice, B.st));
+      const hipError_t e = rays::launch_profile_sum(n_bins, n, B.d_work, have_carry ? B.d_in : nullptr, B.d_out, B.st);
+      if (e != hipSuccess) return hip_fail(e, "profile sum kernel");
+      HIP_TRY(hipMemcpyAsync(carry.data(), B.d_out, sizeof(double) * (size_t)n_bins, hipMemcpyDeviceToHost, B.st));
+      HIP_TRY(hipStreamSynchronize(B.st));
+      have_carry = true;
+      if (work) HIP_TRY_AS("hipMemcpy (work)", work_to_host(B.d_work, n_bins, n, work + (size_t)B.r0 * n_bins, &wbuf));
+      B.bufs.release();
+    }
+  }
+  std::memcpy(profile, carry.data(), sizeof(double) * (size_t)n_bins);
+  if (elapsed_s)
+    *elapsed_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   return 0;
 }
 

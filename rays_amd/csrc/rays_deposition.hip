@@ -51,7 +51,25 @@ profile_sum_kernel(int n_bins, int nray, const double* __restrict__ work, const 
   }
   if (lane == 0) profile[b] = s;
 }
+
+// the DepTraceArgs block of a fused trace launch: a by-value kernel argument written to device memory in stream order
+// (no host memory has to outlive the asynchronous call)
+__global__ void __launch_bounds__(kDepWave) dep_trace_args_kernel(const DepTraceArgs T, DepTraceArgs* out) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) *out = T;
+}
 }  // namespace
+
+hipError_t launch_dep_trace_args(const DepTraceArgs& T, DepTraceArgs* d_out, hipStream_t s) {
+  hipLaunchKernelGGL(dep_trace_args_kernel, dim3(1), dim3(kDepWave), 0, s, T, d_out);
+  return hipGetLastError();
+}
+
+// profile(b) = carry(b) + sum over the rays of work(b, :) in ray order (see profile_sum_kernel)
+hipError_t launch_profile_sum(int n_bins, int nray, const double* work, const double* carry, double* profile,
+                              hipStream_t s) {
+  hipLaunchKernelGGL(profile_sum_kernel, dim3(n_bins), dim3(kDepWave), 0, s, n_bins, nray, work, carry, profile);
+  return hipGetLastError();
+}
 
 hipError_t launch_deposition(const DevParams& P, const DepArgs& D, const double* carry, double* profile,
                              hipStream_t s) {

@@ -54,67 +54,126 @@ RAYS_DEV double dep_grid_value(const DevParams& P, const DepArgs& D, const doubl
   return rho;
 }
 
+// (int)floor(x) of a bin coordinate, as the DEVICE converts it: v_cvt_i32_f64 saturates and turns NaN into 0.  A NaN grid
+// value -- 'Ptotal_rho' with a rho(psiN) spline the host could not build (tests/golden: the 129 x 129 eqdsk) -- thereby
+// puts the segment into bin 1, which is what the reference's binner does with it.  The C++ conversion is undefined
+// there, so the host emulation restates the device's.
+RAYS_DEV int dep_floor_index(double x) {
+#ifdef RAYS_HOST_EMUL
+  const double f = floor(x);
+  if (f != f) return 0;
+  if (f >= 2147483647.0) return 2147483647;
+  if (f <= -2147483648.0) return -2147483647 - 1;
+  return (int)f;
+#else
+  return (int)floor(x);
+#endif
+}
+
+// One segment of binner_real: the absorbed power gained between two consecutive recorded points, (x_prev, q_prev) ->
+// (xq, q), spread over the bins of row[b * stride], b = 0..n_bins-1, that the segment covers.  The body of deposit_ray's
+// point loop, and what the fused trace kernels (kEqDeposit: rays_rk4_body.inc, rays_sg.hpp) call when a point is accepted
+// -- the same statements in the same order, so a row comes out the same bits whichever of the two walks the ray.
+template <class RowPtr, class Stride>
+RAYS_DEV void deposit_segment(RowPtr row_base, Stride stride, int n_bins, double xmin, double xmax, double x_prev,
+                              double q_prev, double xq, double q) {
+  struct Row {
+    RowPtr p;
+    Stride st;
+    RAYS_DEV auto& operator[](int b) const { return p[b * st]; }
+  } row{row_base, stride};
+  const double x_bin_width = (xmax - xmin) / (double)n_bins;
+  double x_low = fmin(x_prev, xq), x_high = fmax(x_prev, xq);
+  double ix_low = (x_low - xmin) / x_bin_width, ix_high = (x_high - xmin) / x_bin_width;
+  const double delta_ix = ix_high - ix_low;
+  int index_low = dep_floor_index(ix_low) + 1, index_high = dep_floor_index(ix_high) + 1;
+  if (x_high >= xmax) index_high = n_bins;
+  int delta_i = index_high - index_low;
+  double delta_Q = q - q_prev;
+  const double Q_density = delta_Q / delta_ix;
+  bool skip = fabs(delta_Q) < 4.0 * 2.2250738585072014e-308;  // 4.0_skind*tiny(delta_Q)
+  if (x_high < xmin || x_low > xmax) skip = true;
+  if (!skip) {
+    if (x_low < xmin) {
+      delta_Q = delta_Q * (ix_high / delta_ix);
+      ix_low = 0.0;
+      index_low = 1;
+      delta_i = index_high - index_low;
+    }
+    if (x_high > xmax) {
+      delta_Q = delta_Q * (((double)n_bins - ix_low) / delta_ix);
+      ix_high = (double)n_bins;
+      index_high = n_bins;
+      delta_i = index_high - index_low;
+    }
+    if (delta_i == 0) {
+      if (index_low >= 1 && index_low <= n_bins) row[index_low - 1] = row[index_low - 1] + delta_Q;
+    } else if (delta_i > 0) {
+      const double Q_incrL = delta_Q * (((double)index_low - ix_low) / delta_ix);
+      row[index_low - 1] = row[index_low - 1] + Q_incrL;
+      const double Q_incrH = delta_Q * ((ix_high - (double)(index_high - 1)) / delta_ix);
+      // x_high just below xmax whose quotient rounds up to n_bins: index_high = n_bins + 1, one element past
+      // the row (the reference updates binned_Q(n_bins + 1) there: undefined)
+      if (index_high <= n_bins) row[index_high - 1] = row[index_high - 1] + Q_incrH;
+      for (int i = index_low + 1; i <= index_high - 1; i++) row[i - 1] = row[i - 1] + Q_density;
+    }
+  }
+}
+
 // bin_a_ray + binner_real for ray `iray` into row[b * stride], b = 0..n_bins-1 (zeroed here, as the
 // binner does)
 template <class RowPtr>
 RAYS_DEV void deposit_ray(const DevParams& P, const DepArgs& D, int iray, RowPtr row_base, int stride) {
   const int n_bins = D.n_bins;
-  struct Row {
-    RowPtr p;
-    int st;
-    RAYS_DEV auto& operator[](int b) const { return p[b * st]; }
-  } row{row_base, stride};
-  for (int b = 0; b < n_bins; b++) row[b] = 0.;
+  for (int b = 0; b < n_bins; b++) row_base[b * stride] = 0.;
   const int np = D.npoints[iray];
   const double* rv = D.ray_vec + (long long)iray * D.npt * D.nv;
   const double pw = D.power[iray];
   const double xmin = D.grid_min, xmax = D.grid_max;
-  const double x_bin_width = (xmax - xmin) / (double)n_bins;
   double x_prev = 0., q_prev = 0.;
   for (int is = 0; is < np; is++) {
     const double* v = rv + (long long)is * D.nv;
     const double xq = dep_grid_value(P, D, v);
     const double q = v[7] * pw;  // ray_vec(8)*initial_ray_power
-    if (is > 0) {
-      double x_low = fmin(x_prev, xq), x_high = fmax(x_prev, xq);
-      double ix_low = (x_low - xmin) / x_bin_width, ix_high = (x_high - xmin) / x_bin_width;
-      const double delta_ix = ix_high - ix_low;
-      int index_low = (int)floor(ix_low) + 1, index_high = (int)floor(ix_high) + 1;
-      if (x_high >= xmax) index_high = n_bins;
-      int delta_i = index_high - index_low;
-      double delta_Q = q - q_prev;
-      const double Q_density = delta_Q / delta_ix;
-      bool skip = fabs(delta_Q) < 4.0 * 2.2250738585072014e-308;  // 4.0_skind*tiny(delta_Q)
-      if (x_high < xmin || x_low > xmax) skip = true;
-      if (!skip) {
-        if (x_low < xmin) {
-          delta_Q = delta_Q * (ix_high / delta_ix);
-          ix_low = 0.0;
-          index_low = 1;
-          delta_i = index_high - index_low;
-        }
-        if (x_high > xmax) {
-          delta_Q = delta_Q * (((double)n_bins - ix_low) / delta_ix);
-          ix_high = (double)n_bins;
-          index_high = n_bins;
-          delta_i = index_high - index_low;
-        }
-        if (delta_i == 0) {
-          if (index_low >= 1 && index_low <= n_bins) row[index_low - 1] = row[index_low - 1] + delta_Q;
-        } else if (delta_i > 0) {
-          const double Q_incrL = delta_Q * (((double)index_low - ix_low) / delta_ix);
-          row[index_low - 1] = row[index_low - 1] + Q_incrL;
-          const double Q_incrH = delta_Q * ((ix_high - (double)(index_high - 1)) / delta_ix);
-          // x_high just below xmax whose quotient rounds up to n_bins: index_high = n_bins + 1, one element past
-          // the row (the reference updates binned_Q(n_bins + 1) there: undefined)
-          if (index_high <= n_bins) row[index_high - 1] = row[index_high - 1] + Q_incrH;
-          for (int i = index_low + 1; i <= index_high - 1; i++) row[i - 1] = row[i - 1] + Q_density;
-        }
-      }
-    }
+    if (is > 0) deposit_segment(row_base, stride, n_bins, xmin, xmax, x_prev, q_prev, xq, q);
     x_prev = xq;
     q_prev = q;
   }
+}
+
+// ---- binning inside the trace kernels (kEqDeposit) -----------------------------------------------------
+// What a fused trace kernel reads besides TraceArgs: a block in device memory, filled on the launch's stream right before
+// the kernel (rays_deposition.hip: launch_dep_trace_args) and found through TraceArgs::dep().  Wave-uniform: scalar loads
+// at the point of use.
+struct DepTraceArgs {
+  int which, n_bins;       // RAYS_DEP_PTOTAL_*; 1..RAYS_DEP_MAX_BINS
+  double grid_min, grid_max;
+  const double* power;     // initial_ray_power[nray]
+  double* work;            // [n_bins][nray], zeroed before the launch; ray i owns work[b * nray + i]
+  const double* rho_grid;  // rho(psiN) spline (Ptotal_rho)
+  const double* rho_fspl;
+  int n_rho, pad_;
+};
+static_assert(sizeof(DepTraceArgs) == 64, "DepTraceArgs: one 64-byte block");
+
+// the post-processor's grid value and absorbed power of the ODE vector v of ray `ray`: dep_grid_value's own bits
+RAYS_DEV void dep_trace_point(const DevParams& P, const DepTraceArgs& T, int ray, const double* v, double& xq, double& q) {
+  DepArgs D;
+  D.which = T.which;
+  D.rho_grid = T.rho_grid;
+  D.rho_fspl = T.rho_fspl;
+  D.n_rho = T.n_rho;
+  xq = dep_grid_value(P, D, v);
+  q = v[7] * T.power[ray];  // ray_vec(8)*initial_ray_power
+}
+// an accepted point of ray `ray` (of nray): the segment from the ray's previous point into the ray's row of work
+RAYS_DEV void dep_trace_segment(const DevParams& P, const DepTraceArgs& T, int ray, int nray, const double* v,
+                                double& x_prev, double& q_prev) {
+  double xq, q;
+  dep_trace_point(P, T, ray, v, xq, q);
+  deposit_segment(T.work + ray, (long long)nray, T.n_bins, T.grid_min, T.grid_max, x_prev, q_prev, xq, q);
+  x_prev = xq;
+  q_prev = q;
 }
 
 }  // namespace rays

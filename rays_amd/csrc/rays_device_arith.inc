@@ -28,6 +28,11 @@ constexpr int kEqTol = 16;
 // ray's arithmetic, its step counting and its per-ray summaries are those of the recording kernel.  Own translation
 // units (Makefile: sum_*.o), exact arithmetic only.
 constexpr int kEqNoTraj = 32;
+// Fused deposition variant of a summary-only kernel (only together with kEqNoTraj; DESIGN.md 4.9): every accepted point
+// is also binned into the ray's row of the deposition work array, with the post-processor's own statements
+// (rays_deposition.hpp: deposit_segment), so the absorbed-power profile exists without the trajectories.  Kernels with
+// the absorbed-power row only; own translation units (Makefile: dep_*.o), exact arithmetic only.
+constexpr int kEqDeposit = 64;
 // Layout of the ODE vector (ode_m.f90:160-173, initialize_ode_vector.f90:25-54):
 //   v(1:6) = (r, k), v(7) = s, [v(8) = total absorbed power, [v(9:9+nspec) per species]], [5 gradient rows]
 template <bool MULTI, int NS, int NV>

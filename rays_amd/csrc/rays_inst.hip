@@ -1,10 +1,14 @@
 // rays_inst.hip -- kernel instantiations.  Compiled once per (solver, equilibrium, derivative,
 // unit-exponent) group:
 //   -DRAYS_INST_SOLVER={0,1} -DRAYS_INST_EQ={0,1,2} -DRAYS_INST_DERIV={0,1} -DRAYS_INST_UE={0,1} -DRAYS_INST_MS={0,1}
-//   -DRAYS_INST_EQT=<EQ + 4 UE + 8 MS + 16 TOL + 32 NOTRAJ>  (the kernels' EQ template argument as a literal, for the
-//   kernel names)
+//   -DRAYS_INST_EQT=<EQ + 4 UE + 8 MS + 16 TOL + 32 NOTRAJ + 64 DEPOSIT>  (the kernels' EQ template argument as a
+//   literal, for the kernel names)
 //   -DRAYS_INST_NOTRAJ=1: the summary-only variant of an exact group (rays_device.hpp: kEqNoTraj; no trajectory point
 //   is recorded).  The same shape lists below apply, so whatever the library traces it also traces summary-only.
+//   -DRAYS_INST_NOTRAJ=1 -DRAYS_INST_DEPOSIT=1: the fused deposition variant (rays_device_arith.inc: kEqDeposit; the
+//   summary-only kernel that also bins every accepted point) of a slab or axisym_toroid group.  The same shape lists,
+//   cut down to the entries with the absorbed-power row (nv = 8 | 13; 8 + NS | 13 + NS in the MS groups) and to the
+//   one-ray-per-lane kernels: a damped configuration is traced fused exactly when it is traced at all.
 //   -DRAYS_INST_TOL=1 -DRAYS_TOL_FLAVOUR -ffp-contract=fast: the tolerance flavour of a cold RK4 group
 //   (rays_device.hpp: kEqTol; 1e-10 relative per step instead of bit-identity)
 // `make FULL=1` (-DRAYS_INST_FULL): each group instantiates the species counts NS = 1..6 (nspec = 0..5,
@@ -33,8 +37,14 @@
 #ifndef RAYS_INST_NOTRAJ
 #define RAYS_INST_NOTRAJ 0
 #endif
+#ifndef RAYS_INST_DEPOSIT
+#define RAYS_INST_DEPOSIT 0
+#endif
 #if RAYS_INST_NOTRAJ && RAYS_INST_TOL
 #error "the summary-only variant exists in the exact arithmetic only"
+#endif
+#if RAYS_INST_DEPOSIT && !(RAYS_INST_NOTRAJ && (RAYS_INST_EQ == 0 || RAYS_INST_EQ == 2))
+#error "the fused deposition variant is a summary-only kernel of the slab or axisym_toroid groups"
 #endif
 #if RAYS_INST_TOL && !(defined(RAYS_TOL_FLAVOUR) && RAYS_INST_SOLVER == 0 && RAYS_INST_DERIV == 0 && RAYS_INST_MS == 0)
 #error "the tolerance flavour exists for the cold RK4 kernels only, compiled with -DRAYS_TOL_FLAVOUR"
@@ -46,7 +56,7 @@
 #define RAYS_CAT(a, b, c, d, e, f) RAYS_CAT_(a, b, c, d, e, f)
 // the kernels' EQ template argument, as a literal (it appears in the kernel names rocprof prints)
 #ifndef RAYS_INST_EQT
-#error "pass -DRAYS_INST_EQT=<RAYS_INST_EQ + 4 RAYS_INST_UE + 8 RAYS_INST_MS + 16 RAYS_INST_TOL + 32 RAYS_INST_NOTRAJ>"
+#error "pass -DRAYS_INST_EQT=<RAYS_INST_EQ + 4 RAYS_INST_UE + 8 RAYS_INST_MS + 16 RAYS_INST_TOL + 32 RAYS_INST_NOTRAJ + 64 RAYS_INST_DEPOSIT>"
 #endif
 #define RAYS_STR_(x) #x
 #define RAYS_STR(x) RAYS_STR_(x)
@@ -56,7 +66,8 @@ namespace rays {
 namespace {
 constexpr int EQ = RAYS_INST_EQT;
 static_assert(EQ == (RAYS_INST_EQ | (RAYS_INST_UE ? kEqUnitExp : 0) | (RAYS_INST_MS ? kEqMultiSpec : 0) |
-                     (RAYS_INST_TOL ? kEqTol : 0) | (RAYS_INST_NOTRAJ ? kEqNoTraj : 0)), "EQ encoding");
+                     (RAYS_INST_TOL ? kEqTol : 0) | (RAYS_INST_NOTRAJ ? kEqNoTraj : 0) |
+                     (RAYS_INST_DEPOSIT ? kEqDeposit : 0)), "EQ encoding");
 constexpr int DERIV = RAYS_INST_DERIV;
 
 template <int NS, int NV, int OCC = 1>
@@ -126,11 +137,33 @@ hipError_t launch_group(const DevParams& P, const TraceArgs& A, hipStream_t stre
 #else
 #define RAYS_SG_FAR(NV) sg_far_doubles_per_lane<NV>()
 #endif
-#define RAYS_ENTRY(NS, NV) \
+#define RAYS_ENTRY_(NS, NV) \
   { RAYS_INST_SOLVER, EQ, NS, DERIV, NV, 1, RAYS_SG_FAR(NV), 1, RAYS_KNAME "<" RAYS_STR(RAYS_INST_EQT) ", " #NS ", " RAYS_STR(RAYS_INST_DERIV) ", " #NV ">", &launch_one<NS, NV> RAYS_RESUME(NS, NV) }
 // two-waves-per-SIMD build of an RK4 kernel (large fans; rays_rk4.hpp)
-#define RAYS_ENTRY_OCC2(NS, NV) \
+#define RAYS_ENTRY_OCC2_(NS, NV) \
   { RAYS_INST_SOLVER, EQ, NS, DERIV, NV, 2, 0, 1, "rk4_trace_kernel_w2<" RAYS_STR(RAYS_INST_EQT) ", " #NS ", " RAYS_STR(RAYS_INST_DERIV) ", " #NV ">", &launch_one<NS, NV, 2> }
+#if RAYS_INST_DEPOSIT
+// The fused deposition objects walk the same lists and keep the entries with the absorbed-power row: the others (and the
+// nv = 7 kernels of the other two families) come out as entries no configuration matches (ns = 0), not as kernels.
+template <int NS, int NV, bool DAMPED = RayVec<RAYS_INST_MS != 0, NS, NV>::DAMP>
+struct DepEntry {
+  static constexpr KernelEntry get(const char*) { return KernelEntry{RAYS_INST_SOLVER, EQ, 0, DERIV, 0, 1, 0, 1, "", nullptr, nullptr}; }
+};
+template <int NS, int NV>
+struct DepEntry<NS, NV, true> {
+  static constexpr KernelEntry get(const char* name) {
+    return KernelEntry{RAYS_INST_SOLVER, EQ, NS, DERIV, NV, 1, RAYS_SG_FAR(NV), 1, name, &launch_one<NS, NV>, nullptr};
+  }
+};
+#define RAYS_ENTRY(NS, NV) \
+  DepEntry<NS, NV>::get(RAYS_KNAME "<" RAYS_STR(RAYS_INST_EQT) ", " #NS ", " RAYS_STR(RAYS_INST_DERIV) ", " #NV ">")
+#define RAYS_ENTRY_OCC2(NS, NV) DepEntry<NS, 7>::get("")
+#undef RAYS_ENTRY_GROUP
+#define RAYS_ENTRY_GROUP(NS) DepEntry<NS, 7>::get("")
+#else
+#define RAYS_ENTRY(NS, NV) RAYS_ENTRY_(NS, NV)
+#define RAYS_ENTRY_OCC2(NS, NV) RAYS_ENTRY_OCC2_(NS, NV)
+#endif
 
 const KernelEntry kEntries[] = {
 #if RAYS_INST_MS
@@ -202,6 +235,8 @@ extern "C" int RAYS_CAT(rays_debug_sg_profile, RAYS_INST_SOLVER, RAYS_INST_EQ, R
 
 #if RAYS_INST_TOL
 #define RAYS_ENTRIES_NAME rays_entries_tol
+#elif RAYS_INST_DEPOSIT
+#define RAYS_ENTRIES_NAME rays_entries_dep
 #elif RAYS_INST_NOTRAJ
 #define RAYS_ENTRIES_NAME rays_entries_sum
 #else

@@ -86,6 +86,12 @@
   typedef PointWindow<NV, RAYS_RK4_USE_WINDOW == 2> Window;  // rays_trace.hpp (2: residual(:) only)
   constexpr bool kNoTraj = (EQ & kEqNoTraj) != 0;  // summary-only variant: no point is recorded, no window exists
   constexpr bool kWindow = RAYS_RK4_USE_WINDOW && Window::kAny && !kNoTraj;
+  // fused deposition variant (kEqDeposit; rays_deposition.hpp): an accepted point is binned into the ray's row of work.
+  // The grid value and the absorbed power of the ray's last recorded point belong to the ray: set at its point 1.
+  constexpr bool kDeposit = (EQ & kEqDeposit) != 0;
+  static_assert(!kDeposit || (kNoTraj && RayVec<(EQ & kEqMultiSpec) != 0, NS, NV>::DAMP),
+                "the fused deposition variant: a summary-only kernel with the absorbed-power row");
+  [[maybe_unused]] double dep_x_prev = 0., dep_q_prev = 0.;
   extern __shared__ double lds[];
   Window win;
   if constexpr (kWindow) win.attach(lds, threadIdx.x);
@@ -306,6 +312,7 @@
             if (start)
 #pragma unroll
               for (int i = 0; i < NV; i++) start[(long long)ray * NV + i] = v[i];
+            if constexpr (kDeposit) dep_trace_point(P, *A.dep(), ray, v, dep_x_prev, dep_q_prev);
           } else if constexpr (kWindow) {
             int pv, pr;
             Window::phases(A_hot, ray, npt, pv, pr);
@@ -340,7 +347,11 @@
           } else {  // :237-243
             nstep = nstep + 1;
             if constexpr (kNoTraj) {
-              // the point is counted, not stored
+              // the point is counted, not stored -- and binned by the fused deposition variant
+              if constexpr (kDeposit) {
+                const TraceArgs& A = cold_args(A_hot);
+                dep_trace_segment(P, *A.dep(), ray, A.nray, v, dep_x_prev, dep_q_prev);
+              }
             } else if constexpr (kWindow) {
               int pv, pr;
               Window::phases(A_hot, ray, npt, pv, pr);

@@ -478,6 +478,12 @@ sg_trace_kernel(const DevParams P_kernarg, const TraceArgs A_hot) {
   // that produces it and the `de` entry that consumes it, it IS yy; a copy for the day the ray stops is kept in
   // the workspace, sg_save_y)
   double last_resid = 0., prev_resid = 0., maxr = -1.7976931348623157e308;
+  // fused deposition variant (kEqDeposit; rays_deposition.hpp): grid value and absorbed power of the ray's last recorded
+  // point, set at its point 1
+  constexpr bool kDeposit = (EQ & kEqDeposit) != 0;
+  static_assert(!kDeposit || ((EQ & kEqNoTraj) != 0 && RayVec<(EQ & kEqMultiSpec) != 0, NS, NV>::DAMP),
+                "the fused deposition variant: a summary-only kernel with the absorbed-power row");
+  [[maybe_unused]] double dep_x_prev = 0., dep_q_prev = 0.;
 
   // ---- per-lane integrator state (de / step locals that live across RHS evaluations) ----------
   double yy[NV], pp[NV];  // (yp of `step` is always the f of the current trip: not kept)
@@ -601,6 +607,7 @@ sg_trace_kernel(const DevParams P_kernarg, const TraceArgs A_hot) {
             if (start)
 #pragma unroll
               for (int i = 0; i < NV; i++) start[(long long)ray * NV + i] = yy[i];
+            if constexpr (kDeposit) dep_trace_point(P, *A.dep(), ray, yy, dep_x_prev, dep_q_prev);
           } else {
             record_point<NV>(cold_args(A_hot), (long long)ray * npt, yy, 0.);
           }
@@ -626,6 +633,10 @@ sg_trace_kernel(const DevParams P_kernarg, const TraceArgs A_hot) {
           } else {
             nstep = nstep + 1;
             if constexpr ((EQ & kEqNoTraj) == 0) record_point<NV>(cold_args(A_hot), (long long)ray * npt + nstep, yy, resid);
+            if constexpr (kDeposit) {  // the point is binned where the recording kernels store it
+              const TraceArgs& A = cold_args(A_hot);
+              dep_trace_segment(P, *A.dep(), ray, A.nray, yy, dep_x_prev, dep_q_prev);
+            }
             if (fabs(last_resid) > maxr) maxr = fabs(last_resid);
             prev_resid = last_resid;
             last_resid = resid;

@@ -16,6 +16,7 @@
 #pragma once
 
 #include "rays_device.hpp"
+#include "rays_deposition.hpp"  // deposit_segment, DepTraceArgs: the fused deposition variant (kEqDeposit)
 
 namespace rays {
 
@@ -66,6 +67,13 @@ struct TraceArgs {
   __host__ __device__ void set_start_ray_vec(double* p) {
     start_ray_vec_lo = (unsigned)((unsigned long long)p & 0xffffffffull);
     start_ray_vec_hi = (unsigned)((unsigned long long)p >> 32);
+  }
+  // Fused deposition kernels (kEqNoTraj | kEqDeposit): no trajectory exists, and the ray_vec slot carries the device
+  // address of the launch's DepTraceArgs block (rays_deposition.hpp) instead; residual stays null.  TraceArgs is not
+  // lengthened for it.
+  __host__ __device__ const DepTraceArgs* dep() const { return reinterpret_cast<const DepTraceArgs*>(ray_vec); }
+  __host__ __device__ void set_dep(const DepTraceArgs* d) {
+    ray_vec = reinterpret_cast<double*>(const_cast<DepTraceArgs*>(d));
   }
 };
 static_assert(sizeof(TraceArgs) == 19 * 8, "TraceArgs: the layout the kernels' cold_args() offsets were compiled for");

@@ -36,6 +36,7 @@ EXPORTED_SYMBOLS = (
     "rays_hip_point_offsets_device", "rays_hip_ray_diagnostics_packed_device",
     "rays_hip_trace_summary_device", "rays_hip_scan_summary_device", "rays_hip_trace_summary",
     "rays_hip_summary_kernel_name_for",
+    "rays_hip_trace_deposition_device", "rays_hip_trace_deposition", "rays_hip_deposition_kernel_name_for",
 )
 
 _lib = None
@@ -113,6 +114,16 @@ def load():
         lib.rays_hip_trace_summary.argtypes = [pp, C.c_int, dp, dp, ip, ip, dp, dp, dp, dp, dp]
         lib.rays_hip_summary_kernel_name_for.restype = C.c_char_p
         lib.rays_hip_summary_kernel_name_for.argtypes = [pp, C.c_int]
+    # (likewise the fused trace + deposition entries -- tools/fused_deposition_bench.py)
+    if hasattr(lib, "rays_hip_trace_deposition_device"):
+        lib.rays_hip_trace_deposition_device.restype = C.c_int
+        lib.rays_hip_trace_deposition_device.argtypes = [pp, C.c_int, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp,
+                                                         vp, vp, vp, vp]
+        lib.rays_hip_trace_deposition.restype = C.c_int
+        lib.rays_hip_trace_deposition.argtypes = [pp, C.c_int, dp, dp, dp, C.c_int, C.c_int, ip, ip, dp, dp, dp, dp, dp, dp,
+                                                  dp]
+        lib.rays_hip_deposition_kernel_name_for.restype = C.c_char_p
+        lib.rays_hip_deposition_kernel_name_for.argtypes = [pp, C.c_int]
     lib.rays_hip_ode_step_device.restype = C.c_int
     lib.rays_hip_ode_step_device.argtypes = [pp, C.c_int, vp, vp, vp, vp, vp, vp]
     lib.rays_hip_pack_device.restype = C.c_int
@@ -591,6 +602,67 @@ def trace_summary_device(p: RaysParams, nray: int, d_rvec0: int, d_rindex_vec0: 
         d_start_ray_vec or None, d_end_ray_vec or None, d_end_residuals or None, d_max_residuals or None,
         stream or None)
     _check(rc, "rays_hip_trace_summary_device")
+
+
+def _dep_which(which) -> int:
+    if which not in DEP_PROFILES:
+        raise ValueError(f"deposition profile {which!r}: known are {tuple(DEP_PROFILES)}")
+    return DEP_PROFILES[which]
+
+
+def deposition_kernel_name(p: RaysParams, nray: int = 0) -> str:
+    """Kernel specialisation a fused trace + deposition of `nray` rays would launch (always an exact kernel: the
+    summary-only kernel's name with EQ + 64)."""
+    name = load().rays_hip_deposition_kernel_name_for(C.byref(p), int(nray)).decode()
+    if not name:
+        check_params(p)
+        raise RaysHipError("rays_hip_deposition_kernel_name_for: no fused deposition kernel for this configuration")
+    return name
+
+
+def trace_deposition_device(p: RaysParams, nray: int, d_rvec0: int, d_rindex_vec0: int, d_power: int, which: str,
+                            n_bins: int, d_npoints: int, d_stop_code: int, d_start_ray_vec: int, d_end_ray_vec: int,
+                            d_end_residuals: int, d_max_residuals: int, d_work: int, d_profile_in, d_profile_out: int,
+                            stream: int = 0):
+    """rays_hip_trace_deposition_device: raw device pointers (ints; d_start_ray_vec and d_profile_in may be 0 / None),
+    asynchronous on `stream`.  d_work[n_bins][nray] is zeroed by the call; the profile continues d_profile_in."""
+    w = _dep_which(which)
+    ensure_tables(p)
+    rc = load().rays_hip_trace_deposition_device(
+        C.byref(p), int(nray), d_rvec0 or None, d_rindex_vec0 or None, d_power or None, w, int(n_bins),
+        d_npoints or None, d_stop_code or None, d_start_ray_vec or None, d_end_ray_vec or None, d_end_residuals or None,
+        d_max_residuals or None, d_work or None, d_profile_in or None, d_profile_out or None, stream or None)
+    _check(rc, "rays_hip_trace_deposition_device")
+
+
+def trace_deposition_host(p: RaysParams, rvec0, rindex_vec0, initial_ray_power, which: str, n_bins: int, ngpu: int = 0,
+                          want_work: bool = True) -> dict:
+    """rays_hip_trace_deposition: host numpy arrays in; the per-ray summaries, profile[n_bins] and (want_work)
+    work[nray][n_bins] out -- no trajectory exists anywhere.  ngpu as for trace_host (None: keep the init_devices()
+    selection)."""
+    lib = load()
+    rvec0 = np.ascontiguousarray(rvec0, dtype=np.float64)
+    rindex_vec0 = np.ascontiguousarray(rindex_vec0, dtype=np.float64)
+    power = np.ascontiguousarray(initial_ray_power, dtype=np.float64)
+    nray, nv = len(rvec0), p.nv
+    if power.shape != (nray,):
+        raise ValueError("trace_deposition_host: initial_ray_power must hold one weight per ray")
+    w = _dep_which(which)
+    if ngpu is not None and lib.rays_hip_init(int(ngpu)) < 0:
+        raise RaysHipError("rays_hip_init: " + last_error())
+    ensure_tables(p)
+    nb = max(int(n_bins), 0)
+    out = dict(npoints=np.zeros(nray, dtype=np.int32), stop_code=np.zeros(nray, dtype=np.int32),
+               start_ray_vec=np.zeros((nray, nv)), end_ray_vec=np.zeros((nray, nv)), end_residuals=np.zeros(nray),
+               max_residuals=np.zeros(nray), work=np.zeros((nray, nb)) if want_work else None, profile=np.zeros(nb))
+    el = C.c_double(0.0)
+    rc = lib.rays_hip_trace_deposition(C.byref(p), nray, _dp(rvec0), _dp(rindex_vec0), _dp(power), w, int(n_bins),
+                                       _ip(out["npoints"]), _ip(out["stop_code"]), _dp(out["start_ray_vec"]),
+                                       _dp(out["end_ray_vec"]), _dp(out["end_residuals"]), _dp(out["max_residuals"]),
+                                       _dp(out["work"]) if want_work else None, _dp(out["profile"]), C.byref(el))
+    _check(rc, "rays_hip_trace_deposition")
+    out["elapsed_s"] = el.value
+    return out
 
 
 def scan_summary_device(p: RaysParams, n_runs: int, d_ds_values: int, nray: int, d_rvec0: int, d_rindex_vec0: int,

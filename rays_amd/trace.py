@@ -122,6 +122,53 @@ class RaySummaries:
         return int(np.maximum(self.npoints.astype(np.int64) - 1, 0).sum())
 
 
+@dataclasses.dataclass
+class RayDeposition:
+    """What a fused trace + deposition returns (rays_hip_trace_deposition*): the per-ray summaries and one deposition
+    profile, binned while the rays were traced -- no trajectory exists.  `profile_record` is the dictionary
+    results.write_deposition_profiles_LD / _NC take."""
+
+    summaries: RaySummaries
+    profile_name: str            # 'Ptotal_psi' | 'Ptotal_rho' | 'Ptotal_x'
+    n_bins: int
+    grid_min: float
+    grid_max: float
+    profile: np.ndarray          # [n_bins]   sum(work, 2) in ray order
+    work: Optional[np.ndarray]   # [nray][n_bins]  the reference's work(n_bins, nray); None if not asked for
+
+    @property
+    def Q_sum(self) -> float:    # the ordered sum of the profile (deposition_profiles_m.f90:251)
+        q = 0.0
+        for x in self.profile:
+            q = q + float(x)
+        return q
+
+    @property
+    def profile_record(self) -> Dict[str, Any]:
+        from .results import deposition_grid
+        return dict(profile_name=self.profile_name, grid_name=self.profile_name.split("_")[1], profile=self.profile,
+                    grid=deposition_grid(self.grid_min, self.grid_max, self.n_bins), Q_sum=self.Q_sum,
+                    n_bins=self.n_bins, grid_min=self.grid_min, grid_max=self.grid_max)
+
+
+def deposition_grid_limits(params: RaysParams, which: str):
+    """(grid_min, grid_max) of a deposition profile: the slab box in x for 'Ptotal_x' (deposition_profiles_m.f90:136-137),
+    0..1 for psiN and rho (:176-177)."""
+    if which == "Ptotal_x":
+        return float(params.slab.xmin), float(params.slab.xmax)
+    return 0.0, 1.0
+
+
+def _deposition_spec(deposition, with_power: bool):
+    """(which, n_bins[, power]) of a `deposition=` argument."""
+    want = 3 if with_power else 2
+    if not isinstance(deposition, (tuple, list)) or len(deposition) != want:
+        raise ValueError("deposition=(which, n_bins, power)" if with_power else "deposition=(which, n_bins)")
+    if deposition[0] not in hip.DEP_PROFILES:
+        raise ValueError(f"deposition profile {deposition[0]!r}: known are {tuple(hip.DEP_PROFILES)}")
+    return deposition
+
+
 def load_axisym_tables(namelist_path: str, nml: Dict[str, Dict[str, Any]]) -> Optional[Dict[str, Any]]:
     """Host-built spline tables of an eqdsk equilibrium: `<eqdsk_file_name>.tables.npz` next to the
     namelist (None for the analytic equilibria)."""
@@ -183,8 +230,25 @@ class RaysRun:
     def nray(self) -> int:
         return len(self.rvec0)
 
-    def trace_rays(self, ngpu: int = 1, trajectories: bool = True):
-        """trajectories=False: the summary-only trace (RaySummaries; no trajectory array on the device or the host)."""
+    def trace_rays(self, ngpu: int = 1, trajectories: bool = True, deposition=None, want_work: bool = False):
+        """trajectories=False: the summary-only trace (RaySummaries; no trajectory array on the device or the host).
+        trajectories=False, deposition=(which, n_bins): the fused trace + deposition (RayDeposition: the summaries and
+        the profile `which` of the launcher's power weights ray_pwr_wt -- initial_ray_power of the run's results -- with
+        work[nray][n_bins] if want_work)."""
+        if deposition is not None:
+            if trajectories:
+                raise ValueError("RaysRun.trace_rays: deposition=... is the fused trace without trajectories -- pass "
+                                 "trajectories=False (or bin a full trace with hip.deposition_host)")
+            which, n_bins = _deposition_spec(deposition, False)
+            if self.ray_pwr_wt is None:
+                raise ValueError("RaysRun.trace_rays: deposition=... needs the launcher's power weights (ray_pwr_wt); this "
+                                 "run has none")
+            power = np.asarray(self.ray_pwr_wt, dtype=np.float64)
+            out = hip.trace_deposition_host(self.params, self.rvec0, self.rindex_vec0, power, which, int(n_bins),
+                                            ngpu=ngpu, want_work=want_work)
+            work, prof = out.pop("work"), out.pop("profile")
+            lo, hi = deposition_grid_limits(self.params, which)
+            return RayDeposition(RaySummaries(**out), which, int(n_bins), lo, hi, prof, work)
         if not trajectories:
             return RaySummaries(**hip.trace_summary_host(self.params, self.rvec0, self.rindex_vec0, ngpu=ngpu))
         out = hip.trace_host(self.params, self.rvec0, self.rindex_vec0, ngpu=ngpu)
@@ -211,9 +275,14 @@ class DeviceTrace:
     """Device-resident trace: inputs/outputs are torch CUDA tensors, launches are asynchronous on
     the current torch stream (used by bench.py and by multi-GPU runs).
     trajectories=False: summary-only (rays_hip_trace_summary_device) -- ray_vec and residual are None, no trajectory
-    tensor is allocated, start_ray_vec exists instead, results() returns a RaySummaries."""
+    tensor is allocated, start_ray_vec exists instead, results() returns a RaySummaries.
+    trajectories=False, deposition=(which, n_bins, power): the fused trace + deposition (rays_hip_trace_deposition_device)
+    -- additionally .work[n_bins][nray] (bin-major, zeroed by every launch) and .profile[n_bins] of the profile `which`
+    with the per-ray power weights `power`; profile_in: a tensor[n_bins] of running sums the profile continues (the
+    block of rays before this one), None = from zero."""
 
-    def __init__(self, params: RaysParams, rvec0, rindex_vec0, device=None, trajectories: bool = True):
+    def __init__(self, params: RaysParams, rvec0, rindex_vec0, device=None, trajectories: bool = True, deposition=None,
+                 profile_in=None):
         import torch
 
         self.torch = torch
@@ -222,6 +291,19 @@ class DeviceTrace:
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
         self.nray = len(rvec0)
         self.trajectories = bool(trajectories)
+        self.deposition = None
+        self.work = self.profile = self.power = None
+        self.profile_in = profile_in
+        if deposition is not None:
+            if self.trajectories:
+                raise ValueError("DeviceTrace: deposition=... is the fused trace without trajectories -- pass "
+                                 "trajectories=False (or bin a full trace with hip.deposition_device)")
+            which, n_bins, power = _deposition_spec(deposition, True)
+            if len(power) != self.nray:
+                raise ValueError("DeviceTrace: deposition power must hold one weight per ray")
+            self.deposition = (which, int(n_bins))
+        elif profile_in is not None:
+            raise ValueError("DeviceTrace: profile_in without deposition=...")
         nv, npt = params.nv, params.nstep_max + 1
         f64, i32 = torch.float64, torch.int32
         self.ray_vec = self.residual = self.start_ray_vec = None
@@ -239,10 +321,26 @@ class DeviceTrace:
             self.end_ray_vec = torch.zeros((self.nray, nv), dtype=f64, device=self.device)
             self.end_residuals = torch.zeros(self.nray, dtype=f64, device=self.device)
             self.max_residuals = torch.zeros(self.nray, dtype=f64, device=self.device)
+            if self.deposition is not None:
+                nb = max(self.deposition[1], 0)
+                pw = deposition[2]
+                self.power = (pw.to(device=self.device, dtype=f64).contiguous() if torch.is_tensor(pw)
+                              else torch.as_tensor(np.ascontiguousarray(pw, dtype=np.float64)).to(self.device))
+                self.work = torch.zeros((nb, self.nray), dtype=f64, device=self.device)
+                self.profile = torch.zeros(nb, dtype=f64, device=self.device)
 
     def launch(self, zero_fill: bool = True):
         t = self.torch
         stream = t.cuda.current_stream(self.device).cuda_stream
+        if self.deposition is not None:
+            hip.trace_deposition_device(self.params, self.nray, self.rvec0.data_ptr(), self.rindex_vec0.data_ptr(),
+                                        self.power.data_ptr(), self.deposition[0], self.deposition[1],
+                                        self.npoints.data_ptr(), self.stop_code.data_ptr(), self.start_ray_vec.data_ptr(),
+                                        self.end_ray_vec.data_ptr(), self.end_residuals.data_ptr(),
+                                        self.max_residuals.data_ptr(), self.work.data_ptr(),
+                                        None if self.profile_in is None else self.profile_in.data_ptr(),
+                                        self.profile.data_ptr(), stream=stream)
+            return
         if not self.trajectories:
             hip.trace_summary_device(self.params, self.nray, self.rvec0.data_ptr(), self.rindex_vec0.data_ptr(),
                                      self.npoints.data_ptr(), self.stop_code.data_ptr(), self.start_ray_vec.data_ptr(),

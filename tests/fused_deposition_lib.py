@@ -1,0 +1,143 @@
+"""TEST INFRASTRUCTURE ONLY: what the fused trace + deposition tests share -- the fixtures that carry the reference
+post-processor's profiles, the expected values cut from them, and the ctypes wrappers around the host emulation of the
+fused kernels (tests/hip_emul/emul_fused_deposition.cpp: TraceArgs::residual is null there and ::ray_vec carries the
+DepTraceArgs block, as in the product's launches)."""
+from __future__ import annotations
+
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+
+from rays_amd.params import RaysParams
+from tests import summary_lib as sl
+from tests.common import ROOT, stop_codes
+
+# the fixtures with dep_work / dep_profile / dep_q_sum of the reference post-processor (tests/golden/make_golden.py)
+DEP_FIXTURES = ["gold_axisym16_eqdsk_zexit_rk4", "gold_axisym64_eqdsk129_tspline_damp_rk4",
+                "gold_axisym64_eqdsk129_tspline_damp_sg", "gold_axisym64_eqdsk_damp_rk4", "gold_axisym64_eqdsk_damp_sg",
+                "gold_axisym64_eqdsk_tspline_rk4_num", "gold_axisym64_eqlin_damp_rk4", "gold_axisym64_eqlin_tspline_sg_num",
+                "gold_axisym64_solmag_damp_rk4", "gold_axisym64_solmag_sg_num", "gold_slab16_damp_multi_grad_rk4",
+                "gold_slab16_damp_rk4"]
+WHICH = {"Ptotal_psi": 0, "Ptotal_rho": 1, "Ptotal_x": 2}
+_DIR = os.path.join(ROOT, "tests", "hip_emul")
+_CSRC = os.path.join(ROOT, "rays_amd", "csrc")
+
+
+def profile_names(g):
+    return [str(n).strip() for n in g["dep_names"]]
+
+
+def rho_table(g):
+    """(grid, fspl) of the fixture's rho(psiN) spline, or (None, None)."""
+    if "dep_rho_grid" in g.files:
+        return (np.ascontiguousarray(g["dep_rho_grid"], dtype=np.float64),
+                np.ascontiguousarray(g["dep_rho_fspl"], dtype=np.float64))
+    return None, None
+
+
+def ordered_sum(profile) -> float:
+    """Q_sum: the sum of the profile in bin order (deposition_profiles_m.f90:251)."""
+    q = 0.0
+    for x in np.asarray(profile, dtype=np.float64):
+        q = q + float(x)
+    return q
+
+
+def assert_golden_summaries(out: dict, g, what: str):
+    """The fused trace of a fixture's FULL fan against what the fixture holds of it: npoints, stop flags and point 1 of
+    every ray, and every summary of the rays whose trajectories the fixture records (ray_index)."""
+    np.testing.assert_array_equal(out["npoints"], g["npoints_full"], err_msg=what + ": npoints")
+    np.testing.assert_array_equal(out["stop_code"], stop_codes(g["stop_flag_full"]), err_msg=what + ": stop_code")
+    np.testing.assert_array_equal(out["start_ray_vec"], g["dep_ray_vec_full"][:, 0, :], err_msg=what + ": start_ray_vec")
+    idx = g["ray_index"].astype(np.int64)   # zero-based rows of the full fan
+    sl.assert_same({k: np.asarray(out[k])[idx] for k in sl.KEYS}, sl.golden_summaries(g), what + " (recorded rays)")
+
+
+def assert_golden_deposition(work_rows, profile, g, i: int, what: str):
+    """work[nray][n_bins], profile and Q_sum against profile i of the fixture, bit for bit."""
+    np.testing.assert_array_equal(work_rows, g["dep_work"][i], err_msg=what + ": work")
+    np.testing.assert_array_equal(profile, g["dep_profile"][i], err_msg=what + ": profile")
+    assert ordered_sum(profile) == float(g["dep_q_sum"][i]), what + ": Q_sum"
+
+
+# ---- host emulation of the fused kernels -------------------------------------------------------------------------------
+_libs = {}
+_SRCS = ["emul_fused_deposition.cpp", "emul_trace.cpp", "emul_group.cpp", "hip/hip_runtime.h", "hip/hip_wave_emul.h"]
+_PRODUCT = sl._PRODUCT + ["rays_deposition.hpp"]
+
+
+def emul_lib(wave: bool = False, tag: str = "", defs=()):
+    """librays_emul_fused[_wave][_<tag>].so, built on first use (extra -D switches get a library of their own)."""
+    key = (wave, tag)
+    if key in _libs:
+        return _libs[key]
+    path = os.path.join(_DIR, "librays_emul_fused" + ("_wave" if wave else "") + (f"_{tag}" if tag else "") + ".so")
+    srcs = [os.path.join(_DIR, f) for f in _SRCS] + [os.path.join(_CSRC, f) for f in _PRODUCT]
+    if not os.path.exists(path) or any(os.path.getmtime(s) > os.path.getmtime(path) for s in srcs):
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fno-extern-tls-init",
+                               "-fPIC", "-shared", "-w", "-DRAYS_RK4_NO_HANDOVER",
+                               *(["-DRAYS_EMUL_DEPOSIT_WAVE=1"] if wave else []), *defs, "-I", _DIR, srcs[0], "-o", path])
+    lib = C.CDLL(path)
+    dp, ip, pp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(RaysParams)
+    tail = [dp, C.c_int, C.c_int, dp, dp, C.c_int, ip, ip, dp, dp, dp, dp, dp, dp, dp]
+    if wave:
+        lib.rays_emul_fused_deposition_waves.restype = C.c_int
+        lib.rays_emul_fused_deposition_waves.argtypes = [pp, C.c_int, C.c_int, C.c_int, C.c_int, dp, dp] + tail
+    else:
+        lib.rays_emul_fused_deposition.restype = C.c_int
+        lib.rays_emul_fused_deposition.argtypes = [pp, C.c_int, dp, dp] + tail
+    lib.rays_emul_set_zfun_table.restype = C.c_int
+    lib.rays_emul_set_zfun_table.argtypes = [dp, C.c_int, C.c_double, C.c_double]
+    from tests.emul_lib import _set_zfun
+    _set_zfun(lib.rays_emul_set_zfun_table)
+    _libs[key] = lib
+    return lib
+
+
+def _outputs(n, nv, n_bins):
+    out = sl._outputs(n, nv)   # poisoned: every element has to be written by the kernel
+    out["work"] = np.full((n_bins, n), np.nan)   # bin-major, as on the device (zeroed by the launch)
+    out["profile"] = np.full(n_bins, np.nan)
+    return out
+
+
+def _tail(out, power, which, n_bins, rho, profile_in):
+    d, i = sl._d, sl._i
+    grid, fspl = rho if rho is not None else (None, None)
+    return [d(power), WHICH[which], int(n_bins), d(grid), d(fspl), 0 if grid is None else len(grid), i(out["npoints"]),
+            i(out["stop_code"]), d(out["start_ray_vec"]), d(out["end_ray_vec"]), d(out["end_residuals"]),
+            d(out["max_residuals"]), d(out["work"]), d(profile_in), d(out["profile"])]
+
+
+def emul_fused(p: RaysParams, rvec0, rindex_vec0, power, which: str, n_bins: int, rho=None, profile_in=None, lib=None):
+    """The fused kernel of p's shape on one emulated lane: summaries, work[nray][n_bins] (transposed to the reference's
+    layout) and the profile."""
+    rvec0 = np.ascontiguousarray(rvec0, dtype=np.float64)
+    rindex_vec0 = np.ascontiguousarray(rindex_vec0, dtype=np.float64)
+    power = np.ascontiguousarray(power, dtype=np.float64)
+    pin = None if profile_in is None else np.ascontiguousarray(profile_in, dtype=np.float64)
+    out = _outputs(len(rvec0), p.nv, n_bins)
+    rc = (lib or emul_lib()).rays_emul_fused_deposition(C.byref(p), len(rvec0), sl._d(rvec0), sl._d(rindex_vec0),
+                                                        *_tail(out, power, which, n_bins, rho, pin))
+    if rc:
+        raise RuntimeError(f"rays_emul_fused_deposition rc={rc}")
+    out["work"] = np.ascontiguousarray(out["work"].T)
+    return out
+
+
+def emul_fused_waves(p: RaysParams, rvec0, rindex_vec0, power, which: str, n_bins: int, kind: str, blocks: int = 1,
+                     stride: int = 0, rho=None, lib=None):
+    """The fused kernel on whole emulated waves (kind "rk4" | "sg")."""
+    rvec0 = np.ascontiguousarray(rvec0, dtype=np.float64)
+    rindex_vec0 = np.ascontiguousarray(rindex_vec0, dtype=np.float64)
+    power = np.ascontiguousarray(power, dtype=np.float64)
+    out = _outputs(len(rvec0), p.nv, n_bins)
+    rc = (lib or emul_lib(wave=True)).rays_emul_fused_deposition_waves(
+        C.byref(p), sl.WAVE_KINDS[kind], int(blocks), int(stride), len(rvec0), sl._d(rvec0), sl._d(rindex_vec0),
+        *_tail(out, power, which, n_bins, rho, None))
+    if rc:
+        raise RuntimeError(f"rays_emul_fused_deposition_waves rc={rc}")
+    out["work"] = np.ascontiguousarray(out["work"].T)
+    return out
