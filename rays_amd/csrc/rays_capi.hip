@@ -33,60 +33,30 @@
 #include "rays_capi_resources.hpp"
 
 namespace rays {
-#define RAYS_DECL_ENTRIES(s, e, d) \
-  const KernelEntry* rays_entries_##s##_##e##_##d##_0_0(int* n); \
-  const KernelEntry* rays_entries_##s##_##e##_##d##_1_0(int* n); \
-  const KernelEntry* rays_entries_##s##_##e##_##d##_0_1(int* n); \
-  const KernelEntry* rays_entries_##s##_##e##_##d##_1_1(int* n);
-RAYS_DECL_ENTRIES(0, 0, 0)
-RAYS_DECL_ENTRIES(0, 0, 1)
-RAYS_DECL_ENTRIES(0, 1, 0)
-RAYS_DECL_ENTRIES(0, 1, 1)
-RAYS_DECL_ENTRIES(0, 2, 0)
-RAYS_DECL_ENTRIES(0, 2, 1)
-RAYS_DECL_ENTRIES(1, 0, 0)
-RAYS_DECL_ENTRIES(1, 0, 1)
-RAYS_DECL_ENTRIES(1, 1, 0)
-RAYS_DECL_ENTRIES(1, 1, 1)
-RAYS_DECL_ENTRIES(1, 2, 0)
-RAYS_DECL_ENTRIES(1, 2, 1)
-#undef RAYS_DECL_ENTRIES
+// The twelve (solver, equilibrium, derivative) kernel groups; each holds four entry lists (unit exponents x
+// multi_spec_damping).  The declarations here and find_kernel's table are generated from this one list.
+#define RAYS_GROUPS(X) \
+  X(0, 0, 0) X(0, 0, 1) X(0, 1, 0) X(0, 1, 1) X(0, 2, 0) X(0, 2, 1) \
+  X(1, 0, 0) X(1, 0, 1) X(1, 1, 0) X(1, 1, 1) X(1, 2, 0) X(1, 2, 1)
+#define RAYS_DECL_ENTRIES(attr, prefix, s, e, d) \
+  attr const KernelEntry* prefix##s##_##e##_##d##_0_0(int* n); \
+  attr const KernelEntry* prefix##s##_##e##_##d##_1_0(int* n); \
+  attr const KernelEntry* prefix##s##_##e##_##d##_0_1(int* n); \
+  attr const KernelEntry* prefix##s##_##e##_##d##_1_1(int* n);
+#define RAYS_DECL_REC(s, e, d) RAYS_DECL_ENTRIES(, rays_entries_, s, e, d)
 // the summary-only variants (rays_device.hpp: kEqNoTraj) of the same groups.  Weak: librays_hip.so holds all of them
 // (Makefile: SUM_OBJS); a library linked from this file and a few groups only -- the CPU tier's emulated C ABI --
 // finds the others null, and find_kernel then reports no summary kernel for them.
-#define RAYS_DECL_ENTRIES(s, e, d) \
-  __attribute__((weak)) const KernelEntry* rays_entries_sum_##s##_##e##_##d##_0_0(int* n); \
-  __attribute__((weak)) const KernelEntry* rays_entries_sum_##s##_##e##_##d##_1_0(int* n); \
-  __attribute__((weak)) const KernelEntry* rays_entries_sum_##s##_##e##_##d##_0_1(int* n); \
-  __attribute__((weak)) const KernelEntry* rays_entries_sum_##s##_##e##_##d##_1_1(int* n);
-RAYS_DECL_ENTRIES(0, 0, 0)
-RAYS_DECL_ENTRIES(0, 0, 1)
-RAYS_DECL_ENTRIES(0, 1, 0)
-RAYS_DECL_ENTRIES(0, 1, 1)
-RAYS_DECL_ENTRIES(0, 2, 0)
-RAYS_DECL_ENTRIES(0, 2, 1)
-RAYS_DECL_ENTRIES(1, 0, 0)
-RAYS_DECL_ENTRIES(1, 0, 1)
-RAYS_DECL_ENTRIES(1, 1, 0)
-RAYS_DECL_ENTRIES(1, 1, 1)
-RAYS_DECL_ENTRIES(1, 2, 0)
-RAYS_DECL_ENTRIES(1, 2, 1)
-#undef RAYS_DECL_ENTRIES
+#define RAYS_DECL_SUM(s, e, d) RAYS_DECL_ENTRIES(__attribute__((weak)), rays_entries_sum_, s, e, d)
 // the fused deposition variants (rays_device_arith.inc: kEqDeposit) of the slab and axisym_toroid groups (Makefile:
-// DEP_OBJS).  Weak for the same reason.
-#define RAYS_DECL_ENTRIES(s, e, d) \
-  __attribute__((weak)) const KernelEntry* rays_entries_dep_##s##_##e##_##d##_0_0(int* n); \
-  __attribute__((weak)) const KernelEntry* rays_entries_dep_##s##_##e##_##d##_1_0(int* n); \
-  __attribute__((weak)) const KernelEntry* rays_entries_dep_##s##_##e##_##d##_0_1(int* n); \
-  __attribute__((weak)) const KernelEntry* rays_entries_dep_##s##_##e##_##d##_1_1(int* n);
-RAYS_DECL_ENTRIES(0, 0, 0)
-RAYS_DECL_ENTRIES(0, 0, 1)
-RAYS_DECL_ENTRIES(0, 2, 0)
-RAYS_DECL_ENTRIES(0, 2, 1)
-RAYS_DECL_ENTRIES(1, 0, 0)
-RAYS_DECL_ENTRIES(1, 0, 1)
-RAYS_DECL_ENTRIES(1, 2, 0)
-RAYS_DECL_ENTRIES(1, 2, 1)
+// DEP_OBJS).  Weak for the same reason; no library defines those of the Solovev groups, which are null everywhere.
+#define RAYS_DECL_DEP(s, e, d) RAYS_DECL_ENTRIES(__attribute__((weak)), rays_entries_dep_, s, e, d)
+RAYS_GROUPS(RAYS_DECL_REC)
+RAYS_GROUPS(RAYS_DECL_SUM)
+RAYS_GROUPS(RAYS_DECL_DEP)
+#undef RAYS_DECL_REC
+#undef RAYS_DECL_SUM
+#undef RAYS_DECL_DEP
 #undef RAYS_DECL_ENTRIES
 #define RAYS_DECL_TOL(e) \
   const KernelEntry* rays_entries_tol_0_##e##_0_0_0(int* n); \
@@ -180,52 +150,54 @@ int initial_numerics() {
 }
 std::atomic<int> g_numerics{initial_numerics()};
 
+// Which build of a configuration's kernel a launch wants:
+//   Recording  the kernel that records the trajectories, in the flavour the numerics setting selects
+//   ExactTwin  the exact twin of a tolerance kernel, whose resume kernel takes the handed-over steps: always the
+//              one-wave-per-SIMD entry (the only one that carries a resume kernel), whatever the fan size or the
+//              developer switch
+//   Summary    the summary-only variant of the exact kernel (always exact: the numerics setting is a permission, and the
+//              tolerance kernels' hand-over reads residual(:)).  Its objects hold the same shapes as the recording ones
+//              (rays_inst.hip), so a configuration is traced summary-only exactly when it is traced at all.
+//   Deposit    the fused deposition variant of the summary-only kernel (slab and axisym_toroid groups)
+enum class KernelVariant { Recording, ExactTwin, Summary, Deposit };
+
 // nray: fan size (0 = unknown).  From two waves per SIMD worth of rays on, the two-waves-per-SIMD build
 // of the kernel is preferred where one exists (rays_rk4.hpp) -- under the tolerance flavour for the slab only: the
 // two-waves build has no hand-over of ill-conditioned steps (rays_rk4_body.inc), which the slab fans do not need
 // (no coalescence; surveyed on 32.8 M steps) and every other equilibrium may.
-// force_exact: the exact twin of a tolerance kernel, whose resume kernel takes the handed-over steps: always the
-// one-wave-per-SIMD entry (the only one that carries a resume kernel), whatever the fan size or the developer switch.
-// summary: the summary-only variant of the exact kernel (always exact: the numerics setting is a permission, and the
-// tolerance kernels' hand-over reads residual(:)).  Its objects hold the same shapes as the recording ones
-// (rays_inst.hip), so a configuration is traced summary-only exactly when it is traced at all.
-// deposit (with summary): the fused deposition variant of the summary-only kernel (slab and axisym_toroid groups).
-const rays::KernelEntry* find_kernel(const rays_params_t& p, long long nray = 0, bool force_exact = false,
-                                     bool summary = false, bool deposit = false) {
+const rays::KernelEntry* find_kernel(const rays_params_t& p, long long nray = 0,
+                                     KernelVariant variant = KernelVariant::Recording) {
   using namespace rays;
   typedef const KernelEntry* (*Getter)(int*);
-  // [solver][equilibrium][derivative][unit exponents][multi_spec_damping]
-#define RAYS_G(s, e, d) {{rays_entries_##s##_##e##_##d##_0_0, rays_entries_##s##_##e##_##d##_0_1}, \
-                         {rays_entries_##s##_##e##_##d##_1_0, rays_entries_##s##_##e##_##d##_1_1}}
-  static const Getter getters[2][3][2][2][2] = {
-      {{RAYS_G(0, 0, 0), RAYS_G(0, 0, 1)}, {RAYS_G(0, 1, 0), RAYS_G(0, 1, 1)}, {RAYS_G(0, 2, 0), RAYS_G(0, 2, 1)}},
-      {{RAYS_G(1, 0, 0), RAYS_G(1, 0, 1)}, {RAYS_G(1, 1, 0), RAYS_G(1, 1, 1)}, {RAYS_G(1, 2, 0), RAYS_G(1, 2, 1)}}};
-#undef RAYS_G
-#define RAYS_G(s, e, d) {{rays_entries_sum_##s##_##e##_##d##_0_0, rays_entries_sum_##s##_##e##_##d##_0_1}, \
-                         {rays_entries_sum_##s##_##e##_##d##_1_0, rays_entries_sum_##s##_##e##_##d##_1_1}}
-  static const Getter sum_getters[2][3][2][2][2] = {
-      {{RAYS_G(0, 0, 0), RAYS_G(0, 0, 1)}, {RAYS_G(0, 1, 0), RAYS_G(0, 1, 1)}, {RAYS_G(0, 2, 0), RAYS_G(0, 2, 1)}},
-      {{RAYS_G(1, 0, 0), RAYS_G(1, 0, 1)}, {RAYS_G(1, 1, 0), RAYS_G(1, 1, 1)}, {RAYS_G(1, 2, 0), RAYS_G(1, 2, 1)}}};
-#undef RAYS_G
-#define RAYS_G(s, e, d) {{rays_entries_dep_##s##_##e##_##d##_0_0, rays_entries_dep_##s##_##e##_##d##_0_1}, \
-                         {rays_entries_dep_##s##_##e##_##d##_1_0, rays_entries_dep_##s##_##e##_##d##_1_1}}
-#define RAYS_G0 {{nullptr, nullptr}, {nullptr, nullptr}}
-  static const Getter dep_getters[2][3][2][2][2] = {
-      {{RAYS_G(0, 0, 0), RAYS_G(0, 0, 1)}, {RAYS_G0, RAYS_G0}, {RAYS_G(0, 2, 0), RAYS_G(0, 2, 1)}},
-      {{RAYS_G(1, 0, 0), RAYS_G(1, 0, 1)}, {RAYS_G0, RAYS_G0}, {RAYS_G(1, 2, 0), RAYS_G(1, 2, 1)}}};
-#undef RAYS_G0
-#undef RAYS_G
+  // [recording | summary | deposit][solver][equilibrium][derivative][unit exponents][multi_spec_damping]
+  struct Table {
+    Getter g[3][2][3][2][2][2];
+  };
+  static const Table table = [] {
+    Table t = {};
+#define RAYS_FILL(v, prefix, s, e, d)                                                                       \
+  t.g[v][s][e][d][0][0] = prefix##s##_##e##_##d##_0_0; t.g[v][s][e][d][0][1] = prefix##s##_##e##_##d##_0_1; \
+  t.g[v][s][e][d][1][0] = prefix##s##_##e##_##d##_1_0; t.g[v][s][e][d][1][1] = prefix##s##_##e##_##d##_1_1;
+#define RAYS_FILL_ALL(s, e, d) \
+  RAYS_FILL(0, rays_entries_, s, e, d) RAYS_FILL(1, rays_entries_sum_, s, e, d) RAYS_FILL(2, rays_entries_dep_, s, e, d)
+    RAYS_GROUPS(RAYS_FILL_ALL)
+#undef RAYS_FILL_ALL
+#undef RAYS_FILL
+    return t;
+  }();
   // tolerance flavour of the cold RK4 groups [equilibrium][unit exponents]
   static const Getter tol_getters[3][2] = {{rays_entries_tol_0_0_0_0_0, rays_entries_tol_0_0_0_1_0},
                                            {rays_entries_tol_0_1_0_0_0, rays_entries_tol_0_1_0_1_0},
                                            {rays_entries_tol_0_2_0_0_0, rays_entries_tol_0_2_0_1_0}};
   int n = 0;
-  const bool tol = !force_exact && !summary && g_numerics.load() == RAYS_NUMERICS_TOLERANCE && p.ode_solver == RAYS_ODE_RK4 &&
-                   p.ray_deriv == RAYS_DERIV_COLD && !p.multi_spec_damping;
+  const bool force_exact = variant == KernelVariant::ExactTwin;
+  const bool tol = variant == KernelVariant::Recording && g_numerics.load() == RAYS_NUMERICS_TOLERANCE &&
+                   p.ode_solver == RAYS_ODE_RK4 && p.ray_deriv == RAYS_DERIV_COLD && !p.multi_spec_damping;
+  const int row = variant == KernelVariant::Summary ? 1 : variant == KernelVariant::Deposit ? 2 : 0;
   const Getter getter = tol ? tol_getters[p.equilib_model][unit_exponents(p) ? 1 : 0]
-                            : (summary ? (deposit ? dep_getters : sum_getters) : getters)[p.ode_solver][p.equilib_model][p.ray_deriv]
-                                  [unit_exponents(p) ? 1 : 0][p.multi_spec_damping ? 1 : 0];
-  if (!getter) return nullptr;  // (a summary group this library was linked without)
+                            : table.g[row][p.ode_solver][p.equilib_model][p.ray_deriv][unit_exponents(p) ? 1 : 0]
+                                     [p.multi_spec_damping ? 1 : 0];
+  if (!getter) return nullptr;  // (a summary or deposit group this library was linked without)
   const KernelEntry* e = getter(&n);
   int ncu = 256;
   {
@@ -317,6 +289,13 @@ int get_axisym_device(rays::DevParams* D) {
   return 0;
 }
 
+// The kernels' parameter block for p with the axisym_toroid tables on the current device (uploaded when stale), for the
+// entries that read no Z-function table.
+int dev_params_with_axisym(const rays_params_t* p, rays::DevParams* D) {
+  *D = make_dev_params(*p);
+  return p->equilib_model == RAYS_EQ_AXISYM ? get_axisym_device(D) : 0;
+}
+
 // rho(psiN) spline table: host = grid[n] then fspl[n][4]
 struct RhoTable : DeviceTable {
   int n = 0;
@@ -326,6 +305,22 @@ int get_rho_device(const double** out, int* n) {
   if (g_rho.n < 2) return fail("Ptotal_rho needs rays_hip_set_rho_table() first");
   HIP_TRY_AS("hipMalloc / hipMemcpy (rho table)", g_rho.device_ptr(out));
   *n = g_rho.n;
+  return 0;
+}
+
+// The binning grid of `which` and the rho(psiN) table on the current device: the same members of DepArgs and DepTraceArgs.
+template <class Args>
+int fill_deposition_grid(const rays_params_t* p, int which, Args* A) {
+  A->grid_min = 0.0; A->grid_max = 1.0;  // deposition_profiles_m.f90:176-177
+  if (which == RAYS_DEP_PTOTAL_X) { A->grid_min = p->slab.xmin; A->grid_max = p->slab.xmax; }  // :136-137
+  A->rho_grid = nullptr; A->rho_fspl = nullptr; A->n_rho = 0;
+  if (which == RAYS_DEP_PTOTAL_RHO) {
+    const double* t = nullptr;
+    int n = 0;
+    const int rc = get_rho_device(&t, &n);
+    if (rc) return rc;
+    A->rho_grid = t; A->rho_fspl = t + n; A->n_rho = n;
+  }
   return 0;
 }
 
@@ -428,18 +423,7 @@ int rays_hip_set_zfun_table(const double* fspl_re, int nx, double x_min, double 
   return 0;
 }
 
-namespace {
-int set_axisym_tables_impl(const rays_axisym_tables_t* t, bool lin, double dR, double dZ);
-}
-int rays_hip_set_axisym_tables(const rays_axisym_tables_t* t) { return set_axisym_tables_impl(t, false, 0., 0.); }
-int rays_hip_set_eqdsk_lin_tables(const rays_axisym_tables_t* t, double dR, double dZ) {
-  if (!t || t->nr < 2 || t->nz < 2 || t->n_rb != t->nr || !t->r_grid || !t->z_grid || !t->psi_fspl || !t->rb_fspl ||
-      !(dR > 0.) || !(dZ > 0.))
-    return fail("rays_hip_set_eqdsk_lin_tables: bad tables");
-  return set_axisym_tables_impl(t, true, dR, dZ);
-}
-namespace {
-int set_axisym_tables_impl(const rays_axisym_tables_t* t, bool lin, double dR, double dZ) {
+static int set_axisym_tables_impl(const rays_axisym_tables_t* t, bool lin, double dR, double dZ) {
   // (magnetics_model = 'solovev_magnetics' with splined profiles: nr = nz = n_rb = 0, profile tables only)
   const bool profiles_only = t && t->nr == 0 && t->nz == 0 && t->n_rb == 0 && (t->n_ne > 0 || t->n_te > 0 || t->n_ti > 0);
   if (!t || (!profiles_only && !lin && (t->nr < 2 || t->nz < 2 || t->n_rb < 2 || !t->r_grid || !t->z_grid || !t->psi_fspl ||
@@ -469,7 +453,13 @@ int set_axisym_tables_impl(const rays_axisym_tables_t* t, bool lin, double dR, d
   h.version++;
   return 0;
 }
-}  // namespace
+int rays_hip_set_axisym_tables(const rays_axisym_tables_t* t) { return set_axisym_tables_impl(t, false, 0., 0.); }
+int rays_hip_set_eqdsk_lin_tables(const rays_axisym_tables_t* t, double dR, double dZ) {
+  if (!t || t->nr < 2 || t->nz < 2 || t->n_rb != t->nr || !t->r_grid || !t->z_grid || !t->psi_fspl || !t->rb_fspl ||
+      !(dR > 0.) || !(dZ > 0.))
+    return fail("rays_hip_set_eqdsk_lin_tables: bad tables");
+  return set_axisym_tables_impl(t, true, dR, dZ);
+}
 
 int rays_hip_sizeof_params(void) { return (int)sizeof(rays_params_t); }
 
@@ -629,7 +619,7 @@ const char* rays_hip_kernel_name_for(const rays_params_t* p, int nray) {
 
 const char* rays_hip_summary_kernel_name_for(const rays_params_t* p, int nray) {
   if (!p || rays_hip_check_params(p)) return "";
-  const rays::KernelEntry* k = find_kernel(*p, nray, false, true);
+  const rays::KernelEntry* k = find_kernel(*p, nray, KernelVariant::Summary);
   return k ? k->name : "";
 }
 
@@ -669,20 +659,19 @@ struct TraceExtras {
   const double* s0 = nullptr;
   const double* ds_run = nullptr;
   int rays_per_run = 0;
-  // summary-only launch (rays_hip_trace_summary_device): no trajectory arrays, the summary-only kernel
-  bool summary = false;
-  double* start_ray_vec = nullptr;
-  // fused deposition launch (with summary): the device block the kernel reads its binning arguments from
+  // KernelVariant::Deposit: the device block the kernel reads its binning arguments from
   const rays::DepTraceArgs* dep = nullptr;
 };
-int launch_trace(const rays_params_t* p, int nray, const double* d_rvec0, const double* d_rindex_vec0,
-                 double* d_ray_vec, double* d_residual, int32_t* d_npoints, int32_t* d_stop_code,
-                 double* d_end_ray_vec, double* d_end_residuals, double* d_max_residuals, hipStream_t stream,
-                 int flags, const TraceExtras& extra) {
+// variant: Recording (into `traj`), Summary or Deposit (no trajectory arrays; out.sv is optional).  out.ev, out.er and
+// out.mr are optional for a recording launch.
+int launch_trace(const rays_params_t* p, KernelVariant variant, int nray, const RayInputs& in,
+                 const TrajectoryArrays& traj, const SummaryArrays& out, hipStream_t stream, int flags,
+                 const TraceExtras& extra = TraceExtras()) {
   const size_t npt = (size_t)p->nstep_max + 1;
-  if (!extra.summary && !(flags & RAYS_TRACE_NO_ZERO_FILL)) {  // ray_results_m.f90:154-164
-    HIP_TRY(hipMemsetAsync(d_ray_vec, 0, sizeof(double) * npt * (size_t)p->nv * (size_t)nray, stream));
-    HIP_TRY(hipMemsetAsync(d_residual, 0, sizeof(double) * npt * (size_t)nray, stream));
+  const bool recording = variant == KernelVariant::Recording;
+  if (recording && !(flags & RAYS_TRACE_NO_ZERO_FILL)) {  // ray_results_m.f90:154-164
+    HIP_TRY(hipMemsetAsync(traj.rv, 0, sizeof(double) * npt * (size_t)p->nv * (size_t)nray, stream));
+    HIP_TRY(hipMemsetAsync(traj.res, 0, sizeof(double) * npt * (size_t)nray, stream));
   }
   unsigned int* counter = nullptr;
   int counter_slot = 0;
@@ -691,15 +680,15 @@ int launch_trace(const rays_params_t* p, int nray, const double* d_rvec0, const 
   HIP_TRY(hipMemsetAsync(counter, 0, sizeof(unsigned int), stream));
   rays::TraceArgs A;
   A.nray = nray;
-  A.rvec0 = d_rvec0;
-  A.rindex_vec0 = d_rindex_vec0;
-  A.ray_vec = d_ray_vec;
-  A.residual = d_residual;
-  A.npoints = d_npoints;
-  A.stop_code = d_stop_code;
-  A.end_ray_vec = d_end_ray_vec;
-  A.end_residuals = d_end_residuals;
-  A.max_residuals = d_max_residuals;
+  A.rvec0 = in.rvec0;
+  A.rindex_vec0 = in.rindex_vec0;
+  A.ray_vec = recording ? traj.rv : nullptr;
+  A.residual = recording ? traj.res : nullptr;
+  A.npoints = out.np;
+  A.stop_code = out.sc;
+  A.end_ray_vec = out.ev;
+  A.end_residuals = out.er;
+  A.max_residuals = out.mr;
   A.next_ray = counter;
   A.v0 = extra.v0;
   A.s0 = extra.s0;
@@ -709,12 +698,13 @@ int launch_trace(const rays_params_t* p, int nray, const double* d_rvec0, const 
   A.sg_far_lanes = 0;
   A.sched = nullptr;
   A.sched_stride = 0;
-  A.set_start_ray_vec(extra.start_ray_vec);
-  if (extra.dep) A.set_dep(extra.dep);
-  const rays::KernelEntry* kernel = find_kernel(*p, nray, false, extra.summary, extra.dep != nullptr);
+  A.set_start_ray_vec(recording ? nullptr : out.sv);
+  if (variant == KernelVariant::Deposit) A.set_dep(extra.dep);
+  const rays::KernelEntry* kernel = find_kernel(*p, nray, variant);
   if (!kernel)
-    return fail(extra.dep ? "rays_hip: the fused deposition kernel of this configuration is not in this build"
-                          : "rays_hip: the summary-only kernel of this configuration is not in this build");
+    return fail(variant == KernelVariant::Deposit
+                    ? "rays_hip: the fused deposition kernel of this configuration is not in this build"
+                    : "rays_hip: the summary-only kernel of this configuration is not in this build");
   const int stride = kernel->solver == RAYS_ODE_RK4 ? sched_stride() : 0;
   if (stride > 1) {
     // more rays than one wave per SIMD holds (the kernel decides with the lanes it is launched with)
@@ -752,7 +742,7 @@ int launch_trace(const rays_params_t* p, int nray, const double* d_rvec0, const 
   // summaries, so they exist for such a launch whether or not the caller asked for them.
   const rays::KernelEntry* twin = nullptr;
   if ((kernel->eq & rays::kEqTol) && kernel->occ == 1) {  // (the two-waves build hands nothing over)
-    twin = find_kernel(*p, 0, true);
+    twin = find_kernel(*p, 0, KernelVariant::ExactTwin);
     if (!twin || !twin->resume) return fail("rays_hip: the tolerance kernel's exact twin is not in this build");
     if (!A.end_ray_vec || !A.max_residuals) {
       double* ws = nullptr;
@@ -800,9 +790,9 @@ int rays_hip_trace_device(const rays_params_t* p, int nray, const double* d_rvec
   if (nray == 0) return 0;
   if (!d_rvec0 || !d_rindex_vec0 || !d_ray_vec || !d_residual || !d_npoints || !d_stop_code)
     return fail("rays_hip_trace_device: null device pointer");
-  return launch_trace(p, nray, d_rvec0, d_rindex_vec0, d_ray_vec, d_residual, d_npoints, d_stop_code,
-                      d_end_ray_vec, d_end_residuals, d_max_residuals, (hipStream_t)hip_stream, flags,
-                      TraceExtras());
+  return launch_trace(p, KernelVariant::Recording, nray, {d_rvec0, d_rindex_vec0}, {d_ray_vec, d_residual},
+                      {d_npoints, d_stop_code, nullptr, d_end_ray_vec, d_end_residuals, d_max_residuals},
+                      (hipStream_t)hip_stream, flags);
 }
 
 // ray_scan fused into one launch (ray_scan.f90:33-49, scanner_m.f90:174-205: scan_parameter = 'ds').
@@ -820,8 +810,9 @@ int rays_hip_scan_device(const rays_params_t* p, int n_runs, const double* d_ds_
   TraceExtras x;
   x.ds_run = d_ds_values;
   x.rays_per_run = nray;
-  return launch_trace(p, n_runs * nray, d_rvec0, d_rindex_vec0, d_ray_vec, d_residual, d_npoints, d_stop_code,
-                      d_end_ray_vec, d_end_residuals, d_max_residuals, (hipStream_t)hip_stream, flags, x);
+  return launch_trace(p, KernelVariant::Recording, n_runs * nray, {d_rvec0, d_rindex_vec0}, {d_ray_vec, d_residual},
+                      {d_npoints, d_stop_code, nullptr, d_end_ray_vec, d_end_residuals, d_max_residuals},
+                      (hipStream_t)hip_stream, flags, x);
 }
 
 // ---- summary-only tracing: ray ends and residual statistics, no trajectories (include/rays_hip.h) --------------------
@@ -835,11 +826,9 @@ int rays_hip_trace_summary_device(const rays_params_t* p, int nray, const double
   if (nray == 0) return 0;
   if (!d_rvec0 || !d_rindex_vec0 || !d_npoints || !d_stop_code || !d_end_ray_vec || !d_end_residuals || !d_max_residuals)
     return fail("rays_hip_trace_summary_device: null device pointer");
-  TraceExtras x;
-  x.summary = true;
-  x.start_ray_vec = d_start_ray_vec;
-  return launch_trace(p, nray, d_rvec0, d_rindex_vec0, nullptr, nullptr, d_npoints, d_stop_code, d_end_ray_vec,
-                      d_end_residuals, d_max_residuals, (hipStream_t)hip_stream, RAYS_TRACE_NO_ZERO_FILL, x);
+  return launch_trace(p, KernelVariant::Summary, nray, {d_rvec0, d_rindex_vec0}, {},
+                      {d_npoints, d_stop_code, d_start_ray_vec, d_end_ray_vec, d_end_residuals, d_max_residuals},
+                      (hipStream_t)hip_stream, RAYS_TRACE_NO_ZERO_FILL);
 }
 
 int rays_hip_scan_summary_device(const rays_params_t* p, int n_runs, const double* d_ds_values, int nray,
@@ -858,11 +847,9 @@ int rays_hip_scan_summary_device(const rays_params_t* p, int n_runs, const doubl
   TraceExtras x;
   x.ds_run = d_ds_values;
   x.rays_per_run = nray;
-  x.summary = true;
-  x.start_ray_vec = d_start_ray_vec;
-  return launch_trace(p, n_runs * nray, d_rvec0, d_rindex_vec0, nullptr, nullptr, d_npoints, d_stop_code,
-                      d_end_ray_vec, d_end_residuals, d_max_residuals, (hipStream_t)hip_stream,
-                      RAYS_TRACE_NO_ZERO_FILL, x);
+  return launch_trace(p, KernelVariant::Summary, n_runs * nray, {d_rvec0, d_rindex_vec0}, {},
+                      {d_npoints, d_stop_code, d_start_ray_vec, d_end_ray_vec, d_end_residuals, d_max_residuals},
+                      (hipStream_t)hip_stream, RAYS_TRACE_NO_ZERO_FILL, x);
 }
 
 // Batched `call ode_solver(eqn_ray, nv, v, s, sout, ray_stop)` (ode_m.f90:218-254) + the check_save that
@@ -912,7 +899,7 @@ int rays_hip_ode_step_device(const rays_params_t* p, int n, const double* d_v0, 
   x.v0 = d_v0;
   x.s0 = d_s0;
   // rvec0 / rindex_vec0 are not read when v0 is given; any valid pointer will do
-  rc = launch_trace(&q, n, d_v0, d_v0, d_rv, d_res, d_np, d_sc, d_ev, nullptr, nullptr, stream,
+  rc = launch_trace(&q, KernelVariant::Recording, n, {d_v0, d_v0}, {d_rv, d_res}, {d_np, d_sc, nullptr, d_ev}, stream,
                     RAYS_TRACE_NO_ZERO_FILL, x);
   if (rc) return rc;
   hipLaunchKernelGGL(rays::ode_step_collect_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, n, (int)nv, d_rv,
@@ -970,7 +957,7 @@ static void release_staging() {  // caller holds g_mu
 // padded ray_vec slab and its npoints on the device it traced on instead of giving them back to the block cache, and
 // rays_hip_deposition_last bins them in place: the trajectories cross PCIe once (to the caller's arrays), never back.
 struct KeptBlock {
-  int slot = -1, device = -1, r0 = 0, r1 = 0;
+  int slot = -1, dev = -1, r0 = 0, r1 = 0;
   double* d_ray_vec = nullptr;
   int32_t* d_npoints = nullptr;
 };
@@ -989,27 +976,56 @@ static void drop_kept_result() {  // caller holds no lock
   if (old.empty()) return;
   CurrentDevice restore;
   for (const KeptBlock& b : old) {
-    (void)hipSetDevice(b.device);
+    (void)hipSetDevice(b.dev);
     cached_free(b.slot, b.d_ray_vec);  // (freed, not cached, when the slot serves another device by now)
     cached_free(b.slot, b.d_npoints);
   }
 }
 
-// The trajectories of one block of rays_hip_trace: only the recorded points cross PCIe.
-// The device arrays that rays_hip_trace_device fills for a block of n rays.
-struct ResultArrays {
-  double *rv = nullptr, *res = nullptr, *ev = nullptr, *er = nullptr, *mr = nullptr;
-  int32_t *np = nullptr, *sc = nullptr;
-  hipError_t alloc(DeviceBuffers& bufs, size_t n, size_t npt, size_t nv) {
-    hipError_t e = bufs.alloc(&rv, npt * nv * n);
-    if (e == hipSuccess) e = bufs.alloc(&res, npt * n);
-    if (e == hipSuccess) e = bufs.alloc(&np, n);
-    if (e == hipSuccess) e = bufs.alloc(&sc, n);
-    if (e == hipSuccess) e = bufs.alloc(&ev, nv * n);
-    if (e == hipSuccess) e = bufs.alloc(&er, n);
-    return e == hipSuccess ? bufs.alloc(&mr, n) : e;
+// ---- the block driver of the sharded entries (rays_hip_trace, _summary, _deposition, _gather) ------------------------
+// The device list of a call: the slots of rays_hip_init[_devices], initialised lazily with every visible device.
+// *explicit_list: the list came from rays_hip_init_devices.  0, or 3 when no device can be had.
+extern "C++" {
+static int call_devices(std::vector<int>* devs, bool* explicit_list = nullptr) {
+  const auto snapshot = [&] {
+    std::lock_guard<std::mutex> lk(g_mu);
+    *devs = g_devices;
+    if (explicit_list) *explicit_list = g_devices_explicit;
+    return !devs->empty();
+  };
+  return snapshot() || (rays_hip_init(0) >= 0 && snapshot()) ? 0 : 3;
+}
+
+// Cuts [0, nray) into one contiguous block per slot of `devs`, like the reference's OpenMP schedule(static)
+// (ray_tracing.f90:62), builds the blocks in `blk`, runs work(block) for each on a host thread of its own and joins
+// them.  The first failing block in block order is the one reported.  The blocks stay with the caller, who may go on
+// using their streams and buffers; they drain and release themselves when `blk` goes out of scope (RayBlock).
+template <class Block, class Work>
+static int run_blocks(const std::vector<int>& devs, int nray, std::deque<Block>* blk, Work work) {
+  const int G = (int)devs.size();
+  const int per = (nray + G - 1) / G;
+  for (int g = 0; g < G; g++) {
+    blk->emplace_back(g);
+    Block& b = blk->back();
+    b.dev = devs[g];
+    b.r0 = std::min(nray, g * per);
+    b.r1 = std::min(nray, (g + 1) * per);
   }
-};
+  std::vector<std::thread> th;
+  for (Block& b : *blk)
+    th.emplace_back([&work, &b] {
+      b.rc = work(b);
+      if (b.rc) b.err = g_err;  // (the message is this worker thread's)
+    });
+  for (auto& t : th) t.join();
+  for (const Block& b : *blk)
+    if (b.rc) {
+      g_err = b.err;
+      return b.rc;
+    }
+  return 0;
+}
+}  // extern "C++"
 
 // The padded arrays are ~80 % zeros (a ray uses npoints of nstep_max+1 slots; 4.7 GB for the 64k
 // fan, 0.82 GB of it data).  Pack on the device, copy the packed block through two pinned
@@ -1017,10 +1033,14 @@ struct ResultArrays {
 // chunk is in flight.  Entries past npoints are not written: like the reference's trace_rays,
 // which relies on initialize_ray_results_m having zero-filled the arrays (ray_results_m.f90:
 // 154-164), this entry leaves them as the caller passed them.
-// npoints: the block's counts on the host; ray_vec, residual: the block's slabs of the caller's arrays.
-static int copy_packed_to_host(int slot, const rays_params_t* p, int n, const int32_t* npoints, int32_t* d_np,
-                               double* d_rv, double* d_res, double* ray_vec, double* residual, hipStream_t st) {
+// npoints: the block's counts on the host; host: the block's slabs of the caller's arrays.
+static int copy_packed_to_host(const RayBlock& B, const rays_params_t* p, const int32_t* npoints,
+                               const TrajectoryArrays& d, const TrajectoryArrays& host) {
   const size_t npt = (size_t)p->nstep_max + 1, nv = (size_t)p->nv;
+  const int slot = B.slot, n = B.n();
+  const hipStream_t st = B.st();
+  int32_t* const d_np = B.d.np;
+  double *const d_rv = d.rv, *const d_res = d.res, *const ray_vec = host.rv, *const residual = host.res;
   std::vector<long long> offs((size_t)n + 1);
   offs[0] = 0;
   for (int i = 0; i < n; i++) offs[(size_t)i + 1] = offs[i] + (npoints[i] > 0 ? npoints[i] : 0);
@@ -1086,11 +1106,9 @@ static int copy_packed_to_host(int slot, const rays_params_t* p, int n, const in
 }
 
 // One device's share of rays_hip_trace: rays [r0, r1) -> contiguous slabs of the host arrays.
-static int trace_block_on_device(int slot, int dev, const rays_params_t* p, int r0, int r1, const double* rvec0,
-                                 const double* rindex_vec0, double* ray_vec, double* residual,
-                                 int32_t* npoints, int32_t* stop_code, double* end_ray_vec,
-                                 double* end_residuals, double* max_residuals) {
-  const int n = r1 - r0;
+static int trace_block_on_device(RayBlock& B, const rays_params_t* p, const RayInputs& in, const TrajectoryArrays& traj,
+                                 const SummaryArrays& out) {
+  const int n = B.n(), r0 = B.r0;
   if (n <= 0) return 0;
   const size_t npt = (size_t)p->nstep_max + 1, nv = (size_t)p->nv;
   const bool timing = std::getenv("RAYS_HIP_TIMING") != nullptr;  // phase times of this entry on stderr
@@ -1098,53 +1116,43 @@ static int trace_block_on_device(int slot, int dev, const rays_params_t* p, int 
   auto lap = [&](const char* what) {
     if (!timing) return;
     const auto now = std::chrono::steady_clock::now();
-    std::fprintf(stderr, "[rays_hip_trace dev %d] %-28s %8.2f ms\n", dev, what,
+    std::fprintf(stderr, "[rays_hip_trace dev %d] %-28s %8.2f ms\n", B.dev, what,
                  std::chrono::duration<double, std::milli>(now - t_prev).count());
     t_prev = now;
   };
-  HIP_TRY(hipSetDevice(dev));
-  claim_slot_for_device(slot, dev);
-  SlotStream stream;
-  HIP_TRY_AS("hipStreamCreate", stream.open(slot));
-  const hipStream_t st = stream.get();
+  HIP_TRY_AS("hipSetDevice / hipStreamCreate", B.open());
+  const hipStream_t st = B.st();
   lap("stream");
-  DeviceBuffers bufs(slot);
-  double *d_r = nullptr, *d_n = nullptr;
-  ResultArrays d;
-  HIP_TRY_AS("hipMalloc(&d_r)", bufs.alloc(&d_r, 3 * (size_t)n));
-  HIP_TRY_AS("hipMalloc(&d_n)", bufs.alloc(&d_n, 3 * (size_t)n));
-  HIP_TRY_AS("hipMalloc (result arrays)", d.alloc(bufs, (size_t)n, npt, nv));
+  TrajectoryArrays d;
+  HIP_TRY_AS("hipMalloc (result arrays)", d.alloc(B.bufs, (size_t)n, npt, nv));
+  HIP_TRY_AS("hipMalloc (result arrays)", B.d.alloc(B.bufs, (size_t)n, nv, false));
   lap("device allocations");
-  HIP_TRY(hipMemcpyAsync(d_r, rvec0 + 3 * (size_t)r0, sizeof(double) * 3 * n, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(d_n, rindex_vec0 + 3 * (size_t)r0, sizeof(double) * 3 * n, hipMemcpyHostToDevice, st));
+  HIP_TRY_AS("hipMalloc / hipMemcpyAsync (block inputs)", B.upload(in));
   // no zero-fill of the device arrays: only recorded points are read back
-  int rc = rays_hip_trace_device(p, n, d_r, d_n, d.rv, d.res, d.np, d.sc, d.ev, d.er, d.mr, st, RAYS_TRACE_NO_ZERO_FILL);
+  int rc = launch_trace(p, KernelVariant::Recording, n, B.in, d, B.d, st, RAYS_TRACE_NO_ZERO_FILL);
   if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(npoints + r0, d.np, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(out.np + r0, B.d.np, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   lap("inputs + trace kernel");
-  rc = copy_packed_to_host(slot, p, n, npoints + r0, d.np, d.rv, d.res, ray_vec + npt * nv * (size_t)r0,
-                           residual + npt * (size_t)r0, st);
+  rc = copy_packed_to_host(B, p, out.np + r0, d, {traj.rv + npt * nv * (size_t)r0, traj.res + npt * (size_t)r0});
   lap("pack + copy + host scatter");
   if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(stop_code + r0, d.sc, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
-  if (end_ray_vec)
-    HIP_TRY(hipMemcpyAsync(end_ray_vec + nv * (size_t)r0, d.ev, sizeof(double) * nv * n, hipMemcpyDeviceToHost, st));
-  if (end_residuals) HIP_TRY(hipMemcpyAsync(end_residuals + r0, d.er, sizeof(double) * n, hipMemcpyDeviceToHost, st));
-  if (max_residuals) HIP_TRY(hipMemcpyAsync(max_residuals + r0, d.mr, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+  SummaryArrays rest = out;  // (npoints is there already)
+  rest.np = nullptr;
+  HIP_TRY_AS("hipMemcpyAsync (summaries)", B.download(rest, nv));
   HIP_TRY(hipStreamSynchronize(st));
   lap("summaries");
   {
     std::lock_guard<std::mutex> lk(g_mu);
     if (g_kept.keep) {  // the slab and its counts stay on the device: theirs is the kept result now
       KeptBlock b;
-      b.slot = slot; b.device = dev; b.r0 = r0; b.r1 = r1;
-      b.d_ray_vec = bufs.detach(d.rv);
-      b.d_npoints = bufs.detach(d.np);
+      b.slot = B.slot; b.dev = B.dev; b.r0 = B.r0; b.r1 = B.r1;
+      b.d_ray_vec = B.bufs.detach(d.rv);
+      b.d_npoints = B.bufs.detach(B.d.np);
       g_kept.blocks.push_back(b);
     }
   }
-  bufs.release();
+  B.bufs.release();
   lap("device frees");
   return 0;
 }
@@ -1159,25 +1167,13 @@ int rays_hip_trace(const rays_params_t* p, int nray, const double* rvec0, const 
   if (nray > 0 && (!rvec0 || !rindex_vec0 || !ray_vec || !residual || !npoints || !stop_code))
     return fail("rays_hip_trace: null array argument");
   std::vector<int> devs;
-  {
-    std::lock_guard<std::mutex> lk(g_mu);
-    devs = g_devices;
-  }
-  if (devs.empty()) {
-    if (rays_hip_init(0) < 0) return 3;
-    std::lock_guard<std::mutex> lk(g_mu);
-    devs = g_devices;
-  }
+  bool explicit_list = false;
+  if (call_devices(&devs, &explicit_list)) return 3;
   {
     // Large fans: several slots per device, so that one slot's packed device-to-host copy (what bounds this
     // entry: 0.8 GB at ~50 GB/s for the 64k fan) runs while the other slots still trace.  Measured on the 64k
     // fan: 22.0 ms with one slot, 20.9 / 18.8 / 21.0 ms with 2 / 4 / 8.  RAYS_HIP_SLOTS_PER_DEVICE overrides;
     // a list given through rays_hip_init_devices is taken as it is.
-    bool explicit_list;
-    {
-      std::lock_guard<std::mutex> lk(g_mu);
-      explicit_list = g_devices_explicit;
-    }
     int k = (long long)nray >= 32768ll * (long long)devs.size() ? 4 : 1;
     if (const char* e = std::getenv("RAYS_HIP_SLOTS_PER_DEVICE")) k = std::atoi(e);
     while (k > 1 && (size_t)k * devs.size() > (size_t)kMaxDevices) k--;
@@ -1190,27 +1186,15 @@ int rays_hip_trace(const rays_params_t* p, int nray, const double* rvec0, const 
   }
   drop_kept_result();  // the image of an earlier call (if any) goes back to the block cache
   const auto t0 = std::chrono::steady_clock::now();
-  const int G = (int)devs.size();
-  // contiguous blocks, like the reference's OpenMP schedule(static) (ray_tracing.f90:62)
-  const int per = (nray + G - 1) / G;
-  std::vector<int> rcs(G, 0);
-  std::vector<std::string> errs(G);
-  std::vector<std::thread> th;
-  for (int g = 0; g < G; g++) {
-    const int r0 = std::min(nray, g * per), r1 = std::min(nray, (g + 1) * per);
-    th.emplace_back([&, g, r0, r1] {
-      rcs[g] = trace_block_on_device(g, devs[g], p, r0, r1, rvec0, rindex_vec0, ray_vec, residual, npoints,
-                                     stop_code, end_ray_vec, end_residuals, max_residuals);
-      if (rcs[g]) errs[g] = g_err;  // (the message is this worker thread's)
-    });
+  std::deque<RayBlock> blk;
+  rc = run_blocks(devs, nray, &blk, [&](RayBlock& B) {
+    return trace_block_on_device(B, p, {rvec0, rindex_vec0}, {ray_vec, residual},
+                                 {npoints, stop_code, nullptr, end_ray_vec, end_residuals, max_residuals});
+  });
+  if (rc) {
+    drop_kept_result();
+    return rc;
   }
-  for (auto& t : th) t.join();
-  for (int g = 0; g < G; g++)
-    if (rcs[g]) {
-      g_err = errs[g];
-      drop_kept_result();
-      return rcs[g];
-    }
   {
     std::lock_guard<std::mutex> lk(g_mu);
     if (g_kept.keep) {
@@ -1225,48 +1209,9 @@ int rays_hip_trace(const rays_params_t* p, int nray, const double* rvec0, const 
   return 0;
 }
 
-// One device's share of rays_hip_trace_summary: rays [r0, r1); only the summaries exist on the device and cross PCIe.
-static int summary_block_on_device(int slot, int dev, const rays_params_t* p, int r0, int r1, const double* rvec0,
-                                   const double* rindex_vec0, int32_t* npoints, int32_t* stop_code,
-                                   double* start_ray_vec, double* end_ray_vec, double* end_residuals,
-                                   double* max_residuals) {
-  const int n = r1 - r0;
-  if (n <= 0) return 0;
-  const size_t nv = (size_t)p->nv, N = (size_t)n;
-  HIP_TRY(hipSetDevice(dev));
-  claim_slot_for_device(slot, dev);
-  SlotStream stream;
-  HIP_TRY_AS("hipStreamCreate", stream.open(slot));
-  const hipStream_t st = stream.get();
-  DeviceBuffers bufs(slot);
-  double *d_r = nullptr, *d_n = nullptr, *d_sv = nullptr, *d_ev = nullptr, *d_er = nullptr, *d_mr = nullptr;
-  int32_t *d_np = nullptr, *d_sc = nullptr;
-  HIP_TRY_AS("hipMalloc(&d_r)", bufs.alloc(&d_r, 3 * N));
-  HIP_TRY_AS("hipMalloc(&d_n)", bufs.alloc(&d_n, 3 * N));
-  HIP_TRY_AS("hipMalloc(&d_np)", bufs.alloc(&d_np, N));
-  HIP_TRY_AS("hipMalloc(&d_sc)", bufs.alloc(&d_sc, N));
-  if (start_ray_vec) HIP_TRY_AS("hipMalloc(&d_sv)", bufs.alloc(&d_sv, nv * N));
-  HIP_TRY_AS("hipMalloc(&d_ev)", bufs.alloc(&d_ev, nv * N));
-  HIP_TRY_AS("hipMalloc(&d_er)", bufs.alloc(&d_er, N));
-  HIP_TRY_AS("hipMalloc(&d_mr)", bufs.alloc(&d_mr, N));
-  HIP_TRY(hipMemcpyAsync(d_r, rvec0 + 3 * (size_t)r0, sizeof(double) * 3 * N, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(d_n, rindex_vec0 + 3 * (size_t)r0, sizeof(double) * 3 * N, hipMemcpyHostToDevice, st));
-  int rc = rays_hip_trace_summary_device(p, n, d_r, d_n, d_np, d_sc, d_sv, d_ev, d_er, d_mr, st);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(npoints + r0, d_np, sizeof(int32_t) * N, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(stop_code + r0, d_sc, sizeof(int32_t) * N, hipMemcpyDeviceToHost, st));
-  if (start_ray_vec)
-    HIP_TRY(hipMemcpyAsync(start_ray_vec + nv * (size_t)r0, d_sv, sizeof(double) * nv * N, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(end_ray_vec + nv * (size_t)r0, d_ev, sizeof(double) * nv * N, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(end_residuals + r0, d_er, sizeof(double) * N, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(max_residuals + r0, d_mr, sizeof(double) * N, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  bufs.release();
-  return 0;
-}
-
 // The host form of summary-only tracing: sharded like rays_hip_trace (contiguous blocks, one thread per device of
-// rays_hip_init[_devices]; one slot per device -- there is no large copy for further slots to overlap).
+// rays_hip_init[_devices]; one slot per device -- there is no large copy for further slots to overlap).  Only the
+// summaries exist on the device and cross PCIe.
 int rays_hip_trace_summary(const rays_params_t* p, int nray, const double* rvec0, const double* rindex_vec0,
                            int32_t* npoints, int32_t* stop_code, double* start_ray_vec, double* end_ray_vec,
                            double* end_residuals, double* max_residuals, double* elapsed_s) {
@@ -1276,36 +1221,24 @@ int rays_hip_trace_summary(const rays_params_t* p, int nray, const double* rvec0
   if (nray > 0 && (!rvec0 || !rindex_vec0 || !npoints || !stop_code || !end_ray_vec || !end_residuals || !max_residuals))
     return fail("rays_hip_trace_summary: null array argument");
   std::vector<int> devs;
-  {
-    std::lock_guard<std::mutex> lk(g_mu);
-    devs = g_devices;
-  }
-  if (devs.empty()) {
-    if (rays_hip_init(0) < 0) return 3;
-    std::lock_guard<std::mutex> lk(g_mu);
-    devs = g_devices;
-  }
+  if (call_devices(&devs)) return 3;
   drop_kept_result();  // the image of an earlier rays_hip_trace (if any) is not this call's result: it goes back
   const auto t0 = std::chrono::steady_clock::now();
-  const int G = (int)devs.size();
-  const int per = (nray + G - 1) / G;
-  std::vector<int> rcs(G, 0);
-  std::vector<std::string> errs(G);
-  std::vector<std::thread> th;
-  for (int g = 0; g < G; g++) {
-    const int r0 = std::min(nray, g * per), r1 = std::min(nray, (g + 1) * per);
-    th.emplace_back([&, g, r0, r1] {
-      rcs[g] = summary_block_on_device(g, devs[g], p, r0, r1, rvec0, rindex_vec0, npoints, stop_code, start_ray_vec,
-                                       end_ray_vec, end_residuals, max_residuals);
-      if (rcs[g]) errs[g] = g_err;  // (the message is this worker thread's)
-    });
-  }
-  for (auto& t : th) t.join();
-  for (int g = 0; g < G; g++)
-    if (rcs[g]) {
-      g_err = errs[g];
-      return rcs[g];
-    }
+  const SummaryArrays out = {npoints, stop_code, start_ray_vec, end_ray_vec, end_residuals, max_residuals};
+  std::deque<RayBlock> blk;
+  rc = run_blocks(devs, nray, &blk, [&](RayBlock& B) {
+    if (B.n() <= 0) return 0;
+    HIP_TRY_AS("hipSetDevice / hipStreamCreate", B.open());
+    HIP_TRY_AS("hipMalloc (result arrays)", B.d.alloc(B.bufs, (size_t)B.n(), (size_t)p->nv, start_ray_vec != nullptr));
+    HIP_TRY_AS("hipMalloc / hipMemcpyAsync (block inputs)", B.upload({rvec0, rindex_vec0}));
+    const int rc_b = launch_trace(p, KernelVariant::Summary, B.n(), B.in, {}, B.d, B.st(), RAYS_TRACE_NO_ZERO_FILL);
+    if (rc_b) return rc_b;
+    HIP_TRY_AS("hipMemcpyAsync (summaries)", B.download(out, (size_t)p->nv));
+    HIP_TRY(hipStreamSynchronize(B.st()));
+    B.bufs.release();
+    return 0;
+  });
+  if (rc) return rc;
   if (elapsed_s)
     *elapsed_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   return 0;
@@ -1342,10 +1275,6 @@ int rays_hip_unpack_device(int nray, int nv, int nstep_max, const int32_t* d_npo
   return e == hipSuccess ? 0 : hip_fail(e, "rays_hip_unpack_device");
 }
 
-// Diagnostic entry (tests): evaluate the RHS pieces at n states on the current device.
-// v[n][nv] host; outputs host: cold7[n][7], num7[n][7], dvds[n][nv], resid[n], codes[n][4]
-// (codes: equilibrium err, eqn_ray stop code, check_save flag, check_save stop_ode).
-
 int rays_hip_set_rho_table(const double* grid, const double* fspl, int n) {
   if (!grid || !fspl || n < 2) return fail("rays_hip_set_rho_table: bad table");
   std::lock_guard<std::mutex> lk(g_mu);
@@ -1364,43 +1293,49 @@ static int refuse_bin_count(int n_bins) {
   return 0;
 }
 
-int rays_hip_deposition_device(const rays_params_t* p, int which, int n_bins, int nray, const double* d_ray_vec,
-                               const int32_t* d_npoints, const double* d_initial_ray_power, double* d_work,
-                               const double* d_profile_in, double* d_profile_out, void* hip_stream) {
+// What a deposition may be asked for: rays_hip_check_params, then the checks rays_hip_deposition_device and the fused
+// entries share.  `who` names the entry in the messages of its own; `fused` selects the fused entries' wording and
+// order (their nray and bin count checks; rays_hip_deposition_device checks its own, behind these).
+static int refuse_deposition(const char* who, bool fused, const rays_params_t* p, int nray, int which, int n_bins) {
   int rc = rays_hip_check_params(p);
   if (rc) return rc;
+  const std::string w(who);
+  if (fused && nray < 0) return fail(w + ": nray < 0");
   if (p->equilib_model != RAYS_EQ_AXISYM && p->equilib_model != RAYS_EQ_SLAB)  // deposition_profiles_m.f90:129-222
     return fail("initialize_deposition_profiles: unimplemented equilib_model");
   if (p->nv < 8 || p->damping_model == RAYS_DAMP_NONE)
-    return fail("rays_hip_deposition: needs a run with damping (ray_vec(8) = absorbed power fraction)");
+    return fail(w + ": needs a run with damping (ray_vec(8) = absorbed power fraction)");
   if (p->equilib_model == RAYS_EQ_AXISYM && p->axisym.magnetics_model != RAYS_AXI_MAG_EQDSK_SPLINE && which == RAYS_DEP_PTOTAL_RHO)
     return fail("axisym_toroid_rho: rho is only implemented for eqdsk_magnetics_spline_interp");  // axisym_toroid_eq_m.f90:398-430
   if (p->equilib_model == RAYS_EQ_SLAB ? which != RAYS_DEP_PTOTAL_X
                                        : (which != RAYS_DEP_PTOTAL_PSI && which != RAYS_DEP_PTOTAL_RHO))
     return fail("initialize_deposition_profiles: unimplemented profile for this equilib_model");  // :162-169, 204-212
-  if (n_bins < 1 || nray < 0) return fail("rays_hip_deposition: bad n_bins / nray");
-  if (refuse_bin_count(n_bins)) return 1;
+  if (!fused) {
+    if (n_bins < 1 || nray < 0) return fail("rays_hip_deposition: bad n_bins / nray");
+    return refuse_bin_count(n_bins);
+  }
+  if (n_bins < 1 || n_bins > RAYS_DEP_MAX_BINS)
+    return fail(w + ": n_bins = " + std::to_string(n_bins) + " is outside 1.." + std::to_string(RAYS_DEP_MAX_BINS) +
+                " (RAYS_DEP_MAX_BINS)");
+  return 0;
+}
+
+int rays_hip_deposition_device(const rays_params_t* p, int which, int n_bins, int nray, const double* d_ray_vec,
+                               const int32_t* d_npoints, const double* d_initial_ray_power, double* d_work,
+                               const double* d_profile_in, double* d_profile_out, void* hip_stream) {
+  int rc = refuse_deposition("rays_hip_deposition", false, p, nray, which, n_bins);
+  if (rc) return rc;
   if (!d_ray_vec || !d_npoints || !d_initial_ray_power || !d_work || !d_profile_out)
     return fail("rays_hip_deposition: null device pointer");
-  rays::DevParams D = make_dev_params(*p);
-  if (p->equilib_model == RAYS_EQ_AXISYM) {
-    rc = get_axisym_device(&D);
-    if (rc) return rc;
-  }
+  rays::DevParams D;
+  rc = dev_params_with_axisym(p, &D);
+  if (rc) return rc;
   rays::DepArgs A;
   A.which = which;
   A.n_bins = n_bins; A.nray = nray; A.nv = p->nv; A.npt = p->nstep_max + 1;
-  A.grid_min = 0.0; A.grid_max = 1.0;  // :176-177
-  if (which == RAYS_DEP_PTOTAL_X) { A.grid_min = p->slab.xmin; A.grid_max = p->slab.xmax; }  // :136-137
   A.ray_vec = d_ray_vec; A.npoints = d_npoints; A.power = d_initial_ray_power; A.work = d_work;
-  A.rho_grid = nullptr; A.rho_fspl = nullptr; A.n_rho = 0;
-  if (which == RAYS_DEP_PTOTAL_RHO) {
-    const double* t = nullptr;
-    int n = 0;
-    rc = get_rho_device(&t, &n);
-    if (rc) return rc;
-    A.rho_grid = t; A.rho_fspl = t + n; A.n_rho = n;
-  }
+  rc = fill_deposition_grid(p, which, &A);
+  if (rc) return rc;
   hipError_t e = rays::launch_deposition(D, A, d_profile_in, d_profile_out, (hipStream_t)hip_stream);
   if (e != hipSuccess) return hip_fail(e, "deposition kernels");
   return 0;
@@ -1464,9 +1399,34 @@ int rays_hip_deposition(const rays_params_t* p, int which, int n_bins, int nray,
   return 0;
 }
 
+// The ray-ordered carry of the profiles of a call's blocks: blocks are binned in ray order, each continuing the running
+// sums of the one before it (rays_hip_deposition_device's d_profile_in), so the profile is the reference's ray-ordered
+// sum bit for bit, whatever the number of blocks / devices.  sum_block(block, scratch, carry_in, carry_out, &d_work), on
+// the block's device: sums the block's rows onto carry_in (host; null for the first block) into carry_out (host), returns
+// when carry_out is there, and names the block's work[n_bins][n] on the device; `scratch` lives until work is copied.
+extern "C++" {
+template <class Blocks, class SumBlock>
+static int chain_profiles(Blocks& blocks, int n_bins, double* work, double* profile, SumBlock sum_block) {
+  std::vector<double> carry((size_t)n_bins, 0.0), wbuf;
+  bool have_carry = false;
+  CurrentDevice restore;
+  for (auto& b : blocks) {
+    const int n = b.r1 - b.r0;
+    if (n <= 0) continue;
+    HIP_TRY(hipSetDevice(b.dev));
+    DeviceBuffers scratch;
+    const double* d_work = nullptr;
+    const int rc = sum_block(b, scratch, have_carry ? carry.data() : nullptr, carry.data(), &d_work);
+    if (rc) return rc;
+    have_carry = true;
+    if (work) HIP_TRY_AS("hipMemcpy (work)", work_to_host(d_work, n_bins, n, work + (size_t)b.r0 * n_bins, &wbuf));
+  }
+  std::memcpy(profile, carry.data(), sizeof(double) * (size_t)n_bins);
+  return 0;
+}
+}  // extern "C++"
+
 // The deposition profiles of the rays the last rays_hip_trace call traced, binned where they lie (see KeptResult).
-// Blocks are binned in ray order, each continuing the running sums of the one before it (rays_hip_deposition_device's
-// d_profile_in): the profile is the reference's ray-ordered sum bit for bit, whatever the number of blocks / devices.
 int rays_hip_deposition_last(const rays_params_t* p, int which, int n_bins, int nray, const double* initial_ray_power,
                              double* work, double* profile) {
   int rc = rays_hip_check_params(p);
@@ -1485,30 +1445,26 @@ int rays_hip_deposition_last(const rays_params_t* p, int which, int n_bins, int 
   }
   const bool timing = std::getenv("RAYS_HIP_TIMING") != nullptr;
   const auto t0 = std::chrono::steady_clock::now();
-  std::vector<double> carry((size_t)n_bins, 0.0), wbuf;
-  bool have_carry = false;
-  CurrentDevice restore;
-  for (const KeptBlock& b : blocks) {
+  const size_t B = (size_t)n_bins;
+  rc = chain_profiles(blocks, n_bins, work, profile, [&](const KeptBlock& b, DeviceBuffers& bufs, const double* carry_in,
+                                                         double* carry_out, const double** d_work_out) {
     const int n = b.r1 - b.r0;
-    if (n <= 0) continue;
-    HIP_TRY(hipSetDevice(b.device));
-    DeviceBuffers bufs;
     double *d_pw = nullptr, *d_work = nullptr, *d_in = nullptr, *d_out = nullptr;
     HIP_TRY_AS("hipMalloc(&d_pw)", bufs.alloc(&d_pw, (size_t)n));
-    HIP_TRY_AS("hipMalloc(&d_work)", bufs.alloc(&d_work, (size_t)n_bins * (size_t)n));
-    HIP_TRY_AS("hipMalloc(&d_in)", bufs.alloc(&d_in, (size_t)n_bins));
-    HIP_TRY_AS("hipMalloc(&d_out)", bufs.alloc(&d_out, (size_t)n_bins));
+    HIP_TRY_AS("hipMalloc(&d_work)", bufs.alloc(&d_work, B * (size_t)n));
+    HIP_TRY_AS("hipMalloc(&d_in)", bufs.alloc(&d_in, B));
+    HIP_TRY_AS("hipMalloc(&d_out)", bufs.alloc(&d_out, B));
     HIP_TRY(hipMemcpy(d_pw, initial_ray_power + b.r0, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
-    if (have_carry) HIP_TRY(hipMemcpy(d_in, carry.data(), sizeof(double) * (size_t)n_bins, hipMemcpyHostToDevice));
-    rc = rays_hip_deposition_device(p, which, n_bins, n, b.d_ray_vec, b.d_npoints, d_pw, d_work, have_carry ? d_in : nullptr,
-                                    d_out, nullptr);
-    if (rc) return rc;
+    if (carry_in) HIP_TRY(hipMemcpy(d_in, carry_in, sizeof(double) * B, hipMemcpyHostToDevice));
+    const int rc_b = rays_hip_deposition_device(p, which, n_bins, n, b.d_ray_vec, b.d_npoints, d_pw, d_work,
+                                                carry_in ? d_in : nullptr, d_out, nullptr);
+    if (rc_b) return rc_b;
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(carry.data(), d_out, sizeof(double) * (size_t)n_bins, hipMemcpyDeviceToHost));
-    have_carry = true;
-    if (work) HIP_TRY_AS("hipMemcpy (work)", work_to_host(d_work, n_bins, n, work + (size_t)b.r0 * n_bins, &wbuf));
-  }
-  std::memcpy(profile, carry.data(), sizeof(double) * (size_t)n_bins);
+    HIP_TRY(hipMemcpy(carry_out, d_out, sizeof(double) * B, hipMemcpyDeviceToHost));
+    *d_work_out = d_work;
+    return 0;
+  });
+  if (rc) return rc;
   if (timing)
     std::fprintf(stderr, "[rays_hip_deposition_last] %d rays in %zu device-resident block(s), no trajectory upload: %.2f ms\n",
                  nray, blocks.size(), std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
@@ -1518,67 +1474,36 @@ int rays_hip_deposition_last(const rays_params_t* p, int which, int n_bins, int 
 // ---- fused trace and deposition: the absorbed-power profile without trajectories (include/rays_hip.h) ---------------
 // What the entries refuse before anything is allocated or launched; `who` names the entry in the messages of its own.
 static int refuse_trace_deposition(const char* who, const rays_params_t* p, int nray, int which, int n_bins) {
-  int rc = rays_hip_check_params(p);
+  int rc = refuse_deposition(who, true, p, nray, which, n_bins);
   if (rc) return rc;
-  const std::string w(who);
-  if (nray < 0) return fail(w + ": nray < 0");
-  if (p->equilib_model != RAYS_EQ_AXISYM && p->equilib_model != RAYS_EQ_SLAB)  // deposition_profiles_m.f90:129-222
-    return fail("initialize_deposition_profiles: unimplemented equilib_model");
-  if (p->nv < 8 || p->damping_model == RAYS_DAMP_NONE)
-    return fail(w + ": needs a run with damping (ray_vec(8) = absorbed power fraction)");
-  if (p->equilib_model == RAYS_EQ_AXISYM && p->axisym.magnetics_model != RAYS_AXI_MAG_EQDSK_SPLINE && which == RAYS_DEP_PTOTAL_RHO)
-    return fail("axisym_toroid_rho: rho is only implemented for eqdsk_magnetics_spline_interp");  // axisym_toroid_eq_m.f90:398-430
-  if (p->equilib_model == RAYS_EQ_SLAB ? which != RAYS_DEP_PTOTAL_X
-                                       : (which != RAYS_DEP_PTOTAL_PSI && which != RAYS_DEP_PTOTAL_RHO))
-    return fail("initialize_deposition_profiles: unimplemented profile for this equilib_model");  // :162-169, 204-212
-  if (n_bins < 1 || n_bins > RAYS_DEP_MAX_BINS)
-    return fail(w + ": n_bins = " + std::to_string(n_bins) + " is outside 1.." + std::to_string(RAYS_DEP_MAX_BINS) +
-                " (RAYS_DEP_MAX_BINS)");
   if (which == RAYS_DEP_PTOTAL_RHO) {
     std::lock_guard<std::mutex> lk(g_mu);
     if (g_rho.n < 2) return fail("Ptotal_rho needs rays_hip_set_rho_table() first");
   }
-  if (!find_kernel(*p, nray, false, true, true) || !rays::launch_dep_trace_args || !rays::launch_profile_sum)
-    return fail(w + ": the fused deposition kernel of this configuration is not in this build");
+  if (!find_kernel(*p, nray, KernelVariant::Deposit) || !rays::launch_dep_trace_args || !rays::launch_profile_sum)
+    return fail(std::string(who) + ": the fused deposition kernel of this configuration is not in this build");
   return 0;
 }
 
-// zero work, the DepTraceArgs block, the fused trace; `sum`: + the ray-ordered profile sum.  Arguments already checked.
-static int trace_deposition_launch(const rays_params_t* p, int nray, const double* d_rvec0, const double* d_rindex_vec0,
-                                   const double* d_power, int which, int n_bins, int32_t* d_npoints, int32_t* d_stop_code,
-                                   double* d_start_ray_vec, double* d_end_ray_vec, double* d_end_residuals,
-                                   double* d_max_residuals, double* d_work, const double* d_profile_in,
-                                   double* d_profile_out, hipStream_t stream, bool sum) {
+// zero work, the DepTraceArgs block, the fused trace (in.power: the rays' initial power).  Arguments already checked.
+static int trace_deposition_launch(const rays_params_t* p, int nray, const RayInputs& in, int which, int n_bins,
+                                   const SummaryArrays& out, double* d_work, hipStream_t stream) {
   rays::DepTraceArgs T;
   T.which = which;
   T.n_bins = n_bins;
-  T.grid_min = 0.0; T.grid_max = 1.0;  // deposition_profiles_m.f90:176-177
-  if (which == RAYS_DEP_PTOTAL_X) { T.grid_min = p->slab.xmin; T.grid_max = p->slab.xmax; }  // :136-137
-  T.power = d_power;
+  T.power = in.power;
   T.work = d_work;
-  T.rho_grid = nullptr; T.rho_fspl = nullptr; T.n_rho = 0; T.pad_ = 0;
-  if (which == RAYS_DEP_PTOTAL_RHO) {
-    const double* t = nullptr;
-    int n = 0;
-    int rc = get_rho_device(&t, &n);
-    if (rc) return rc;
-    T.rho_grid = t; T.rho_fspl = t + n; T.n_rho = n;
-  }
+  T.pad_ = 0;
+  int rc = fill_deposition_grid(p, which, &T);
+  if (rc) return rc;
   rays::DepTraceArgs* d_T = nullptr;
   HIP_TRY_AS("hipMalloc (deposition arguments)", g_dep_ws.get(stream, sizeof(rays::DepTraceArgs), (void**)&d_T));
   HIP_TRY(hipMemsetAsync(d_work, 0, sizeof(double) * (size_t)n_bins * (size_t)nray, stream));
   hipError_t e = rays::launch_dep_trace_args(T, d_T, stream);
   if (e != hipSuccess) return hip_fail(e, "deposition arguments kernel");
   TraceExtras x;
-  x.summary = true;
-  x.start_ray_vec = d_start_ray_vec;
   x.dep = d_T;
-  int rc = launch_trace(p, nray, d_rvec0, d_rindex_vec0, nullptr, nullptr, d_npoints, d_stop_code, d_end_ray_vec,
-                        d_end_residuals, d_max_residuals, stream, RAYS_TRACE_NO_ZERO_FILL, x);
-  if (rc || !sum) return rc;
-  e = rays::launch_profile_sum(n_bins, nray, d_work, d_profile_in, d_profile_out, stream);
-  if (e != hipSuccess) return hip_fail(e, "profile sum kernel");
-  return 0;
+  return launch_trace(p, KernelVariant::Deposit, nray, in, {}, out, stream, RAYS_TRACE_NO_ZERO_FILL, x);
 }
 
 int rays_hip_trace_deposition_device(const rays_params_t* p, int nray, const double* d_rvec0, const double* d_rindex_vec0,
@@ -1603,76 +1528,29 @@ int rays_hip_trace_deposition_device(const rays_params_t* p, int nray, const dou
   if (!d_rvec0 || !d_rindex_vec0 || !d_initial_ray_power || !d_npoints || !d_stop_code || !d_end_ray_vec ||
       !d_end_residuals || !d_max_residuals || !d_work)
     return fail("rays_hip_trace_deposition_device: null device pointer");
-  return trace_deposition_launch(p, nray, d_rvec0, d_rindex_vec0, d_initial_ray_power, which, n_bins, d_npoints,
-                                 d_stop_code, d_start_ray_vec, d_end_ray_vec, d_end_residuals, d_max_residuals, d_work,
-                                 d_profile_in, d_profile_out, stream, true);
+  rc = trace_deposition_launch(p, nray, {d_rvec0, d_rindex_vec0, d_initial_ray_power}, which, n_bins,
+                               {d_npoints, d_stop_code, d_start_ray_vec, d_end_ray_vec, d_end_residuals, d_max_residuals},
+                               d_work, stream);
+  if (rc) return rc;
+  // + the ray-ordered profile sum
+  const hipError_t e = rays::launch_profile_sum(n_bins, nray, d_work, d_profile_in, d_profile_out, stream);
+  if (e != hipSuccess) return hip_fail(e, "profile sum kernel");
+  return 0;
 }
 
 const char* rays_hip_deposition_kernel_name_for(const rays_params_t* p, int nray) {
   if (!p || rays_hip_check_params(p)) return "";
-  const rays::KernelEntry* k = find_kernel(*p, nray, false, true, true);
+  const rays::KernelEntry* k = find_kernel(*p, nray, KernelVariant::Deposit);
   return k ? k->name : "";
 }
 
 namespace {
-// One device's share of rays_hip_trace_deposition: rays [r0, r1) traced and binned; the summaries go to the caller's
-// arrays, work stays on the device (owned by `bufs`) until the blocks' profiles have been chained in ray order.
-struct DepositionBlock {
-  int slot = 0, dev = 0, r0 = 0, r1 = 0;
-  DeviceBuffers bufs;
+// A block of rays_hip_trace_deposition: work stays on the device (owned by the block's bufs) until the blocks' profiles
+// have been chained in ray order.
+struct DepositionBlock : RayBlock {
+  using RayBlock::RayBlock;
   double *d_work = nullptr, *d_in = nullptr, *d_out = nullptr;
-  hipStream_t st = nullptr;
-  explicit DepositionBlock(int s) : slot(s), bufs(s) {}
-  // however the call ends -- another block's worker failed, a copy of the chaining phase failed -- nothing of this block
-  // is still in flight when its buffers go back to the slot's cache (bufs is destroyed after this body)
-  ~DepositionBlock() {
-    if (!st) return;
-    CurrentDevice restore;
-    if (hipSetDevice(dev) == hipSuccess) (void)hipStreamSynchronize(st);
-  }
 };
-int deposition_block_on_device(DepositionBlock& B, const rays_params_t* p, const double* rvec0, const double* rindex_vec0,
-                               const double* power, int which, int n_bins, int32_t* npoints, int32_t* stop_code,
-                               double* start_ray_vec, double* end_ray_vec, double* end_residuals, double* max_residuals) {
-  const int r0 = B.r0, n = B.r1 - B.r0;
-  if (n <= 0) return 0;
-  const size_t nv = (size_t)p->nv, N = (size_t)n;
-  HIP_TRY(hipSetDevice(B.dev));
-  claim_slot_for_device(B.slot, B.dev);
-  SlotStream stream;
-  HIP_TRY_AS("hipStreamCreate", stream.open(B.slot));
-  const hipStream_t st = stream.get();
-  B.st = st;
-  double *d_r = nullptr, *d_n = nullptr, *d_pw = nullptr, *d_sv = nullptr, *d_ev = nullptr, *d_er = nullptr, *d_mr = nullptr;
-  int32_t *d_np = nullptr, *d_sc = nullptr;
-  HIP_TRY_AS("hipMalloc(&d_r)", B.bufs.alloc(&d_r, 3 * N));
-  HIP_TRY_AS("hipMalloc(&d_n)", B.bufs.alloc(&d_n, 3 * N));
-  HIP_TRY_AS("hipMalloc(&d_pw)", B.bufs.alloc(&d_pw, N));
-  HIP_TRY_AS("hipMalloc(&d_np)", B.bufs.alloc(&d_np, N));
-  HIP_TRY_AS("hipMalloc(&d_sc)", B.bufs.alloc(&d_sc, N));
-  if (start_ray_vec) HIP_TRY_AS("hipMalloc(&d_sv)", B.bufs.alloc(&d_sv, nv * N));
-  HIP_TRY_AS("hipMalloc(&d_ev)", B.bufs.alloc(&d_ev, nv * N));
-  HIP_TRY_AS("hipMalloc(&d_er)", B.bufs.alloc(&d_er, N));
-  HIP_TRY_AS("hipMalloc(&d_mr)", B.bufs.alloc(&d_mr, N));
-  HIP_TRY_AS("hipMalloc(&d_work)", B.bufs.alloc(&B.d_work, (size_t)n_bins * N));
-  HIP_TRY_AS("hipMalloc(&d_in)", B.bufs.alloc(&B.d_in, (size_t)n_bins));
-  HIP_TRY_AS("hipMalloc(&d_out)", B.bufs.alloc(&B.d_out, (size_t)n_bins));
-  HIP_TRY(hipMemcpyAsync(d_r, rvec0 + 3 * (size_t)r0, sizeof(double) * 3 * N, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(d_n, rindex_vec0 + 3 * (size_t)r0, sizeof(double) * 3 * N, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(d_pw, power + r0, sizeof(double) * N, hipMemcpyHostToDevice, st));
-  int rc = trace_deposition_launch(p, n, d_r, d_n, d_pw, which, n_bins, d_np, d_sc, d_sv, d_ev, d_er, d_mr, B.d_work,
-                                   nullptr, nullptr, st, false);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(npoints + r0, d_np, sizeof(int32_t) * N, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(stop_code + r0, d_sc, sizeof(int32_t) * N, hipMemcpyDeviceToHost, st));
-  if (start_ray_vec)
-    HIP_TRY(hipMemcpyAsync(start_ray_vec + nv * (size_t)r0, d_sv, sizeof(double) * nv * N, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(end_ray_vec + nv * (size_t)r0, d_ev, sizeof(double) * nv * N, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(end_residuals + r0, d_er, sizeof(double) * N, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(max_residuals + r0, d_mr, sizeof(double) * N, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  return 0;
-}
 }  // namespace
 
 // The host form: sharded like rays_hip_trace_summary (the devices of rays_hip_init[_devices], contiguous blocks, one
@@ -1690,65 +1568,39 @@ int rays_hip_trace_deposition(const rays_params_t* p, int nray, const double* rv
                    !end_residuals || !max_residuals))
     return fail("rays_hip_trace_deposition: null array argument");
   std::vector<int> devs;
-  {
-    std::lock_guard<std::mutex> lk(g_mu);
-    devs = g_devices;
-  }
-  if (devs.empty()) {
-    if (rays_hip_init(0) < 0) return 3;
-    std::lock_guard<std::mutex> lk(g_mu);
-    devs = g_devices;
-  }
+  if (call_devices(&devs)) return 3;
   drop_kept_result();  // the image of an earlier rays_hip_trace (if any) is not this call's result: it goes back
   const auto t0 = std::chrono::steady_clock::now();
-  const int G = (int)devs.size();
-  const int per = (nray + G - 1) / G;
-  std::vector<int> rcs(G, 0);
-  std::vector<std::string> errs(G);
-  std::vector<std::unique_ptr<DepositionBlock>> blocks;
-  for (int g = 0; g < G; g++) {
-    blocks.emplace_back(new DepositionBlock(g));
-    blocks[g]->dev = devs[g];
-    blocks[g]->r0 = std::min(nray, g * per);
-    blocks[g]->r1 = std::min(nray, (g + 1) * per);
-  }
-  {
-    std::vector<std::thread> th;
-    for (int g = 0; g < G; g++)
-      th.emplace_back([&, g] {
-        rcs[g] = deposition_block_on_device(*blocks[g], p, rvec0, rindex_vec0, initial_ray_power, which, n_bins, npoints,
-                                            stop_code, start_ray_vec, end_ray_vec, end_residuals, max_residuals);
-        if (rcs[g]) errs[g] = g_err;  // (the message is this worker thread's)
-      });
-    for (auto& t : th) t.join();
-  }
-  for (int g = 0; g < G; g++)
-    if (rcs[g]) {
-      g_err = errs[g];
-      return rcs[g];
-    }
-  // the ray-ordered sums, block after block
-  std::vector<double> carry((size_t)n_bins, 0.0), wbuf;
-  bool have_carry = false;
-  {
-    CurrentDevice restore;
-    for (int g = 0; g < G; g++) {
-      DepositionBlock& B = *blocks[g];
-      const int n = B.r1 - B.r0;
-      if (n <= 0) continue;
-      HIP_TRY(hipSetDevice(B.dev));
-      if (have_carry)
-        HIP_TRY(hipMemcpyAsync(B.d_in, carry.data(), sizeof(double) * (size_t)n_bins, hipMemcpyHostToDevice, B.st));
-      const hipError_t e = rays::launch_profile_sum(n_bins, n, B.d_work, have_carry ? B.d_in : nullptr, B.d_out, B.st);
-      if (e != hipSuccess) return hip_fail(e, "profile sum kernel");
-      HIP_TRY(hipMemcpyAsync(carry.data(), B.d_out, sizeof(double) * (size_t)n_bins, hipMemcpyDeviceToHost, B.st));
-      HIP_TRY(hipStreamSynchronize(B.st));
-      have_carry = true;
-      if (work) HIP_TRY_AS("hipMemcpy (work)", work_to_host(B.d_work, n_bins, n, work + (size_t)B.r0 * n_bins, &wbuf));
-      B.bufs.release();
-    }
-  }
-  std::memcpy(profile, carry.data(), sizeof(double) * (size_t)n_bins);
+  const SummaryArrays out = {npoints, stop_code, start_ray_vec, end_ray_vec, end_residuals, max_residuals};
+  const size_t nb = (size_t)n_bins;
+  std::deque<DepositionBlock> blk;
+  // every block traced and binned; the summaries go to the caller's arrays
+  rc = run_blocks(devs, nray, &blk, [&](DepositionBlock& B) {
+    if (B.n() <= 0) return 0;
+    HIP_TRY_AS("hipSetDevice / hipStreamCreate", B.open());
+    HIP_TRY_AS("hipMalloc (result arrays)", B.d.alloc(B.bufs, (size_t)B.n(), (size_t)p->nv, start_ray_vec != nullptr));
+    HIP_TRY_AS("hipMalloc(&d_work)", B.bufs.alloc(&B.d_work, nb * (size_t)B.n()));
+    HIP_TRY_AS("hipMalloc(&d_in)", B.bufs.alloc(&B.d_in, nb));
+    HIP_TRY_AS("hipMalloc(&d_out)", B.bufs.alloc(&B.d_out, nb));
+    HIP_TRY_AS("hipMalloc / hipMemcpyAsync (block inputs)", B.upload({rvec0, rindex_vec0, initial_ray_power}));
+    const int rc_b = trace_deposition_launch(p, B.n(), B.in, which, n_bins, B.d, B.d_work, B.st());
+    if (rc_b) return rc_b;
+    HIP_TRY_AS("hipMemcpyAsync (summaries)", B.download(out, (size_t)p->nv));
+    HIP_TRY(hipStreamSynchronize(B.st()));
+    return 0;
+  });
+  if (rc) return rc;
+  rc = chain_profiles(blk, n_bins, work, profile, [&](DepositionBlock& B, DeviceBuffers&, const double* carry_in,
+                                                      double* carry_out, const double** d_work_out) {
+    if (carry_in) HIP_TRY(hipMemcpyAsync(B.d_in, carry_in, sizeof(double) * nb, hipMemcpyHostToDevice, B.st()));
+    const hipError_t e = rays::launch_profile_sum(n_bins, B.n(), B.d_work, carry_in ? B.d_in : nullptr, B.d_out, B.st());
+    if (e != hipSuccess) return hip_fail(e, "profile sum kernel");
+    HIP_TRY(hipMemcpyAsync(carry_out, B.d_out, sizeof(double) * nb, hipMemcpyDeviceToHost, B.st()));
+    HIP_TRY(hipStreamSynchronize(B.st()));
+    *d_work_out = B.d_work;
+    return 0;
+  });
+  if (rc) return rc;
   if (elapsed_s)
     *elapsed_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   return 0;
@@ -1770,11 +1622,9 @@ static int ray_init_run(const rays_params_t* p, const rays_fan_t* fan, int nray_
   if (fan_setup(p, fan, nray_max, &F, &launch, per_r_launch, &why)) return fail(why);
   const int n_cand = F.n_launch * F.n_a * F.n_b;
   const int nb = (n_cand + rays::ray_init_block() - 1) / rays::ray_init_block();
-  rays::DevParams D = make_dev_params(*p);
-  if (p->equilib_model == RAYS_EQ_AXISYM) {
-    rc = get_axisym_device(&D);
-    if (rc) return rc;
-  }
+  rays::DevParams D;
+  rc = dev_params_with_axisym(p, &D);
+  if (rc) return rc;
   DeviceBuffers bufs;
   double *d_launch = nullptr, *d_cand = nullptr;
   int *d_keep = nullptr, *d_bc = nullptr, *d_offs = nullptr, *d_first = nullptr;
@@ -1850,6 +1700,9 @@ int rays_hip_ray_init(const rays_params_t* p, const rays_fan_t* fan, int nray_ma
   return 0;
 }
 
+// Diagnostic entry (tests): evaluate the RHS pieces at n states on the current device.
+// v[n][nv] host; outputs host: cold7[n][7], num7[n][7], dvds[n][nv], resid[n], codes[n][4]
+// (codes: equilibrium err, eqn_ray stop code, check_save flag, check_save stop_ode).
 int rays_hip_probe(const rays_params_t* p, int n, const double* v, double* cold7, double* num7,
                    double* dvds, double* resid, int32_t* codes) {
   int rc = rays_hip_check_params(p);
@@ -1866,11 +1719,9 @@ int rays_hip_probe(const rays_params_t* p, int n, const double* v, double* cold7
   HIP_TRY_AS("hipMalloc(&d_r)", bufs.alloc(&d_r, (size_t)n));
   HIP_TRY_AS("hipMalloc(&d_k)", bufs.alloc(&d_k, 4 * (size_t)n));
   HIP_TRY(hipMemcpy(d_v, v, sizeof(double) * nv * n, hipMemcpyHostToDevice));
-  rays::DevParams D = make_dev_params(*p);
-  if (p->equilib_model == RAYS_EQ_AXISYM) {
-    rc = get_axisym_device(&D);
-    if (rc) return rc;
-  }
+  rays::DevParams D;
+  rc = dev_params_with_axisym(p, &D);
+  if (rc) return rc;
   hipLaunchKernelGGL(rays::probe_kernel, dim3((n + 63) / 64), dim3(64), 0, 0, D, p->equilib_model,
                      p->nspec + 1, p->nv, n, d_v, d_c, d_n, d_f, d_r, d_k);
   HIP_TRY(hipGetLastError());

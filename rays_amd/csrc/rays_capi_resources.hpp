@@ -8,12 +8,14 @@
 //   the block cache   device blocks and the stream of a slot of the device list, kept between calls
 //   DeviceBuffers     the device blocks of ONE call, given back when the call ends, however it ends
 //   SlotStream, EventPair, CurrentDevice   the same for a call's stream, its two copy events, the caller's device
+//   RayBlock          one block of a sharded call: its slot's stream and buffers, drained before the buffers go back
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <map>
 #include <mutex>
+#include <string>
 #include <utility>
 #include <vector>
 
@@ -291,6 +293,94 @@ class EventPair {
 
  private:
   hipEvent_t ev_[2] = {nullptr, nullptr};
+};
+
+// The per-ray arrays of a trace, on a device or on the host: the inputs, the summaries every trace kernel writes
+// (sv, the state each ray started from, is optional) and the trajectories the recording kernels write as well.
+struct RayInputs {
+  const double *rvec0 = nullptr, *rindex_vec0 = nullptr, *power = nullptr;  // power: fused deposition only
+};
+struct SummaryArrays {
+  int32_t *np = nullptr, *sc = nullptr;
+  double *sv = nullptr, *ev = nullptr, *er = nullptr, *mr = nullptr;
+  hipError_t alloc(DeviceBuffers& bufs, size_t n, size_t nv, bool with_sv) {
+    hipError_t e = bufs.alloc(&np, n);
+    if (e == hipSuccess) e = bufs.alloc(&sc, n);
+    if (e == hipSuccess && with_sv) e = bufs.alloc(&sv, nv * n);
+    if (e == hipSuccess) e = bufs.alloc(&ev, nv * n);
+    if (e == hipSuccess) e = bufs.alloc(&er, n);
+    return e == hipSuccess ? bufs.alloc(&mr, n) : e;
+  }
+};
+struct TrajectoryArrays {
+  double *rv = nullptr, *res = nullptr;
+  hipError_t alloc(DeviceBuffers& bufs, size_t n, size_t npt, size_t nv) {
+    const hipError_t e = bufs.alloc(&rv, npt * nv * n);
+    return e == hipSuccess ? bufs.alloc(&res, npt * n) : e;
+  }
+};
+
+// One block of a call that shards its rays over the slots of the device list: rays [r0, r1) on `dev`, with the slot's
+// stream and cached buffers.  The worker thread of the block opens it and leaves rc / err behind.  THE rule of these
+// calls lives in the destructor: however the call ends -- this block's worker failed half-way, another block's did, a
+// later phase of the call failed -- nothing of the block is still in flight when its buffers go back to the slot's
+// cache (bufs is destroyed after the destructor's body), and the caller's current device is as it was.
+struct RayBlock {
+  const int slot;
+  int dev = 0, r0 = 0, r1 = 0;
+  SlotStream stream;
+  DeviceBuffers bufs;
+  RayInputs in;      // the device copies of the block's inputs
+  SummaryArrays d;   // the block's summaries on the device
+  int rc = 0;
+  std::string err;   // the worker thread's message when rc != 0
+
+  explicit RayBlock(int s) : slot(s), bufs(s) {}
+  ~RayBlock() {
+    if (!st()) return;
+    CurrentDevice restore;
+    if (hipSetDevice(dev) == hipSuccess) (void)hipStreamSynchronize(st());
+  }
+  int n() const { return r1 - r0; }
+  hipStream_t st() const { return stream.get(); }
+  // the block's device, its claim on the slot, the slot's stream: what a worker does first
+  hipError_t open() {
+    const hipError_t e = hipSetDevice(dev);
+    if (e != hipSuccess) return e;
+    claim_slot_for_device(slot, dev);
+    return stream.open(slot);
+  }
+  // device copies of rvec0 / rindex_vec0 (/ power) of rays [r0, r1), queued on the block's stream
+  hipError_t upload(const RayInputs& host) {
+    const size_t N = (size_t)n();
+    const auto up = [&](const double* src, size_t per_ray, const double** out) {
+      double* p = nullptr;
+      hipError_t e = bufs.alloc(&p, per_ray * N);
+      if (e == hipSuccess)
+        e = hipMemcpyAsync(p, src + per_ray * (size_t)r0, sizeof(double) * per_ray * N, hipMemcpyHostToDevice, st());
+      *out = p;
+      return e;
+    };
+    hipError_t e = up(host.rvec0, 3, &in.rvec0);
+    if (e == hipSuccess) e = up(host.rindex_vec0, 3, &in.rindex_vec0);
+    if (e == hipSuccess && host.power) e = up(host.power, 1, &in.power);
+    return e;
+  }
+  // the summaries' device-to-host copies into the caller's arrays at r0, queued on the block's stream; an array the
+  // caller did not ask for (null) is skipped
+  hipError_t download(const SummaryArrays& host, size_t nv) const {
+    const size_t N = (size_t)n();
+    const auto down = [&](auto* dst, const auto* src, size_t per_ray) {
+      if (!dst) return hipSuccess;
+      return hipMemcpyAsync(dst + per_ray * (size_t)r0, src, sizeof(*dst) * per_ray * N, hipMemcpyDeviceToHost, st());
+    };
+    hipError_t e = down(host.np, d.np, 1);
+    if (e == hipSuccess) e = down(host.sc, d.sc, 1);
+    if (e == hipSuccess) e = down(host.sv, d.sv, nv);
+    if (e == hipSuccess) e = down(host.ev, d.ev, nv);
+    if (e == hipSuccess) e = down(host.er, d.er, 1);
+    return e == hipSuccess ? down(host.mr, d.mr, 1) : e;
+  }
 };
 
 }  // namespace host

@@ -73,55 +73,46 @@ void rccl_close() {
 }
 
 // One device's share: trace rays [r0, r1) into slabs on that device; peers also pack them.
-struct GatherBlock {
-  explicit GatherBlock(int slot) : bufs(slot) {}
-  int dev = 0, r0 = 0, r1 = 0;
-  SlotStream stream;
-  hipStream_t st = nullptr;
-  DeviceBuffers bufs;  // everything below but the root's slabs, which are the gathered result's
-  double *d_r = nullptr, *d_n = nullptr;
-  ResultArrays d;
+struct GatherBlock : RayBlock {
+  using RayBlock::RayBlock;  // (bufs: everything below but the root's slabs, which are the gathered result's)
+  TrajectoryArrays t;
   long long* d_off = nullptr;
   double *d_pv = nullptr, *d_pr = nullptr;  // packed (peers: send buffers)
   std::vector<int32_t> np;                  // host copy of the block's npoints
   std::vector<long long> offs;
   long long total = 0;
-  int rc = 0;
-  std::string err;
 };
 
 // The gathered result: library-owned until the next rays_hip_trace_gather call / rays_hip_finalize
 // (never destroyed: no HIP call may run during static destruction, when the runtime may be gone already)
 DeviceBuffers& g_gathered = *new DeviceBuffers(kResultSlot);
 
-// Phase 1 on one device (its own host thread): trace block g, slot g of the block cache.
-int gather_trace_block(int g, GatherBlock& b, const ResultArrays& A, const rays_params_t* p, int nray,
-                       const double* rvec0, const double* rindex_vec0) {
+// Phase 1 on one device (its own host thread): trace block g, slot g of the block cache.  A: the root's global arrays.
+int gather_trace_block(GatherBlock& b, const SummaryArrays& A, const TrajectoryArrays& At, const rays_params_t* p,
+                       int nray, const RayInputs& in) {
   const size_t npt = (size_t)p->nstep_max + 1, nv = (size_t)p->nv;
-  const int n = b.r1 - b.r0;
-  HIP_TRY(hipSetDevice(b.dev));
-  claim_slot_for_device(g, b.dev);  // slot g may hold another device's stream and blocks (rays_hip_trace: slots per device)
-  HIP_TRY_AS("hipStreamCreate", b.stream.open(g));
-  b.st = b.stream.get();
+  const int g = b.slot, n = b.n();
+  // (slot g may hold another device's stream and blocks -- rays_hip_trace: slots per device; the stream is opened for an
+  // empty block too: phase 2 runs on the root's)
+  HIP_TRY_AS("hipSetDevice / hipStreamCreate", b.open());
+  const hipStream_t st = b.st();
   if (n <= 0) return 0;
-  HIP_TRY_AS("hipMalloc(&b.d_r)", b.bufs.alloc(&b.d_r, 3 * (size_t)n));
-  HIP_TRY_AS("hipMalloc(&b.d_n)", b.bufs.alloc(&b.d_n, 3 * (size_t)n));
   if (g == 0) {  // the root traces straight into its slab of the global arrays
     b.d = A;
-    HIP_TRY(hipMemsetAsync(A.rv, 0, sizeof(double) * npt * nv * (size_t)nray, b.st));  // ray_results_m.f90:154-164
-    HIP_TRY(hipMemsetAsync(A.res, 0, sizeof(double) * npt * (size_t)nray, b.st));
+    b.t = At;
+    HIP_TRY(hipMemsetAsync(At.rv, 0, sizeof(double) * npt * nv * (size_t)nray, st));  // ray_results_m.f90:154-164
+    HIP_TRY(hipMemsetAsync(At.res, 0, sizeof(double) * npt * (size_t)nray, st));
   } else {
-    HIP_TRY_AS("hipMalloc (result arrays)", b.d.alloc(b.bufs, (size_t)n, npt, nv));
+    HIP_TRY_AS("hipMalloc (result arrays)", b.t.alloc(b.bufs, (size_t)n, npt, nv));
+    HIP_TRY_AS("hipMalloc (result arrays)", b.d.alloc(b.bufs, (size_t)n, nv, false));
   }
-  HIP_TRY(hipMemcpyAsync(b.d_r, rvec0 + 3 * (size_t)b.r0, sizeof(double) * 3 * n, hipMemcpyHostToDevice, b.st));
-  HIP_TRY(hipMemcpyAsync(b.d_n, rindex_vec0 + 3 * (size_t)b.r0, sizeof(double) * 3 * n, hipMemcpyHostToDevice, b.st));
-  const int rc = rays_hip_trace_device(p, n, b.d_r, b.d_n, b.d.rv, b.d.res, b.d.np, b.d.sc, b.d.ev, b.d.er, b.d.mr, b.st,
-                                       RAYS_TRACE_NO_ZERO_FILL);
+  HIP_TRY_AS("hipMalloc / hipMemcpyAsync (block inputs)", b.upload(in));
+  const int rc = launch_trace(p, KernelVariant::Recording, n, b.in, b.t, b.d, st, RAYS_TRACE_NO_ZERO_FILL);
   if (rc || g == 0) return rc;
   // pack: the block's points back to back
   b.np.resize(n);
-  HIP_TRY(hipMemcpyAsync(b.np.data(), b.d.np, sizeof(int32_t) * n, hipMemcpyDeviceToHost, b.st));
-  HIP_TRY(hipStreamSynchronize(b.st));
+  HIP_TRY(hipMemcpyAsync(b.np.data(), b.d.np, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
   b.offs.resize((size_t)n + 1);
   b.offs[0] = 0;
   for (int i = 0; i < n; i++) b.offs[(size_t)i + 1] = b.offs[i] + (b.np[i] > 0 ? b.np[i] : 0);
@@ -129,18 +120,18 @@ int gather_trace_block(int g, GatherBlock& b, const ResultArrays& A, const rays_
   HIP_TRY_AS("hipMalloc(&b.d_off)", b.bufs.alloc(&b.d_off, (size_t)n + 1));
   HIP_TRY_AS("hipMalloc(&b.d_pv)", b.bufs.alloc(&b.d_pv, nv * (size_t)std::max(b.total, 1ll)));
   HIP_TRY_AS("hipMalloc(&b.d_pr)", b.bufs.alloc(&b.d_pr, (size_t)std::max(b.total, 1ll)));
-  HIP_TRY(hipMemcpyAsync(b.d_off, b.offs.data(), sizeof(long long) * ((size_t)n + 1), hipMemcpyHostToDevice, b.st));
-  HIP_TRY(rays::launch_pack(true, n, (int)nv, p->nstep_max, b.d.np, b.d_off, b.d.rv, b.d.res, b.d_pv, b.d_pr, b.st));
+  HIP_TRY(hipMemcpyAsync(b.d_off, b.offs.data(), sizeof(long long) * ((size_t)n + 1), hipMemcpyHostToDevice, st));
+  HIP_TRY(rays::launch_pack(true, n, (int)nv, p->nstep_max, b.d.np, b.d_off, b.t.rv, b.t.res, b.d_pv, b.d_pr, st));
   return 0;
 }
 
 // Phase 2, the gather.  One grouped batch: peer g sends on its stream, the root receives on its own (rs) into rx's
 // buffers and unpacks them into the peers' slabs of the global arrays.  Asynchronous: the caller drains the streams.
-int gather_to_root(const std::deque<GatherBlock>& blk, const ResultArrays& A, const rays_params_t* p, int root,
-                   DeviceBuffers& rx) {
+int gather_to_root(const std::deque<GatherBlock>& blk, const SummaryArrays& A, const TrajectoryArrays& At,
+                   const rays_params_t* p, int root, DeviceBuffers& rx) {
   const int G = (int)blk.size();
   const size_t npt = (size_t)p->nstep_max + 1, nv = (size_t)p->nv;
-  const hipStream_t rs = blk[0].st;
+  const hipStream_t rs = blk[0].st();
   std::vector<double*> rx_pv(G, nullptr), rx_pr(G, nullptr);
   std::vector<long long*> rx_off(G, nullptr);
   if (hipSetDevice(root) != hipSuccess) return fail("rays_hip_trace_gather: hipSetDevice(root)");
@@ -161,20 +152,20 @@ int gather_to_root(const std::deque<GatherBlock>& blk, const ResultArrays& A, co
     const size_t n = (size_t)(b.r1 - b.r0);
     if (n == 0) continue;
     // peer g -> root: summaries straight into the global arrays, trajectories packed
-    r = g_rccl.Send(b.d.np, n, kNcclInt32, 0, g_rccl.comms[g], b.st);
+    r = g_rccl.Send(b.d.np, n, kNcclInt32, 0, g_rccl.comms[g], b.st());
     if (!r) r = g_rccl.Recv(A.np + b.r0, n, kNcclInt32, g, g_rccl.comms[0], rs);
-    if (!r) r = g_rccl.Send(b.d.sc, n, kNcclInt32, 0, g_rccl.comms[g], b.st);
+    if (!r) r = g_rccl.Send(b.d.sc, n, kNcclInt32, 0, g_rccl.comms[g], b.st());
     if (!r) r = g_rccl.Recv(A.sc + b.r0, n, kNcclInt32, g, g_rccl.comms[0], rs);
-    if (!r) r = g_rccl.Send(b.d.ev, n * nv, kNcclDouble, 0, g_rccl.comms[g], b.st);
+    if (!r) r = g_rccl.Send(b.d.ev, n * nv, kNcclDouble, 0, g_rccl.comms[g], b.st());
     if (!r) r = g_rccl.Recv(A.ev + nv * (size_t)b.r0, n * nv, kNcclDouble, g, g_rccl.comms[0], rs);
-    if (!r) r = g_rccl.Send(b.d.er, n, kNcclDouble, 0, g_rccl.comms[g], b.st);
+    if (!r) r = g_rccl.Send(b.d.er, n, kNcclDouble, 0, g_rccl.comms[g], b.st());
     if (!r) r = g_rccl.Recv(A.er + b.r0, n, kNcclDouble, g, g_rccl.comms[0], rs);
-    if (!r) r = g_rccl.Send(b.d.mr, n, kNcclDouble, 0, g_rccl.comms[g], b.st);
+    if (!r) r = g_rccl.Send(b.d.mr, n, kNcclDouble, 0, g_rccl.comms[g], b.st());
     if (!r) r = g_rccl.Recv(A.mr + b.r0, n, kNcclDouble, g, g_rccl.comms[0], rs);
     if (b.total > 0) {
-      if (!r) r = g_rccl.Send(b.d_pv, (size_t)b.total * nv, kNcclDouble, 0, g_rccl.comms[g], b.st);
+      if (!r) r = g_rccl.Send(b.d_pv, (size_t)b.total * nv, kNcclDouble, 0, g_rccl.comms[g], b.st());
       if (!r) r = g_rccl.Recv(rx_pv[g], (size_t)b.total * nv, kNcclDouble, g, g_rccl.comms[0], rs);
-      if (!r) r = g_rccl.Send(b.d_pr, (size_t)b.total, kNcclDouble, 0, g_rccl.comms[g], b.st);
+      if (!r) r = g_rccl.Send(b.d_pr, (size_t)b.total, kNcclDouble, 0, g_rccl.comms[g], b.st());
       if (!r) r = g_rccl.Recv(rx_pr[g], (size_t)b.total, kNcclDouble, g, g_rccl.comms[0], rs);
     }
   }
@@ -185,8 +176,8 @@ int gather_to_root(const std::deque<GatherBlock>& blk, const ResultArrays& A, co
     const GatherBlock& b = blk[g];
     const int n = b.r1 - b.r0;
     if (n <= 0 || b.total == 0) continue;
-    if (rays::launch_pack(false, n, (int)nv, p->nstep_max, A.np + b.r0, rx_off[g], A.rv + npt * nv * (size_t)b.r0,
-                          A.res + npt * (size_t)b.r0, rx_pv[g], rx_pr[g], rs) != hipSuccess)
+    if (rays::launch_pack(false, n, (int)nv, p->nstep_max, A.np + b.r0, rx_off[g], At.rv + npt * nv * (size_t)b.r0,
+                          At.res + npt * (size_t)b.r0, rx_pv[g], rx_pr[g], rs) != hipSuccess)
       return fail("rays_hip_trace_gather: unpack kernel launch failed");
   }
   return 0;
@@ -204,15 +195,7 @@ extern "C" int rays_hip_trace_gather(const rays_params_t* p, int nray, const dou
   if (nray < 0) return fail("rays_hip_trace_gather: nray < 0");
   if (nray > 0 && (!rvec0 || !rindex_vec0)) return fail("rays_hip_trace_gather: null array argument");
   std::vector<int> devs;
-  {
-    std::lock_guard<std::mutex> lk(g_mu);
-    devs = g_devices;
-  }
-  if (devs.empty()) {
-    if (rays_hip_init(0) < 0) return 3;
-    std::lock_guard<std::mutex> lk(g_mu);
-    devs = g_devices;
-  }
+  if (call_devices(&devs)) return 3;
   for (size_t i = 0; i < devs.size(); i++)
     for (size_t j = i + 1; j < devs.size(); j++)
       if (devs[i] == devs[j]) return fail("rays_hip_trace_gather: the device list must not repeat a device (RCCL: one rank per device)");
@@ -230,43 +213,30 @@ extern "C" int rays_hip_trace_gather(const rays_params_t* p, int nray, const dou
   HIP_TRY(hipSetDevice(root));
   g_gathered.release();
   claim_slot_for_device(kResultSlot, root);
-  ResultArrays A;
-  HIP_TRY_AS("hipMalloc (result arrays)", A.alloc(g_gathered, (size_t)nray, npt, nv));
+  SummaryArrays A;
+  TrajectoryArrays At;
+  HIP_TRY_AS("hipMalloc (result arrays)", At.alloc(g_gathered, (size_t)nray, npt, nv));
+  HIP_TRY_AS("hipMalloc (result arrays)", A.alloc(g_gathered, (size_t)nray, nv, false));
   // ---- phase 1: every device traces its block (one host thread per device) ------------------------------------
-  // (blk and rx give their buffers back to the cache when this call returns: after the streams are drained below)
-  const int per = (nray + G - 1) / G;
-  std::deque<GatherBlock> blk;
+  // (rx gives its buffers back to the cache when this call returns -- after blk, declared behind it, has drained its
+  // streams)
   DeviceBuffers rx(0);  // the root's receive buffers, from the root block's slot
-  std::vector<std::thread> th;
-  for (int g = 0; g < G; g++) {
-    blk.emplace_back(g);
-    blk[g].dev = devs[g];
-    blk[g].r0 = std::min(nray, g * per);
-    blk[g].r1 = std::min(nray, (g + 1) * per);
-  }
-  for (int g = 0; g < G; g++)
-    th.emplace_back([&, g] {
-      GatherBlock& b = blk[g];
-      b.rc = gather_trace_block(g, b, A, p, nray, rvec0, rindex_vec0);
-      if (b.rc) b.err = g_err;  // (the message is this worker thread's)
-    });
-  for (auto& t : th) t.join();
-  for (int g = 0; g < G; g++)
-    if (blk[g].rc) {
-      g_err = blk[g].err;
-      return blk[g].rc;
-    }
+  std::deque<GatherBlock> blk;
+  rc = run_blocks(devs, nray, &blk,
+                  [&](GatherBlock& b) { return gather_trace_block(b, A, At, p, nray, {rvec0, rindex_vec0}); });
+  if (rc) return rc;
   // ---- phase 2: the gather ---------------------------------------------------------------------------------------
-  int result = G > 1 ? gather_to_root(blk, A, p, root, rx) : 0;
-  // ---- completion: every stream drained before the buffers go back to the cache ---------------------------------
-  for (int g = 0; g < G; g++) {
-    if (!blk[g].st) continue;
-    if (hipSetDevice(blk[g].dev) == hipSuccess && hipStreamSynchronize(blk[g].st) != hipSuccess && !result)
+  int result = G > 1 ? gather_to_root(blk, A, At, p, root, rx) : 0;
+  // ---- completion: every stream drained here, where a failure can still be reported (RayBlock's destructor drains
+  // again, silently, on every way out of this call) ---------------------------------------------------------------
+  for (const GatherBlock& b : blk) {
+    if (!b.st()) continue;
+    if (hipSetDevice(b.dev) == hipSuccess && hipStreamSynchronize(b.st()) != hipSuccess && !result)
       result = fail("rays_hip_trace_gather: stream synchronisation failed");
   }
   (void)hipSetDevice(root);
   if (result) return result;
-  out->ray_vec = A.rv; out->residual = A.res; out->npoints = A.np; out->stop_code = A.sc;
+  out->ray_vec = At.rv; out->residual = At.res; out->npoints = A.np; out->stop_code = A.sc;
   out->end_ray_vec = A.ev; out->end_residuals = A.er; out->max_residuals = A.mr;
   return 0;
 }

@@ -4,9 +4,12 @@
 //   emul_summary_capi <case file>
 // Case file (native endianness): int32 nray, nv, sizeof(rays_params_t); the parameter block; rvec0[nray][3],
 // rindex_vec0[nray][3]; then the oracle's summaries of these rays: npoints[nray], stop_code[nray] (int32),
-// start_ray_vec[nray][nv], end_ray_vec[nray][nv], end_residuals[nray], max_residuals[nray].
+// start_ray_vec[nray][nv], end_ray_vec[nray][nv], end_residuals[nray], max_residuals[nray]; then the oracle's trajectories
+// of the same trace, packed to npoints points per ray: ray_vec[sum npoints][nv], residual[sum npoints].
 // Every device list of 1 to 4 devices traces the first n rays for several n -- a ragged last block, blocks that are
 // empty -- and must reproduce the oracle's bytes; after rays_hip_finalize the emulated driver holds nothing.
+// rays_hip_trace does the same on these lists and on one that repeats a device, with and without the kept result, and
+// rays_hip_trace_gather on one device: the block workers of both under the sanitizers without a Python host.
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -27,6 +30,36 @@ static bool read_n(std::FILE* f, std::vector<T>& v, size_t n) {
   v.resize(n);
   return n == 0 || std::fread(v.data(), sizeof(T), n, f) == n;
 }
+static const double kPoison = -7.;
+// the oracle's case: summaries and packed trajectories (offs[i]: first packed point of ray i)
+struct Case {
+  size_t nv = 0, npt = 0;
+  std::vector<int32_t> np, sc;
+  std::vector<double> end, eres, mres, pv, pr;
+  std::vector<size_t> offs;
+};
+// ray_vec[n][npt][nv] / residual[n][npt] of the first n rays: points 1..npoints are the oracle's bit for bit, every
+// slot behind them holds `rest` (the poison the entry must not overwrite, or the zeros of a gathered result)
+static bool same_trajectories(const Case& c, size_t n, const double* rv, const double* res, double rest) {
+  for (size_t i = 0; i < n; i++) {
+    const size_t k = (size_t)c.np[i];
+    if (std::memcmp(rv + c.npt * c.nv * i, c.pv.data() + c.offs[i] * c.nv, sizeof(double) * c.nv * k) != 0 ||
+        std::memcmp(res + c.npt * i, c.pr.data() + c.offs[i], sizeof(double) * k) != 0)
+      return false;
+    for (size_t j = k * c.nv; j < c.npt * c.nv; j++)
+      if (std::memcmp(&rv[c.npt * c.nv * i + j], &rest, sizeof rest) != 0) return false;
+    for (size_t j = k; j < c.npt; j++)
+      if (std::memcmp(&res[c.npt * i + j], &rest, sizeof rest) != 0) return false;
+  }
+  return true;
+}
+static bool same_summaries(const Case& c, size_t n, const int32_t* np, const int32_t* sc, const double* end,
+                           const double* er, const double* mr) {
+  return std::memcmp(np, c.np.data(), sizeof(int32_t) * n) == 0 && std::memcmp(sc, c.sc.data(), sizeof(int32_t) * n) == 0 &&
+         std::memcmp(end, c.end.data(), sizeof(double) * c.nv * n) == 0 &&
+         std::memcmp(er, c.eres.data(), sizeof(double) * n) == 0 && std::memcmp(mr, c.mres.data(), sizeof(double) * n) == 0;
+}
+
 static std::string last_error() {
   char buf[512];
   rays_hip_last_error(buf, (int)sizeof buf);
@@ -49,7 +82,17 @@ int main(int argc, char** argv) {
   bool ok = std::fread(&p, sizeof p, 1, f) == 1 && read_n(f, r0, 3 * nray) && read_n(f, n0, 3 * nray) &&
             read_n(f, np, nray) && read_n(f, sc, nray) && read_n(f, start, nv * nray) && read_n(f, end, nv * nray) &&
             read_n(f, eres, nray) && read_n(f, mres, nray);
+  Case c;
+  c.nv = nv;
+  c.npt = (size_t)p.nstep_max + 1;
+  c.offs.assign(nray + 1, 0);
+  for (size_t i = 0; ok && i < nray; i++) {
+    ok = np[i] >= 1 && (size_t)np[i] <= c.npt;
+    c.offs[i + 1] = c.offs[i] + (size_t)np[i];
+  }
+  ok = ok && read_n(f, c.pv, nv * c.offs[nray]) && read_n(f, c.pr, c.offs[nray]);
   std::fclose(f);
+  c.np = np; c.sc = sc; c.end = end; c.eres = eres; c.mres = mres;
   if (!ok || (int)nv != p.nv) { std::fprintf(stderr, "short or inconsistent case file\n"); return 2; }
   if (rays_hip_device_count() < 4) { std::fprintf(stderr, "needs 4 emulated devices\n"); return 2; }
 
@@ -84,6 +127,63 @@ int main(int argc, char** argv) {
       calls += 2;
     }
   }
+  long long summary_launches = 0, wrong = 0, live = -1;
+  rays_emul_runtime_stats(&summary_launches, &wrong, &live);
+
+  // rays_hip_trace on the same device lists and on one that repeats a device (three blocks, three slots, one device):
+  // without the kept result, and with it switched on for the call and off again (the blocks' slabs stay on the devices
+  // and go back to the slots' caches)
+  const int trace_lists[][4] = {{0}, {2, 1}, {0, 1, 3}, {0, 1, 2, 3}, {0, 0, 0}};
+  const int trace_G[] = {1, 2, 3, 4, 3};
+  int trace_calls = 0;
+  for (int l = 0; l < 5; l++) {
+    const int G = trace_G[l];
+    CHECK(rays_hip_init_devices(G, trace_lists[l]) >= 0);
+    const size_t counts[] = {nray, (size_t)G + 1, 1, 0};
+    for (size_t n : counts) {
+      if (n > nray) continue;
+      for (int keep = 0; keep < 2; keep++) {
+        // poisoned outputs, one element longer than asked for; slots past npoints are not the entry's to write either
+        std::vector<double> o_rv(c.npt * nv * n + 1, kPoison), o_res(c.npt * n + 1, kPoison);
+        std::vector<int32_t> o_np(n + 1, -7), o_sc(n + 1, -7);
+        std::vector<double> o_end(nv * n + 1, kPoison), o_er(n + 1, kPoison), o_mr(n + 1, kPoison);
+        double elapsed = -1.;
+        if (keep) CHECK(rays_hip_keep_last_result(1) == 0);
+        const int rc = rays_hip_trace(&p, (int)n, r0.data(), n0.data(), o_rv.data(), o_res.data(), o_np.data(), o_sc.data(),
+                                      o_end.data(), o_er.data(), o_mr.data(), &elapsed);
+        if (keep) CHECK(rays_hip_keep_last_result(0) == 1);
+        if (rc) std::fprintf(stderr, "rays_hip_trace(list %d, n = %zu, keep %d): rc %d: %s\n", l, n, keep, rc, last_error().c_str());
+        CHECK(rc == 0 && elapsed >= 0.);
+        CHECK(same_trajectories(c, n, o_rv.data(), o_res.data(), kPoison));
+        CHECK(o_rv[c.npt * nv * n] == kPoison && o_res[c.npt * n] == kPoison);
+        CHECK(same_summaries(c, n, o_np.data(), o_sc.data(), o_end.data(), o_er.data(), o_mr.data()));
+        CHECK(o_np[n] == -7 && o_sc[n] == -7 && o_end[nv * n] == kPoison && o_er[n] == kPoison && o_mr[n] == kPoison);
+        trace_calls++;
+      }
+    }
+  }
+  // rays_hip_trace_gather on one device (no RCCL) and rays_hip_result_to_host: the same trajectories, zeros past npoints
+  const int one[] = {0};
+  CHECK(rays_hip_init_devices(1, one) >= 0);
+  const size_t gather_counts[] = {nray, 2, 1, 0};
+  for (size_t n : gather_counts) {
+    if (n > nray) continue;
+    rays_device_result_t res;
+    const int rc = rays_hip_trace_gather(&p, (int)n, r0.data(), n0.data(), &res);
+    if (rc) std::fprintf(stderr, "rays_hip_trace_gather(n = %zu): rc %d: %s\n", n, rc, last_error().c_str());
+    CHECK(rc == 0 && res.nray == (int)n && res.device == 0);
+    std::vector<double> o_rv(c.npt * nv * n + 1, kPoison), o_res(c.npt * n + 1, kPoison);
+    std::vector<int32_t> o_np(n + 1, -7), o_sc(n + 1, -7);
+    std::vector<double> o_end(nv * n + 1, kPoison), o_er(n + 1, kPoison), o_mr(n + 1, kPoison);
+    CHECK(rays_hip_result_to_host(&p, &res, o_rv.data(), o_res.data(), o_np.data(), o_sc.data(), o_end.data(), o_er.data(),
+                                  o_mr.data()) == 0);
+    CHECK(same_trajectories(c, n, o_rv.data(), o_res.data(), 0.));
+    CHECK(o_rv[c.npt * nv * n] == kPoison && o_res[c.npt * n] == kPoison);
+    CHECK(same_summaries(c, n, o_np.data(), o_sc.data(), o_end.data(), o_er.data(), o_mr.data()));
+    CHECK(o_np[n] == -7 && o_sc[n] == -7 && o_end[nv * n] == kPoison && o_er[n] == kPoison && o_mr[n] == kPoison);
+    trace_calls++;
+  }
+
   // refusals, by name
   std::vector<int32_t> i1(1);
   std::vector<double> d1(nv);
@@ -98,7 +198,7 @@ int main(int argc, char** argv) {
         last_error().find("n_runs * nray exceeds") != std::string::npos);
   CHECK(std::strstr(rays_hip_summary_kernel_name_for(&p, (int)nray), "rk4_trace_kernel<37, 2, 0, 7>") != nullptr);
 
-  long long launches = 0, wrong = 0, live = -1, pinned = -1, streams = -1, events = -1;
+  long long launches = 0, pinned = -1, streams = -1, events = -1;
   rays_emul_runtime_stats(&launches, &wrong, &live);
   CHECK(wrong == 0 && live > 0);   // (the entry's cached blocks and the refill counters are still held)
   CHECK(rays_hip_finalize() == 0);
@@ -106,6 +206,7 @@ int main(int argc, char** argv) {
   rays_emul_runtime_live(&pinned, &streams, &events);
   CHECK(live == 0 && pinned == 0 && streams == 0 && events == 0 && wrong == 0);
   if (failures) { std::fprintf(stderr, "%d check(s) failed\n", failures); return 1; }
-  std::printf("summary capi ok: %d calls, %lld launches\n", calls, launches);
+  std::printf("summary capi ok: %d calls, %lld launches\n", calls, summary_launches);
+  std::printf("trace capi ok: %d calls, %lld launches\n", trace_calls, launches - summary_launches);
   return 0;
 }

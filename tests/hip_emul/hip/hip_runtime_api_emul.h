@@ -44,7 +44,8 @@ struct State {
   std::mutex mu;
   std::map<const char*, Alloc> allocs;   // device memory: base -> (size, owner)
   std::map<int, emul_stream> null_stream;
-  long long launches = 0, wrong_device = 0;
+  std::atomic<long long> launches{0};    // (kernels are launched from several host threads at once)
+  long long wrong_device = 0;
   std::atomic<long long> live_pinned{0}, live_streams{0}, live_events{0};   // created and not yet destroyed
 };
 inline State& state() { static State s; return s; }

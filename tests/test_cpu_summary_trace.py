@@ -127,7 +127,8 @@ def _case_file(path):
     r0, n0 = g["rvec0_full"][:301].copy(), g["rindex_vec0_full"][:301].copy()
     r0[17, 0] = 10.0      # launched outside the box: npoints = 1
     n0[40] *= 3.0         # off the dispersion surface: stops at the initial check
-    ref = sl.summaries_of(oracle_lib.trace(q, r0, n0))
+    full = oracle_lib.trace(q, r0, n0)
+    ref = sl.summaries_of(full)
     assert ref["npoints"].min() == 1 and ref["npoints"].max() == 126 and len(np.unique(ref["npoints"])) > 5
     with open(path, "wb") as f:
         f.write(struct.pack("=3i", len(r0), q.nv, len(bytes(q))))
@@ -136,12 +137,18 @@ def _case_file(path):
             f.write(np.ascontiguousarray(a, dtype=np.float64).tobytes())
         for k in sl.KEYS:
             f.write(np.ascontiguousarray(ref[k], dtype=np.int32 if k in ("npoints", "stop_code") else np.float64).tobytes())
+        # the trajectories of the same trace, packed: points 1..npoints of ray 0, of ray 1, ... (ray_vec, then residual)
+        for k in ("ray_vec", "residual"):
+            f.write(np.concatenate([np.asarray(full[k], dtype=np.float64)[r, :n].ravel()
+                                    for r, n in enumerate(ref["npoints"])]).tobytes())
 
 
 @pytest.mark.parametrize("sanitize", [False, True], ids=["plain", "asan_ubsan"])
 def test_host_entry_on_emulated_devices(sanitize, tmp_path):
     """rays_hip_trace_summary with 1 to 4 devices, a ragged last block and empty blocks, equals the oracle; the named
     refusals; after rays_hip_finalize the emulated driver reports no live allocation, pinned block, stream or event.
+    rays_hip_trace on the same device lists and on one that repeats a device, with and without the kept result, and
+    rays_hip_trace_gather on one device reproduce the oracle's trajectories bit for bit and write nothing else.
     Once plain and once as an ASan + UBSan executable with its own main (leak detection on)."""
     subprocess.check_call(["make", "-s", "-j", str(min(4, os.cpu_count() or 1)), "-f", "Makefile.capi_summary"] +
                           (["SAN=1"] if sanitize else []), cwd=EMUL_DIR)
