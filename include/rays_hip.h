@@ -415,6 +415,13 @@ int rays_hip_ode_step_device(const rays_params_t* p, int n, const double* d_v0, 
 const char* rays_hip_kernel_name(const rays_params_t* p);
 /* Same for a fan of nray rays: large fans may get a differently tuned build of the kernel. */
 const char* rays_hip_kernel_name_for(const rays_params_t* p, int nray);
+/* Which step loop that kernel runs for p: the one-wave-per-SIMD RK4 kernels of the Solovev equilibrium (analytic
+ * derivatives, up to two species) hold their step loop twice under ONE name -- 1: the lean loop, compiled for a run whose
+ * density model is not 'constant', whose species have no parabolic temperature profile and whose ray_param is not
+ * 'arcl'; 0: the general loop (every other kernel and parameter set; every launch while the developer switch
+ * RAYS_HIP_RK4_LOOP=general is set in the environment).  -1: p is refused or is not an RK4 configuration.  Summary-only,
+ * fused-deposition and rays_hip_ode_step_device launches of p take the same loop. */
+int rays_hip_rk4_loop_for(const rays_params_t* p, int nray);
 
 /* ---- multi-GPU trace with a device-resident result: the final trajectory gather over RCCL -------
  * (north_star: "RCCL over xGMI used only for the final trajectory gather".)

@@ -387,6 +387,21 @@ int sched_stride() {
   return (s >= 2 && s <= 8) ? s : kSchedStride;
 }
 
+// RAYS_HIP_RK4_LOOP=general: every launch of an RK4 trace kernel takes the general step loop, also where its parameters
+// allow the lean one (rays_rk4.hpp; developer switch for A/B measurements on one library and for the tests -- the exact
+// kernels' results are the same).  Read at every launch.
+bool rk4_loop_forced_general() {
+  const char* f = std::getenv("RAYS_HIP_RK4_LOOP");
+  return f && (f[0] == 'g' || f[0] == 'G');
+}
+// The loop `kernel` runs for p: 1 = lean, 0 = general.  What the kernel itself decides from its arguments.
+int rk4_loop_of(const rays::KernelEntry& kernel, const rays_params_t& p) {
+  if (kernel.solver != RAYS_ODE_RK4 || kernel.occ != 1 || !rays::rk4_lean_built(kernel.eq, kernel.ns, kernel.deriv)) return 0;
+  rays::TraceArgs A = rays::TraceArgs();
+  if (rk4_loop_forced_general()) A.sg_far_lanes = rays::kRk4ForceGeneralLoop;
+  return rays::rk4_lean_loop(make_dev_params(p), kernel.ns, A) ? 1 : 0;
+}
+
 int counter_launched(int slot, hipStream_t stream) {
   int dev = 0;
   HIP_TRY(hipGetDevice(&dev));
@@ -617,6 +632,11 @@ const char* rays_hip_kernel_name_for(const rays_params_t* p, int nray) {
   return find_kernel(*p, nray)->name;
 }
 
+int rays_hip_rk4_loop_for(const rays_params_t* p, int nray) {
+  if (!p || rays_hip_check_params(p) || p->ode_solver != RAYS_ODE_RK4) return -1;
+  return rk4_loop_of(*find_kernel(*p, nray), *p);
+}
+
 const char* rays_hip_summary_kernel_name_for(const rays_params_t* p, int nray) {
   if (!p || rays_hip_check_params(p)) return "";
   const rays::KernelEntry* k = find_kernel(*p, nray, KernelVariant::Summary);
@@ -706,6 +726,7 @@ int launch_trace(const rays_params_t* p, KernelVariant variant, int nray, const 
                     ? "rays_hip: the fused deposition kernel of this configuration is not in this build"
                     : "rays_hip: the summary-only kernel of this configuration is not in this build");
   const int stride = kernel->solver == RAYS_ODE_RK4 ? sched_stride() : 0;
+  if (kernel->solver == RAYS_ODE_RK4 && rk4_loop_forced_general()) A.sg_far_lanes = rays::kRk4ForceGeneralLoop;
   if (stride > 1) {
     // more rays than one wave per SIMD holds (the kernel decides with the lanes it is launched with)
     int dev = 0;

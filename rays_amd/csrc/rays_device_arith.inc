@@ -362,7 +362,9 @@ RAYS_DEV void solovev_magnetics(const DevParams& P, double x, double y, double z
 }
 
 // solovev_eq + solovev_psi  solovev_eq_m.f90:122-276, 280-322
-template <int NS, bool UE>
+// LEAN (the lean step loop of rk4_trace_kernel, rays_rk4.hpp; rays_trace.hpp: rk4_lean_loop): the launch has established that the density
+// model is not 'constant' and that no species has a parabolic temperature profile, so both tests are compile-time false.
+template <int NS, bool UE, bool LEAN = false>
 RAYS_DEV int solovev_fields(const DevParams& P, const double rvec[3], double bvec[3],
                             double gbt[3][3], double ns[NS], double gradns[NS][3], double ts[NS],
                             double gradts[NS][3], bool check_box) {
@@ -383,7 +385,7 @@ RAYS_DEV int solovev_fields(const DevParams& P, const double rvec[3], double bve
 #pragma unroll
     for (int i = 0; i < 3; i++) gradns[is][i] = gradts[is][i] = 0.;
   }
-  if (P.v_n_model == RAYS_SOLOVEV_N_CONSTANT) {  // :210-212
+  if (!LEAN && P.v_n_model == RAYS_SOLOVEV_N_CONSTANT) {  // :210-212
 #pragma unroll
     for (int is = 0; is < NS; is++) ns[is] = P.n0s[is];
   } else if (psiN < 1.0) {  // :214-225
@@ -404,7 +406,7 @@ RAYS_DEV int solovev_fields(const DevParams& P, const double rvec[3], double bve
   // and uses exponent alphat1 in the gradient: kept as in the reference.
 #pragma unroll
   for (int is = 0; is < NS; is++) {
-    if (P.v_t_model[is] == RAYS_SOLOVEV_T_PARABOLIC) {
+    if (!LEAN && P.v_t_model[is] == RAYS_SOLOVEV_T_PARABOLIC) {
 #pragma unroll
       for (int j = 0; j < NS; j++) {
         ts[j] = 0.;
@@ -934,7 +936,7 @@ RAYS_DEV int axisym_fields(const DevParams& P, const double rvec[3], double bvec
 // omgrf / omgrf2 are arguments because deriv_num re-evaluates the equilibrium at omgrf(1 +- delta/2)
 // (deriv_num.f90:72-79); on the device these are per-call values, which also removes the
 // reference's data race on the module variables.
-template <int EQ, int NS>
+template <int EQ, int NS, bool LEAN = false>
 RAYS_DEV void equilibrium(const DevParams& P, const Recip& Romgrf, const Recip& Romgrf2,
                           const double rvec[3], EqPoint<NS>& eq, bool check_box) {
   double ns[NS], gradns[NS][3], ts[NS], gradts[NS][3];
@@ -944,7 +946,7 @@ RAYS_DEV void equilibrium(const DevParams& P, const Recip& Romgrf, const Recip& 
   if (MODEL == RAYS_EQ_SLAB)
     err = slab_fields<NS, UE>(P, rvec, eq.bvec, eq.gbt, ns, gradns, ts, gradts, check_box);
   else if (MODEL == RAYS_EQ_SOLOVEV)
-    err = solovev_fields<NS, UE>(P, rvec, eq.bvec, eq.gbt, ns, gradns, ts, gradts, check_box);
+    err = solovev_fields<NS, UE, LEAN>(P, rvec, eq.bvec, eq.gbt, ns, gradns, ts, gradts, check_box);
   else
     err = axisym_fields<NS, UE>(P, rvec, eq.bvec, eq.gbt, ns, gradns, ts, gradts, check_box);
   eq.err = err;
@@ -1452,7 +1454,8 @@ RAYS_DEV double damp_fund_ech(const DevParams& P, const EqPoint<NS>& eq, const d
 // eqn_ray tail               eqn_ray.f90:131-229: group velocity + ray equations from dD/d(x,k,w).
 // Returns a stop code (0 = ok).  NV = 7 (+5 with integrate_eq_gradients).
 // ---------------------------------------------------------------------------------------------
-template <int NS, int NV, bool MULTI = false>
+// LEAN (rays_trace.hpp: rk4_lean_loop): ray_param is not 'arcl' -- the test is compile-time false.
+template <int NS, int NV, bool MULTI = false, bool LEAN = false>
 RAYS_DEV int ray_equations(const DevParams& P, const EqPoint<NS>& eq, const double kvec[3], double v7,
                            const double dddx[3], const double dddk[3], double dddw, double dvds[NV]) {
   if (!(dddw != 0.)) return RAYS_STOP_INFINITE_VG_RHS;  // :133 (`/= 0.` is true for NaN)
@@ -1462,7 +1465,7 @@ RAYS_DEV int ray_equations(const DevParams& P, const EqPoint<NS>& eq, const doub
   for (int i = 0; i < 3; i++) vg[i] = div(-dddk[i], Rw);
   const double vg0 = fsqrt(sq(vg[0]) + sq(vg[1]) + sq(vg[2]));
   double dsd;
-  if (P.ray_param == RAYS_PARAM_ARCL) {  // :150-170
+  if (!LEAN && P.ray_param == RAYS_PARAM_ARCL) {  // :150-170
     if (dddk[0] != 0. || dddk[1] != 0. || dddk[2] != 0.) {
       const double sgn = copysign(1.0, dddw);
       const Recip Rnk = make_recip(fsqrt(sq(dddk[0]) + sq(dddk[1]) + sq(dddk[2])));
@@ -1543,12 +1546,13 @@ RAYS_DEV int eqn_ray(const DevParams& P, const double v[NV], double dvds[NV]) {
 // ---------------------------------------------------------------------------------------------
 //   cond     : (optional) dD/dw of this evaluation -- the denominator of the ray equations, whose collapse within a
 //              step is what the tolerance kernels watch (rays_rk4_body.inc)
-template <int EQ, int NS, int DERIV, int NV>
+//   LEAN     : the three run constants of the lean step loop are compile-time false here (solovev_fields, ray_equations)
+template <int EQ, int NS, int DERIV, int NV, bool LEAN = false>
 RAYS_DEV void rhs_eval(const DevParams& P, const double v[NV], bool do_check, double& resid,
                        int& cs_flag, bool& cs_stop, int& code, double f[NV], double* cond = nullptr) {
   const double rvec[3] = {v[0], v[1], v[2]}, kvec[3] = {v[3], v[4], v[5]};
   EqPoint<NS> eq;
-  equilibrium<EQ, NS>(P, const_recip(P.omgrf, P.inv_omgrf), const_recip(P.omgrf2, P.inv_omgrf2), rvec, eq, true);
+  equilibrium<EQ, NS, LEAN>(P, const_recip(P.omgrf, P.inv_omgrf), const_recip(P.omgrf2, P.inv_omgrf2), rvec, eq, true);
   const Recip Rk0 = const_recip(P.k0, P.inv_k0);
   const double nvec[3] = {div(kvec[0], Rk0), div(kvec[1], Rk0), div(kvec[2], Rk0)};  // eqn_ray.f90:84
   cs_flag = 0;
@@ -1594,7 +1598,7 @@ RAYS_DEV void rhs_eval(const DevParams& P, const double v[NV], bool do_check, do
     }
   }
   if (DERIV == RAYS_DERIV_NUM) deriv_num<EQ, NS>(P, eq, rvec, kvec, dddx, dddk, dddw);
-  const int rc = ray_equations<NS, NV, MULTI>(P, eq, kvec, v[DAMP ? 7 : 0], dddx, dddk, dddw, f);
+  const int rc = ray_equations<NS, NV, MULTI, LEAN>(P, eq, kvec, v[DAMP ? 7 : 0], dddx, dddk, dddw, f);
   code = eq.err ? eq.err : rc;  // eqn_ray.f90:90-102 returns before the derivatives
   if (cond) *cond = dddw;
 }

@@ -143,6 +143,11 @@ extern "C" __attribute__((visibility("default"), used)) inline int* rays_emul_ea
   static int n = 0;
   return &n;
 }
+// ... and the lanes that entered the lean copy of rk4_trace_kernel's step loop (rays_trace.hpp: rk4_lean_loop)
+extern "C" __attribute__((visibility("default"), used)) inline int* rays_emul_lean_loop_lanes() {
+  static int n = 0;
+  return &n;
+}
 inline void uniform_stage_violation(int ray, int lane_stage, int wave_stage) {
   int& n = *rays_emul_uniform_stage_violations();
   if (n++ < 8)
@@ -150,6 +155,20 @@ inline void uniform_stage_violation(int ray, int lane_stage, int wave_stage) {
                  wave_stage);
 }
 #endif
+
+// ---- the lean step loop of the one-wave-per-SIMD kernel ---------------------------------------------------------------
+// Three switches of the Solovev RHS are constants of a RUN -- the density model, the species' temperature models
+// (solovev_fields) and ray_param (ray_equations) -- yet wave-uniform branches on the parameter block inside the unrolled
+// step: they cut every evaluation into a dozen basic blocks with zero-fills, selects and exec-mask regions round the
+// joins, and keep the dead arms in the loop's text.  rk4_trace_kernel therefore holds its body TWICE, and a launch takes
+// one copy: the lean one, compiled with the three tests false (LEAN of rhs_eval, rays_device_arith.inc), when the density
+// model is not 'constant', no species has a parabolic temperature profile (ts = 0 then, as the general code computes it)
+// and ray_param is not 'arcl'; the general one -- the body as it is compiled everywhere else -- otherwise.  Same
+// operations in the same order: the exact kernels' results are bit-identical in both.  One copy runs per launch, so the
+// instruction-cache footprint of a pass is one loop's.  Built where the stage loop is unrolled and the equilibrium is
+// Solovev (rk4_lean_built); every other kernel holds the general body alone.  Same kernel, same name: what a parameter
+// set takes is asked through rays_hip_rk4_loop_for (rays_capi.hip).
+// (rk4_lean_built, rk4_lean_loop: rays_trace.hpp, next to the argument block the switch travels in)
 
 #ifndef RAYS_HOST_EMUL
 // One wave per SIMD (all 256 VGPRs): fastest while the fan has at most one wave per SIMD (<= 64k rays).
@@ -162,7 +181,24 @@ rk4_trace_kernel(const DevParams P_kernarg, const TraceArgs A_hot) {
 #define RAYS_RK4_USE_WINDOW 1
 #endif
 #define RAYS_RK4_LONG_FIRST 1  // pass loop around the trip loop, rays handed out long-first (rays_rk4_body.inc)
+  // the body twice, one copy per launch (rays_trace.hpp: rk4_lean_loop); the selection is made here, once, from kernel
+  // arguments that are dead before the pass loop starts
+  if constexpr (rk4_lean_built(EQ, NS, DERIV)) {
+    if (rk4_lean_loop(P_kernarg, NS, A_hot)) {
+#if defined(RAYS_HOST_EMUL) && defined(RAYS_EMUL_CHECK_UNIFORM_STAGE)
+      ++*rays_emul_lean_loop_lanes();
+#endif
+#define RAYS_RK4_LEAN 1
 #include "rays_rk4_body.inc"
+#undef RAYS_RK4_LEAN
+      return;
+    }
+  }
+  {
+#define RAYS_RK4_LEAN 0
+#include "rays_rk4_body.inc"
+#undef RAYS_RK4_LEAN
+  }
 #undef RAYS_RK4_LONG_FIRST
 #undef RAYS_RK4_USE_WINDOW
 }
@@ -181,7 +217,9 @@ rk4_trace_kernel_w2(const DevParams P_kernarg, const TraceArgs A_hot) {
 #define RAYS_RK4_USE_WINDOW 2  // residual(:) through a 30 KB window, ray_vec stored directly (rays_trace.hpp)
 #endif
 #define RAYS_RK4_LONG_FIRST 0  // one loop, rays in index order: what fits this build's 256 registers (rays_rk4_body.inc)
+#define RAYS_RK4_LEAN 0
 #include "rays_rk4_body.inc"
+#undef RAYS_RK4_LEAN
 #undef RAYS_RK4_LONG_FIRST
 #undef RAYS_RK4_USE_WINDOW
 }
@@ -191,7 +229,9 @@ template <int EQ, int NS, int DERIV, int NV>
 void rk4_trace_kernel_w2(const DevParams P_kernarg, const TraceArgs A_hot) {
 #define RAYS_RK4_USE_WINDOW 2
 #define RAYS_RK4_LONG_FIRST 0
+#define RAYS_RK4_LEAN 0
 #include "rays_rk4_body.inc"
+#undef RAYS_RK4_LEAN
 #undef RAYS_RK4_LONG_FIRST
 #undef RAYS_RK4_USE_WINDOW
 }
@@ -203,7 +243,24 @@ void rk4_trace_kernel(const DevParams P_kernarg, const TraceArgs A_hot) {
 #define RAYS_RK4_USE_WINDOW 1
 #endif
 #define RAYS_RK4_LONG_FIRST 1  // pass loop around the trip loop, rays handed out long-first (rays_rk4_body.inc)
+  // the body twice, one copy per launch (rays_trace.hpp: rk4_lean_loop); the selection is made here, once, from kernel
+  // arguments that are dead before the pass loop starts
+  if constexpr (rk4_lean_built(EQ, NS, DERIV)) {
+    if (rk4_lean_loop(P_kernarg, NS, A_hot)) {
+#if defined(RAYS_HOST_EMUL) && defined(RAYS_EMUL_CHECK_UNIFORM_STAGE)
+      ++*rays_emul_lean_loop_lanes();
+#endif
+#define RAYS_RK4_LEAN 1
 #include "rays_rk4_body.inc"
+#undef RAYS_RK4_LEAN
+      return;
+    }
+  }
+  {
+#define RAYS_RK4_LEAN 0
+#include "rays_rk4_body.inc"
+#undef RAYS_RK4_LEAN
+  }
 #undef RAYS_RK4_LONG_FIRST
 #undef RAYS_RK4_USE_WINDOW
 }

@@ -4,7 +4,10 @@
 // own on purpose: as a device function taking the kernel's by-value arguments by reference it
 // compiled 5 % slower (the by-value kernel arguments were no longer read as plain scalar kernarg
 // loads).  Uses: template parameters EQ, NS, DERIV, NV and the kernel arguments
-// `const DevParams P_kernarg, const TraceArgs A_hot`.
+// `const DevParams P_kernarg, const TraceArgs A_hot`; RAYS_RK4_LEAN: 1 in the copy of rk4_trace_kernel's two that a launch
+// takes when the run's model switches allow it (rays_trace.hpp: rk4_lean_loop) -- its evaluations are compiled with those
+// switches folded -- 0 in every other inclusion.
+  constexpr bool kLean = RAYS_RK4_LEAN != 0;
   DevParams P;  // working copy: scalarised by the compiler, hot constants in vector registers
   hot_params<EQ, NS>(P_kernarg, P);
 #ifndef RAYS_HOST_EMUL
@@ -258,10 +261,10 @@
       // block of its own behind the evaluation it cost the trip four more exec-mask regions and 7 % of the pass)
       double dddw_now = 0.;
       if constexpr (DERIV == RAYS_DERIV_COLD)
-        rhs_eval<EQ, NS, DERIV, NV>(P, w, jw == 3, resid, cs_flag, cs_stop, code, f, &dddw_now);
+        rhs_eval<EQ, NS, DERIV, NV, kLean>(P, w, jw == 3, resid, cs_flag, cs_stop, code, f, &dddw_now);
       else
 #endif
-        rhs_eval<EQ, NS, DERIV, NV>(P, w, jw == 3, resid, cs_flag, cs_stop, code, f);
+        rhs_eval<EQ, NS, DERIV, NV, kLean>(P, w, jw == 3, resid, cs_flag, cs_stop, code, f);
       // The two arms are two if-then regions in sequence, not an if / else: as an if / else the compiler's structured
       // control flow runs the second arm behind a guard AFTER the first, keeps the first arm's inputs alive for it and
       // joins the arms' results by copies (33 64-bit moves per stage-3 trip, 8 per other trip); in sequence each arm

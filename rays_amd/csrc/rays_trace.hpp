@@ -15,6 +15,10 @@
 //     (record_point) or through a per-lane LDS window that emits whole 64-byte sectors (PointWindow).
 #pragma once
 
+#ifdef RAYS_HOST_EMUL
+#include <cstdlib>
+#endif
+
 #include "rays_device.hpp"
 #include "rays_deposition.hpp"  // deposit_segment, DepTraceArgs: the fused deposition variant (kEqDeposit)
 
@@ -160,6 +164,27 @@ RAYS_DEV int take_rays(const TraceArgs& A, unsigned total_lanes, int S, bool wan
   }
   dry = true;  // both sweeps are through and lanes still want: nothing is left
   return got;
+}
+
+// ---- which of its two step loops a launch of rk4_trace_kernel takes (rays_rk4.hpp: the lean step loop) -------------
+// eq, ns, deriv: the kernel's template arguments -- the shapes whose one-wave-per-SIMD kernel holds the lean loop at all
+constexpr bool rk4_lean_built(int eq, int ns, int deriv) {
+  return (eq & 3) == RAYS_EQ_SOLOVEV && deriv == RAYS_DERIV_COLD && (eq & kEqMultiSpec) == 0 && ns <= 2;
+}
+// Developer switch (RAYS_HIP_RK4_LOOP=general, rays_capi.hip) -> "this launch takes the general loop whatever its
+// parameters".  It travels in the sign of TraceArgs::sg_far_lanes, which no RK4 kernel reads and no launcher of one sets
+// (the SG kernels' workspace size: >= 0), so the block keeps its layout.
+constexpr long long kRk4ForceGeneralLoop = -1;
+// ns = species count of the kernel (NS).  Wave-uniform: kernel arguments only.
+__host__ __device__ inline bool rk4_lean_loop(const DevParams& P, int ns, const TraceArgs& A) {
+#ifdef RAYS_HOST_EMUL
+  // (the CPU tier's emulators fill TraceArgs themselves: the developer switch is read here for them)
+  if (const char* f = std::getenv("RAYS_HIP_RK4_LOOP"))
+    if (f[0] == 'g' || f[0] == 'G') return false;
+#endif
+  bool lean = A.sg_far_lanes >= 0 && P.v_n_model != RAYS_SOLOVEV_N_CONSTANT && P.ray_param != RAYS_PARAM_ARCL;
+  for (int is = 0; is < ns; is++) lean = lean && P.v_t_model[is] != RAYS_SOLOVEV_T_PARABOLIC;
+  return lean;
 }
 
 // Start of a ray: initialize_ode_vector (or the caller's v0), the ray parameter and the run's step.

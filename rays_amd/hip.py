@@ -37,6 +37,7 @@ EXPORTED_SYMBOLS = (
     "rays_hip_trace_summary_device", "rays_hip_scan_summary_device", "rays_hip_trace_summary",
     "rays_hip_summary_kernel_name_for",
     "rays_hip_trace_deposition_device", "rays_hip_trace_deposition", "rays_hip_deposition_kernel_name_for",
+    "rays_hip_rk4_loop_for",
 )
 
 _lib = None
@@ -124,6 +125,10 @@ def load():
                                                   dp]
         lib.rays_hip_deposition_kernel_name_for.restype = C.c_char_p
         lib.rays_hip_deposition_kernel_name_for.argtypes = [pp, C.c_int]
+    # (likewise the step-loop query -- an A/B run times the parent commit's library next to this one)
+    if hasattr(lib, "rays_hip_rk4_loop_for"):
+        lib.rays_hip_rk4_loop_for.restype = C.c_int
+        lib.rays_hip_rk4_loop_for.argtypes = [pp, C.c_int]
     lib.rays_hip_ode_step_device.restype = C.c_int
     lib.rays_hip_ode_step_device.argtypes = [pp, C.c_int, vp, vp, vp, vp, vp, vp]
     lib.rays_hip_pack_device.restype = C.c_int
@@ -245,6 +250,18 @@ def kernel_name(p: RaysParams, nray: int = 0) -> str:
         check_params(p)
         raise RaysHipError("rays_hip_kernel_name: no kernel for this configuration")
     return name
+
+
+def rk4_loop(p: RaysParams, nray: int = 0) -> str:
+    """Which of its step loops the RK4 kernel `kernel_name(p, nray)` runs for p: "lean" (the loop compiled for runs whose
+    Solovev density model is not 'constant', whose species have no parabolic temperature profile and whose ray_param is
+    not 'arcl') or "general".  The kernel's name is the same for both.  RAYS_HIP_RK4_LOOP=general in the environment
+    (read by the library at every launch) forces the general loop."""
+    which = load().rays_hip_rk4_loop_for(C.byref(p), int(nray))
+    if which < 0:
+        check_params(p)
+        raise RaysHipError("rays_hip_rk4_loop_for: not an RK4 configuration")
+    return "lean" if which else "general"
 
 
 def summary_kernel_name(p: RaysParams, nray: int = 0) -> str:
