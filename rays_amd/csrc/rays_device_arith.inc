@@ -991,10 +991,19 @@ RAYS_DEV void equilibrium(const DevParams& P, const Recip& Romgrf, const Recip& 
   for (int i = 0; i < 3; i++) eq.gradts0[i] = gradts[0][i];
 }
 
+#if defined(RAYS_TOL_FLAVOUR) && !defined(RAYS_HOST_EMUL)
+#include "rays_cold_adjoint.inc"
+#endif
+
 // deriv_cold                deriv_cold.f90:1-228
+//   idx : (tolerance flavour only, optional) {n3, n1**2} of this evaluation, for check_save's residual (rhs_eval)
 template <int NS>
 RAYS_DEV void deriv_cold(const DevParams& P, const EqPoint<NS>& eq, const double nvec[3],
-                         double dddx[3], double dddk[3], double& dddw) {
+                         double dddx[3], double dddk[3], double& dddw
+#if defined(RAYS_TOL_FLAVOUR) && !defined(RAYS_HOST_EMUL)
+                         , double* idx = nullptr
+#endif
+                         ) {
   const Recip Rk0 = const_recip(P.k0, P.inv_k0);
   double alpha[NS], gamma[NS];
 #pragma unroll
@@ -1013,17 +1022,20 @@ RAYS_DEV void deriv_cold(const DevParams& P, const EqPoint<NS>& eq, const double
   const double n1 = fsqrt(sq(np[0]) + sq(np[1]) + sq(np[2]));  // :46
 #define RAYS_N1_SQ sq(n1)
 #endif
+#if defined(RAYS_TOL_FLAVOUR) && !defined(RAYS_HOST_EMUL)
+  // the chain-rule tables of :50-75 (dn3dk .. dgdw) are not formed: their common factors are taken out below
+  (void)Rk0;
+  if (idx) {
+    idx[0] = n3;
+    idx[1] = n1_2;
+  }
+#else
   double dn3dk[3], dn12dk[3], dn3dx[3], dn12dx[3];
 #pragma unroll
   for (int i = 0; i < 3; i++) {
     dn3dk[i] = div(eq.bunit[i], Rk0);         // :50
     dn12dk[i] = P.two_over_k0 * np[i];        // :51
-#if defined(RAYS_TOL_FLAVOUR) && !defined(RAYS_HOST_EMUL)
-    // grad(b_j) n_j = (dB_j/dx_i n_j - d|B|/dx_i (b . n)) / |B|: three quotients instead of the nine of gradbunit (:54-56)
-    dn3dx[i] = div((eq.gbt[i][0] * nvec[0] + eq.gbt[i][1] * nvec[1] + eq.gbt[i][2] * nvec[2]) - eq.gradbmag[i] * n3, eq.rbmag);
-#else
     dn3dx[i] = eq.gradbunit[i][0] * nvec[0] + eq.gradbunit[i][1] * nvec[1] + eq.gradbunit[i][2] * nvec[2];
-#endif
     dn12dx[i] = -2. * n3 * dn3dx[i];          // :57
   }
   double dadx[3][NS], dgdx[3][NS];
@@ -1044,6 +1056,7 @@ RAYS_DEV void deriv_cold(const DevParams& P, const EqPoint<NS>& eq, const double
     dadw[is] = P.m2_over_omgrf * alpha[is];  // :74
     dgdw[is] = P.m1_over_omgrf * gamma[is];  // :75
   }
+#endif
   double sa = 0.;
 #pragma unroll
   for (int is = 0; is < NS; is++) sa += alpha[is];
@@ -1073,7 +1086,7 @@ RAYS_DEV void deriv_cold(const DevParams& P, const EqPoint<NS>& eq, const double
   const double u = t - su;               // :98
   const double q = 2. * u - t + q1 * q2; // :101
 #if defined(RAYS_TOL_FLAVOUR) && !defined(RAYS_HOST_EMUL)
-  const double n3_2 = sq(n3), n3_4 = sq(n3_2), n1_4 = sq(n1_2);
+  const double n3_2 = sq(n3);
 #else
   const double n3_2 = sq(n3), n3_4 = pow4(n3), n1_2 = sq(n1), n1_4 = pow4(n1);
 #endif
@@ -1083,8 +1096,12 @@ RAYS_DEV void deriv_cold(const DevParams& P, const EqPoint<NS>& eq, const double
   for (int is = 0; is < NS; is++) {  // :104-112
     duda[is] = -dq1da[is] * dq2da[is];
     dqda[is] = 2. * duda[is] + dq1da[is] * q2 + q1 * dq2da[is];
+#if defined(RAYS_TOL_FLAVOUR) && !defined(RAYS_HOST_EMUL)
+    // ddda[is]: cold_adjoint below, with dddg[is]
+#else
     ddda[is] = -t * n3_4 + (2. * (u - p * duda[is]) + (-t + duda[is]) * n1_2) * n3_2 - q +
                p * dqda[is] - (dqda[is] - u + p * duda[is]) * n1_2 + duda[is] * n1_4;
+#endif
   }
   double gp[NS][NS], gm[NS][NS], gpm[NS][NS];
 #pragma unroll
@@ -1118,9 +1135,15 @@ RAYS_DEV void deriv_cold(const DevParams& P, const EqPoint<NS>& eq, const double
     dq1dg[is] = b - alpha[is] * dq1da[is];                              // :140
     dq2dg[is] = -c + alpha[is] * dq2da[is];                             // :146
     dqdg[is] = 2. * dudg[is] - dtdg[is] + dq1dg[is] * q2 + q1 * dq2dg[is];  // :149
+#if defined(RAYS_TOL_FLAVOUR) && !defined(RAYS_HOST_EMUL)
+  }
+  // :104-112 and :152-154 are partial derivatives of one polynomial: its four partials once, the chain rule per species
+  cold_adjoint<NS>(p, t, u, q, n1_2, n3_2, duda, dqda, dtdg, dudg, dqdg, ddda, dddg);
+#else
     dddg[is] = dtdg[is] * p * n3_4 + (-2. * p * dudg[is] + (dtdg[is] * p + dudg[is]) * n1_2) * n3_2 +
                p * dqdg[is] - (dqdg[is] + p * dudg[is]) * n1_2 + dudg[is] * n1_4;  // :152-154
   }
+#endif
   const double dddn3 = (4. * t * p * n3_2 + 2. * (-2. * p * u + (t * p + u) * n1_2)) * n3;  // :157
   const double dddn12 = (t * p + u) * n3_2 - (q + p * u) + 2. * u * n1_2;                   // :158
 #if defined(RAYS_TOL_FLAVOUR) && !defined(RAYS_HOST_EMUL)
@@ -1128,23 +1151,30 @@ RAYS_DEV void deriv_cold(const DevParams& P, const EqPoint<NS>& eq, const double
   //   dn3/dk = b / k0, dn1**2/dk = (2 / k0) n_perp;   dn1**2/dx = -2 n3 dn3/dx;   dgamma_s/dx = gamma_s grad|B| / |B|;
   //   d/dw: dalpha_s = (-2/w) alpha_s, dgamma_s = (-1/w) gamma_s, dn3 = (-1/w) n3, dn1**2 = (-2/w) n1**2
   // (a third fewer multiplications than the term-by-term sums; same value to rounding).
-  double wg = 0., wa = 0.;
+  // The gradient takes the factors out once more, so that neither dalpha_s/dx nor dn3/dx is formed per component:
+  //   dalpha_s/dx = (alpha_s / n_s) grad n_s  ->  e_s = dD/dalpha_s alpha_s / n_s   (outside the plasma 0 * inf = NaN, as :64)
+  //   dn3/dx = (grad(B) . n - n3 grad|B|) / |B| (three quotients instead of the nine of gradbunit, :54-56)
+  //   ->  dD/dx = sum_s e_s grad n_s + (c3 grad(B) . n + (wg - c3 n3) grad|B|) / |B|
+  double wg = 0., wa = 0., e[NS];
 #pragma unroll
   for (int is = 0; is < NS; is++) {
     wg += dddg[is] * gamma[is];
     wa += ddda[is] * alpha[is];
+    const Recip Rns = make_recip(eq.ns[is]);
+    e[is] = ddda[is] * (alpha[is] * Rns.rc);
   }
   const double c3 = dddn3 - 2. * n3 * dddn12, twon12 = 2. * dddn12;
+  const double cg = wg - c3 * n3;
 #pragma unroll
   for (int i = 0; i < 3; i++) {
     dddk[i] = P.inv_k0 * (dddn3 * eq.bunit[i] + twon12 * np[i]);
+    const double gn = eq.gbt[i][0] * nvec[0] + eq.gbt[i][1] * nvec[1] + eq.gbt[i][2] * nvec[2];
     double a = 0.;
 #pragma unroll
-    for (int is = 0; is < NS; is++) a += ddda[is] * dadx[i][is];
-    dddx[i] = a + wg * (eq.gradbmag[i] * eq.rbmag.rc) + c3 * dn3dx[i];
+    for (int is = 0; is < NS; is++) a += e[is] * eq.gradns[is][i];
+    dddx[i] = a + eq.rbmag.rc * (c3 * gn + cg * eq.gradbmag[i]);
   }
   dddw = P.m1_over_omgrf * (2. * wa + wg + dddn3 * n3 + twon12 * n1_2);
-  (void)dn3dk; (void)dn12dk; (void)dn12dx; (void)dgdx; (void)dadw; (void)dgdw; (void)dn3dw; (void)dn12dw;
 #else
 #pragma unroll
   for (int i = 0; i < 3; i++) {
@@ -1558,6 +1588,36 @@ RAYS_DEV void rhs_eval(const DevParams& P, const double v[NV], bool do_check, do
   cs_flag = 0;
   cs_stop = false;
   resid = 0.;
+#if defined(RAYS_TOL_FLAVOUR) && !defined(RAYS_HOST_EMUL)
+  // Tolerance flavour (cold derivatives only): the residual of :163-235 from the index components deriv_cold has
+  // already formed at this state, n3 = n . b and n1**2 = |n - n3 b|**2 -- n1 enters the determinant and its norm only
+  // squared, so check_save's own k3, k1 (:53-57: a root and two quotients) are not needed.  With nsq = n1**2 + n3**2
+  // and the terms that carry a literal zero factor dropped:
+  //   E11 = e11 - n3**2, E22 = e11 - nsq, E33 = e33 - n1**2, E13**2 = n1**2 n3**2;  N13**2 = n1**2 n3**2, N23 = 0
+  // The flags are latched in check_save's order: eq.err, the residual limit, tiny(dddw).
+  static_assert(DERIV == RAYS_DERIV_COLD, "the tolerance flavour exists for the cold derivatives only");
+  double dddx[3], dddk[3], dddw, idx[2];
+  deriv_cold<NS>(P, eq, nvec, dddx, dddk, dddw, idx);  // eqn_ray.f90:111 / check_save.f90:82
+  if (do_check) {
+    cs_flag = eq.err;  // check_save.f90:41-43: flag text only
+    const double n3_2 = sq(idx[0]), n1_2 = idx[1], x13 = n1_2 * n3_2;
+    double e11, e33, x12;
+    eps_cold<NS>(eq.alpha, eq.gamma, e11, e33, x12);
+    const double E11 = e11 - n3_2, E22 = E11 - n1_2, E33 = e33 - n1_2;
+    const double det = E33 * (E11 * E22 - x12 * x12) - E22 * x13;
+    const double N11 = fabs(e11) + n1_2, N22 = fabs(e11), N33 = fabs(e33) + n3_2, N12 = fabs(x12);
+    const double den = N33 * (N11 * N22) + N33 * (N12 * N12) + N22 * x13;
+    resid = divdc3_real(fabs(det), den);  // eps_norm is complex(rkind) -> __divdc3
+    if (resid > P.resid_limit) {          // :68-71
+      cs_stop = true;
+      cs_flag = RAYS_STOP_DISP_RESIDUAL;
+    }
+    if (!(fabs(dddw) > 2.2250738585072014e-308)) {  // check_save.f90:90 tiny(dddw)
+      cs_stop = true;
+      cs_flag = RAYS_STOP_INFINITE_VG_CHECK;  // :107-108
+    }
+  }
+#else
   if (do_check) {
     cs_flag = eq.err;  // check_save.f90:41-43: flag text only
     // :53-57
@@ -1589,6 +1649,7 @@ RAYS_DEV void rhs_eval(const DevParams& P, const double v[NV], bool do_check, do
       cs_flag = RAYS_STOP_INFINITE_VG_CHECK;  // :107-108
     }
   }
+#endif
   constexpr bool MULTI = (EQ & kEqMultiSpec) != 0;
   constexpr bool DAMP = RayVec<MULTI, NS, NV>::DAMP;
   if (do_check && DAMP) {  // check_save.f90:114-125
