@@ -66,6 +66,14 @@
         type(c_ptr) :: ti_grid, ti_fspl
     end type rays_axisym_tables_t
 
+    ! The saved ray state of windowed tracing (include/rays_hip.h: rays_ray_state_t): device pointers, in Fortran order
+    ! v(nv, nray), s(nray), nstep(nray), stop_code(nray), resid(3, nray), sg_err(2, nray) (c_null_ptr allowed for RK4_ODE),
+    ! flags(nray).  The caller owns the arrays and may copy them to disk and back.
+    integer(c_int32_t), parameter :: RAYS_STATE_REFUSED = 1
+    type, bind(C) :: rays_ray_state_t
+        type(c_ptr) :: v, s, nstep, stop_code, resid, sg_err, flags
+    end type rays_ray_state_t
+
     type, bind(C) :: rays_params_t
         integer(c_int32_t) :: abi_version
         integer(c_int32_t) :: nv, nspec, nstep_max
@@ -281,6 +289,65 @@
           real(c_double), intent(inout) :: start_ray_vec(*), end_ray_vec(*), end_residuals(*), max_residuals(*)
           real(c_double), intent(out) :: elapsed_s
        end function rays_hip_trace_summary
+
+       ! Windowed tracing (include/rays_hip.h): rays are paused after n_steps recorded steps and continued from the saved
+       ! state.  Device pointers, asynchronous on hip_stream.  state_init: initialize_ode_vector and the initial check_save
+       ! for every ray, point 1 into d_start_ray_vec(nv, nray) (c_null_ptr: not wanted).
+       integer(c_int) function rays_hip_state_init_device(p, nray, d_rvec0, d_rindex_vec0, state, d_start_ray_vec, &
+                    & hip_stream) bind(C, name='rays_hip_state_init_device')
+          import :: c_int, c_ptr, rays_params_t, rays_ray_state_t
+          type(rays_params_t), intent(in) :: p
+          integer(c_int), value :: nray
+          type(c_ptr), value :: d_rvec0, d_rindex_vec0
+          type(rays_ray_state_t), intent(in) :: state
+          type(c_ptr), value :: d_start_ray_vec, hip_stream
+       end function rays_hip_state_init_device
+
+       ! One window: d_ray_vec_win(nv, n_steps, nray), d_residual_win(n_steps, nray) receive the points recorded by this
+       ! call alone, d_npoints_win(nray) their number (0 for a ray that had ended); both window arrays c_null_ptr: a summary
+       ! window.  The state is updated in place.  nstep_max and s_max stay limits of the whole ray.
+       integer(c_int) function rays_hip_trace_window_device(p, nray, state, n_steps, d_ray_vec_win, d_residual_win, &
+                    & d_npoints_win, hip_stream) bind(C, name='rays_hip_trace_window_device')
+          import :: c_int, c_ptr, rays_params_t, rays_ray_state_t
+          type(rays_params_t), intent(in) :: p
+          integer(c_int), value :: nray, n_steps
+          type(rays_ray_state_t), intent(in) :: state
+          type(c_ptr), value :: d_ray_vec_win, d_residual_win, d_npoints_win, hip_stream
+       end function rays_hip_trace_window_device
+
+       ! The five per-ray summary arrays of ray_results_m from the state (rays under way as they stand).
+       integer(c_int) function rays_hip_state_summary_device(p, nray, state, d_npoints, d_stop_code, d_end_ray_vec, &
+                    & d_end_residuals, d_max_residuals, hip_stream) bind(C, name='rays_hip_state_summary_device')
+          import :: c_int, c_ptr, rays_params_t, rays_ray_state_t
+          type(rays_params_t), intent(in) :: p
+          integer(c_int), value :: nray
+          type(rays_ray_state_t), intent(in) :: state
+          type(c_ptr), value :: d_npoints, d_stop_code, d_end_ray_vec, d_end_residuals, d_max_residuals, hip_stream
+       end function rays_hip_state_summary_device
+
+       ! Blocking, host arrays: rays_hip_trace's arguments and results, traced in windows of n_steps on one device (the
+       ! device holds the state and two window slabs, whatever nstep_max is).  The three summary arrays are type(c_ptr)
+       ! so that c_null_ptr can stand for "not wanted" (else c_loc(array)).
+       integer(c_int) function rays_hip_trace_windowed(p, nray, rvec0, rindex_vec0, n_steps, ray_vec, residual, npoints, &
+                    & stop_code, end_ray_vec, end_residuals, max_residuals, elapsed_s) &
+                    & bind(C, name='rays_hip_trace_windowed')
+          import :: c_int, c_int32_t, c_double, c_ptr, rays_params_t
+          type(rays_params_t), intent(in) :: p
+          integer(c_int), value :: nray, n_steps
+          real(c_double), intent(in) :: rvec0(3,*), rindex_vec0(3,*)
+          real(c_double), intent(inout) :: ray_vec(*), residual(*)
+          integer(c_int32_t), intent(inout) :: npoints(*), stop_code(*)
+          type(c_ptr), value :: end_ray_vec, end_residuals, max_residuals
+          real(c_double), intent(out) :: elapsed_s
+       end function rays_hip_trace_windowed
+
+       ! Name of the kernel a window launches (recording /= 0: with window arrays); c_null_char-terminated C string.
+       type(c_ptr) function rays_hip_window_kernel_name_for(p, nray, recording) &
+                    & bind(C, name='rays_hip_window_kernel_name_for')
+          import :: c_int, c_ptr, rays_params_t
+          type(rays_params_t), intent(in) :: p
+          integer(c_int), value :: nray, recording
+       end function rays_hip_window_kernel_name_for
 
        ! Fused trace and deposition (include/rays_hip.h): the summary-only trace that also bins every accepted point, so
        ! the absorbed-power profile exists without ray_vec(:,:,:).  Device pointers, asynchronous on hip_stream; d_work is

@@ -392,6 +392,82 @@ int rays_hip_trace_deposition(const rays_params_t* p, int nray, const double* rv
 /* Name of the kernel the fused entries launch for a fan of nray rays ("" when p is refused or has no such kernel). */
 const char* rays_hip_deposition_kernel_name_for(const rays_params_t* p, int nray);
 
+/* ---- windowed tracing: pause rays after n steps, continue from a saved state ---------------------------------------
+ * Every entry above runs a ray from its launch point to its end in one launch, so whoever wants trajectories holds
+ * ray_vec[nray][nstep_max+1][nv] on the device at once.  These entries advance a fan in WINDOWS of at most n_steps
+ * recorded steps per ray: between two windows everything a ray needs to go on is in a saved state, a struct of device
+ * arrays the caller owns (and may copy to disk and back: nothing in it is an address or depends on the launch):
+ *   v[nray][nv]        the ray's last recorded point (of an ended ray: the state the reference leaves in v)
+ *   s[nray]            sout as ray_tracing.f90:118 finds it at the top of the next trip, not yet advanced
+ *   nstep[nray]        steps taken and recorded so far (npoints - 1)
+ *   stop_code[nray]    RAYS_STOP_NONE: under way; else the ray has ended with this code
+ *   resid[nray][3]     residual of the last recorded point, of the one before, running max |residual|
+ *                      (ray_tracing.f90:252-260: end_residuals, max_residuals)
+ *   sg_err[nray][2]    SG_ODE: ray_stop%rel_err, %abs_err, which persist and grow across output steps
+ *                      (SG_ode_m.f90:115-126) and are reset only by ray_init_ode_solver.  Required for SG_ODE; may be
+ *                      NULL for RK4_ODE.
+ *   flags[nray]        bit 0 (RAYS_STATE_REFUSED): the initial check_save refused the ray -- npoints 1 and every summary
+ *                      field zero, unlike a ray that started and ended on its first step (npoints 1, end_ray_vec = v)
+ * A ray that is under way is exactly where trace_rays stands at ray_tracing.f90:116, before any of the three tests of
+ * the next trip: nstep steps taken and recorded, v the last recorded point, s not yet advanced.
+ *
+ * rays_hip_state_init_device   initialize_ode_vector and the initial check_save (ray_tracing.f90:77-112) for every ray;
+ *                              a refused ray gets its stop code here.  d_start_ray_vec[nray][nv] (may be NULL) is point
+ *                              1 of every ray; its residual is 0.
+ * rays_hip_trace_window_device advances every ray under way by at most n_steps recorded steps and updates the state in
+ *                              place.  d_ray_vec_win[nray][n_steps][nv], d_residual_win[nray][n_steps] receive only the
+ *                              points recorded by this call (not zero-filled beyond them), d_npoints_win[nray] their
+ *                              number: 0 for a ray that had ended before.  Both window arrays NULL: the summary policy
+ *                              -- nothing that scales with n_steps or nstep_max exists anywhere.  p->nstep_max and
+ *                              p->s_max stay limits of the WHOLE ray: ' nstep > nstep_max' is given when the ray's own
+ *                              count reaches nstep_max, never at a window's end.
+ * rays_hip_state_summary_device the five per-ray summary arrays of rays_hip_trace_device from the state; rays under
+ *                              way are included as they stand.
+ * CONTRACT: point 1 followed by the windows' points equals one rays_hip_trace_device call bit for bit -- ray_vec,
+ * residual, npoints, stop_code -- for any sequence of n_steps >= 1, recording and summary windows mixed freely, and the
+ * summaries after the last window equal rays_hip_trace_summary_device's.  Once every ray has ended, further calls
+ * change no byte of the state and return npoints_win = 0.
+ * KERNELS: the one-ray-per-lane trace kernel of the shape, compiled with the continuation bit (EQ + 128 in the name;
+ * EQ + 160 for the summary policy), whatever the fan size -- bit-identical to the two-waves-per-SIMD and lane-group
+ * kernels.  Always exact, whatever rays_hip_set_numerics says (see the summary entries).  Built for every shape the
+ * library traces.
+ * Asynchronous on hip_stream.  Refused by name, before anything is launched: n_steps < 1, nray < 0, a null required
+ * pointer, sg_err == NULL with SG_ODE, only one of the two window arrays, a shape that is not built.
+ * OUT OF SCOPE: continuing the fused deposition variant or the fused ds scan; a tolerance flavour; re-opening a ray
+ * that ended with ' nstep > nstep_max' under a larger nstep_max (its s has been advanced). */
+#define RAYS_STATE_REFUSED 1
+typedef struct rays_ray_state {
+  double* v;          /* [nray][nv] */
+  double* s;          /* [nray] */
+  int32_t* nstep;     /* [nray] */
+  int32_t* stop_code; /* [nray] */
+  double* resid;      /* [nray][3] */
+  double* sg_err;     /* [nray][2]; may be NULL for RK4_ODE */
+  int32_t* flags;     /* [nray] */
+} rays_ray_state_t;
+int rays_hip_state_init_device(const rays_params_t* p, int nray, const double* d_rvec0, const double* d_rindex_vec0,
+                               const rays_ray_state_t* state, double* d_start_ray_vec /* may be NULL */,
+                               void* hip_stream);
+int rays_hip_trace_window_device(const rays_params_t* p, int nray, const rays_ray_state_t* state, int n_steps,
+                                 double* d_ray_vec_win /* NULL with d_residual_win: summary policy */,
+                                 double* d_residual_win, int32_t* d_npoints_win, void* hip_stream);
+int rays_hip_state_summary_device(const rays_params_t* p, int nray, const rays_ray_state_t* state, int32_t* d_npoints,
+                                  int32_t* d_stop_code, double* d_end_ray_vec, double* d_end_residuals,
+                                  double* d_max_residuals, void* hip_stream);
+/* Name of the kernel rays_hip_trace_window_device launches (recording != 0: with window arrays; 0: summary policy);
+ * "" when p is refused or has no such kernel. */
+const char* rays_hip_window_kernel_name_for(const rays_params_t* p, int nray, int recording);
+/* Host pointers, blocking: the arguments and the results of rays_hip_trace, bit for bit (entries past npoints are left
+ * as the caller passed them), traced in windows of n_steps.  Device memory is the ray state, two window slabs
+ * [nray][n_steps][nv + 1] and the inputs, whatever nstep_max is; window k is copied out (whole slabs, through pinned
+ * staging buffers of one slab each) and scattered into the caller's arrays while window k + 1 runs.  One device: the
+ * first of rays_hip_init[_devices].  Uses rays_hip_trace's resource owners -- everything is freed by
+ * rays_hip_finalize.  A device image kept by rays_hip_keep_last_result is dropped and none is left. */
+int rays_hip_trace_windowed(const rays_params_t* p, int nray, const double* rvec0, const double* rindex_vec0,
+                            int n_steps, double* ray_vec, double* residual, int32_t* npoints, int32_t* stop_code,
+                            double* end_ray_vec /* may be NULL */, double* end_residuals /* may be NULL */,
+                            double* max_residuals /* may be NULL */, double* elapsed_s /* may be NULL */);
+
 /* ---- one output step from arbitrary states: the ode_m interface --------------------------------
  * Batched image of `call ode_solver(eqn_ray, nv, v, s, sout, ray_stop)` (ode_m.f90:218-254, with
  * sout = s + ds and, for SG_ODE, ray_stop%rel_err/abs_err at rel_err0/abs_err0 as after

@@ -51,9 +51,17 @@ namespace rays {
 // the fused deposition variants (rays_device_arith.inc: kEqDeposit) of the slab and axisym_toroid groups (Makefile:
 // DEP_OBJS).  Weak for the same reason; no library defines those of the Solovev groups, which are null everywhere.
 #define RAYS_DECL_DEP(s, e, d) RAYS_DECL_ENTRIES(__attribute__((weak)), rays_entries_dep_, s, e, d)
+// the continuation variants (rays_device_arith.inc: kEqContinue; windowed tracing), recording and summary-only
+// (Makefile: WIN_OBJS).  Weak for the same reason.
+#define RAYS_DECL_WIN(s, e, d) RAYS_DECL_ENTRIES(__attribute__((weak)), rays_entries_win_, s, e, d)
+#define RAYS_DECL_WSUM(s, e, d) RAYS_DECL_ENTRIES(__attribute__((weak)), rays_entries_wsum_, s, e, d)
 RAYS_GROUPS(RAYS_DECL_REC)
 RAYS_GROUPS(RAYS_DECL_SUM)
 RAYS_GROUPS(RAYS_DECL_DEP)
+RAYS_GROUPS(RAYS_DECL_WIN)
+RAYS_GROUPS(RAYS_DECL_WSUM)
+#undef RAYS_DECL_WIN
+#undef RAYS_DECL_WSUM
 #undef RAYS_DECL_REC
 #undef RAYS_DECL_SUM
 #undef RAYS_DECL_DEP
@@ -159,7 +167,10 @@ std::atomic<int> g_numerics{initial_numerics()};
 //              tolerance kernels' hand-over reads residual(:)).  Its objects hold the same shapes as the recording ones
 //              (rays_inst.hip), so a configuration is traced summary-only exactly when it is traced at all.
 //   Deposit    the fused deposition variant of the summary-only kernel (slab and axisym_toroid groups)
-enum class KernelVariant { Recording, ExactTwin, Summary, Deposit };
+//   Window, WindowSummary
+//              the continuation variant (windowed tracing) of the exact kernel, recording or summary-only: always the
+//              one-ray-per-lane entry, whatever the fan size -- the only one built, and bit-identical to the others
+enum class KernelVariant { Recording, ExactTwin, Summary, Deposit, Window, WindowSummary };
 
 // nray: fan size (0 = unknown).  From two waves per SIMD worth of rays on, the two-waves-per-SIMD build
 // of the kernel is preferred where one exists (rays_rk4.hpp) -- under the tolerance flavour for the slab only: the
@@ -169,9 +180,9 @@ const rays::KernelEntry* find_kernel(const rays_params_t& p, long long nray = 0,
                                      KernelVariant variant = KernelVariant::Recording) {
   using namespace rays;
   typedef const KernelEntry* (*Getter)(int*);
-  // [recording | summary | deposit][solver][equilibrium][derivative][unit exponents][multi_spec_damping]
+  // [recording | summary | deposit | window | window summary][solver][equilibrium][derivative][unit exponents][multi_spec_damping]
   struct Table {
-    Getter g[3][2][3][2][2][2];
+    Getter g[5][2][3][2][2][2];
   };
   static const Table table = [] {
     Table t = {};
@@ -179,7 +190,8 @@ const rays::KernelEntry* find_kernel(const rays_params_t& p, long long nray = 0,
   t.g[v][s][e][d][0][0] = prefix##s##_##e##_##d##_0_0; t.g[v][s][e][d][0][1] = prefix##s##_##e##_##d##_0_1; \
   t.g[v][s][e][d][1][0] = prefix##s##_##e##_##d##_1_0; t.g[v][s][e][d][1][1] = prefix##s##_##e##_##d##_1_1;
 #define RAYS_FILL_ALL(s, e, d) \
-  RAYS_FILL(0, rays_entries_, s, e, d) RAYS_FILL(1, rays_entries_sum_, s, e, d) RAYS_FILL(2, rays_entries_dep_, s, e, d)
+  RAYS_FILL(0, rays_entries_, s, e, d) RAYS_FILL(1, rays_entries_sum_, s, e, d) RAYS_FILL(2, rays_entries_dep_, s, e, d) \
+  RAYS_FILL(3, rays_entries_win_, s, e, d) RAYS_FILL(4, rays_entries_wsum_, s, e, d)
     RAYS_GROUPS(RAYS_FILL_ALL)
 #undef RAYS_FILL_ALL
 #undef RAYS_FILL
@@ -193,7 +205,8 @@ const rays::KernelEntry* find_kernel(const rays_params_t& p, long long nray = 0,
   const bool force_exact = variant == KernelVariant::ExactTwin;
   const bool tol = variant == KernelVariant::Recording && g_numerics.load() == RAYS_NUMERICS_TOLERANCE &&
                    p.ode_solver == RAYS_ODE_RK4 && p.ray_deriv == RAYS_DERIV_COLD && !p.multi_spec_damping;
-  const int row = variant == KernelVariant::Summary ? 1 : variant == KernelVariant::Deposit ? 2 : 0;
+  const int row = variant == KernelVariant::Summary ? 1 : variant == KernelVariant::Deposit ? 2
+                  : variant == KernelVariant::Window ? 3 : variant == KernelVariant::WindowSummary ? 4 : 0;
   const Getter getter = tol ? tol_getters[p.equilib_model][unit_exponents(p) ? 1 : 0]
                             : table.g[row][p.ode_solver][p.equilib_model][p.ray_deriv][unit_exponents(p) ? 1 : 0]
                                      [p.multi_spec_damping ? 1 : 0];
@@ -681,9 +694,15 @@ struct TraceExtras {
   int rays_per_run = 0;
   // KernelVariant::Deposit: the device block the kernel reads its binning arguments from
   const rays::DepTraceArgs* dep = nullptr;
+  // KernelVariant::Window | WindowSummary: the saved ray state and the window's length (rays_trace.hpp:
+  // TraceArgs::state); state_init: launch the shape's state_init kernel instead of the trace kernel
+  const rays::TraceArgs::State* state = nullptr;
+  int n_steps = 0;
+  bool state_init = false;
 };
 // variant: Recording (into `traj`), Summary or Deposit (no trajectory arrays; out.sv is optional).  out.ev, out.er and
-// out.mr are optional for a recording launch.
+// out.mr are optional for a recording launch.  Window (into the slabs `traj`) | WindowSummary: out.np is npoints_win and
+// the other summaries live in extra.state.
 int launch_trace(const rays_params_t* p, KernelVariant variant, int nray, const RayInputs& in,
                  const TrajectoryArrays& traj, const SummaryArrays& out, hipStream_t stream, int flags,
                  const TraceExtras& extra = TraceExtras()) {
@@ -702,8 +721,9 @@ int launch_trace(const rays_params_t* p, KernelVariant variant, int nray, const 
   A.nray = nray;
   A.rvec0 = in.rvec0;
   A.rindex_vec0 = in.rindex_vec0;
-  A.ray_vec = recording ? traj.rv : nullptr;
-  A.residual = recording ? traj.res : nullptr;
+  const bool window = variant == KernelVariant::Window || variant == KernelVariant::WindowSummary;
+  A.ray_vec = recording || variant == KernelVariant::Window ? traj.rv : nullptr;
+  A.residual = recording || variant == KernelVariant::Window ? traj.res : nullptr;
   A.npoints = out.np;
   A.stop_code = out.sc;
   A.end_ray_vec = out.ev;
@@ -720,11 +740,21 @@ int launch_trace(const rays_params_t* p, KernelVariant variant, int nray, const 
   A.sched_stride = 0;
   A.set_start_ray_vec(recording ? nullptr : out.sv);
   if (variant == KernelVariant::Deposit) A.set_dep(extra.dep);
+  if (window) A.set_state(*extra.state, extra.n_steps);
   const rays::KernelEntry* kernel = find_kernel(*p, nray, variant);
-  if (!kernel)
-    return fail(variant == KernelVariant::Deposit
+  if (!kernel || (extra.state_init && !kernel->resume))
+    return fail(window ? "rays_hip: the continuation kernel of this configuration is not in this build"
+                : variant == KernelVariant::Deposit
                     ? "rays_hip: the fused deposition kernel of this configuration is not in this build"
                     : "rays_hip: the summary-only kernel of this configuration is not in this build");
+  if (extra.state_init) {  // one lane per ray, no refill: neither the counter nor a workspace is used
+    rays::DevParams Di = make_dev_params(*p);
+    rc = device_tables(p, &Di);
+    if (rc) return rc;
+    const hipError_t ei = kernel->resume(Di, A, stream);
+    if (ei != hipSuccess) return hip_fail(ei, "state_init kernel launch");
+    return counter_launched(counter_slot, stream);
+  }
   const int stride = kernel->solver == RAYS_ODE_RK4 ? sched_stride() : 0;
   if (kernel->solver == RAYS_ODE_RK4 && rk4_loop_forced_general()) A.sg_far_lanes = rays::kRk4ForceGeneralLoop;
   if (stride > 1) {
@@ -871,6 +901,105 @@ int rays_hip_scan_summary_device(const rays_params_t* p, int n_runs, const doubl
   return launch_trace(p, KernelVariant::Summary, n_runs * nray, {d_rvec0, d_rindex_vec0}, {},
                       {d_npoints, d_stop_code, d_start_ray_vec, d_end_ray_vec, d_end_residuals, d_max_residuals},
                       (hipStream_t)hip_stream, RAYS_TRACE_NO_ZERO_FILL, x);
+}
+
+// ---- windowed tracing: pause rays after n steps, continue from a saved state (include/rays_hip.h) ----
+namespace {
+int refuse_state(const char* who, const rays_params_t* p, int nray, const rays_ray_state_t* st) {
+  if (nray < 0) return fail(std::string(who) + ": nray < 0");
+  if (!st || !st->v || !st->s || !st->nstep || !st->stop_code || !st->resid || !st->flags)
+    return fail(std::string(who) + ": null pointer in the ray state");
+  if (p->ode_solver == RAYS_ODE_SG && !st->sg_err)
+    return fail(std::string(who) + ": SG_ODE needs the ray state's sg_err (rel_err, abs_err persist across output steps)");
+  return 0;
+}
+rays::TraceArgs::State state_of(const rays_ray_state_t* st) {
+  return rays::TraceArgs::State{st->v, st->s, st->nstep, st->stop_code, st->resid, st->sg_err, st->flags};
+}
+}  // namespace
+
+int rays_hip_state_init_device(const rays_params_t* p, int nray, const double* d_rvec0, const double* d_rindex_vec0,
+                               const rays_ray_state_t* state, double* d_start_ray_vec, void* hip_stream) {
+  int rc = rays_hip_check_params(p);
+  if (rc) return rc;
+  rc = refuse_state("rays_hip_state_init_device", p, nray, state);
+  if (rc) return rc;
+  if (!d_rvec0 || !d_rindex_vec0) return fail("rays_hip_state_init_device: null device pointer");
+  if (nray == 0) return 0;
+  const rays::TraceArgs::State st = state_of(state);
+  TraceExtras x;
+  x.state = &st;
+  x.n_steps = 1;
+  x.state_init = true;
+  SummaryArrays out = {};
+  out.sv = d_start_ray_vec;
+  return launch_trace(p, KernelVariant::Window, nray, {d_rvec0, d_rindex_vec0}, {}, out, (hipStream_t)hip_stream,
+                      RAYS_TRACE_NO_ZERO_FILL, x);
+}
+
+int rays_hip_trace_window_device(const rays_params_t* p, int nray, const rays_ray_state_t* state, int n_steps,
+                                 double* d_ray_vec_win, double* d_residual_win, int32_t* d_npoints_win,
+                                 void* hip_stream) {
+  int rc = rays_hip_check_params(p);
+  if (rc) return rc;
+  rc = refuse_state("rays_hip_trace_window_device", p, nray, state);
+  if (rc) return rc;
+  if (n_steps < 1) return fail("rays_hip_trace_window_device: n_steps < 1");
+  if (!d_npoints_win) return fail("rays_hip_trace_window_device: null device pointer");
+  if (!d_ray_vec_win != !d_residual_win)
+    return fail("rays_hip_trace_window_device: ray_vec_win and residual_win are given together or not at all");
+  if ((long long)nray * n_steps > 0x7fffffffll)
+    return fail("rays_hip_trace_window_device: nray * n_steps exceeds 2^31 - 1");
+  if (nray == 0) return 0;
+  const rays::TraceArgs::State st = state_of(state);
+  TraceExtras x;
+  x.state = &st;
+  x.n_steps = n_steps;
+  SummaryArrays out = {};
+  out.np = d_npoints_win;
+  return launch_trace(p, d_ray_vec_win ? KernelVariant::Window : KernelVariant::WindowSummary, nray, {nullptr, nullptr},
+                      {d_ray_vec_win, d_residual_win}, out, (hipStream_t)hip_stream, RAYS_TRACE_NO_ZERO_FILL, x);
+}
+
+namespace rays {
+// the five summary arrays of a trace from the saved state (ray_tracing.f90:252-260); a refused ray keeps the zeros of
+// initialize_ray_results_m
+__global__ void state_summary_kernel(int n, int nv, TraceArgs::State st, int32_t* __restrict__ npoints,
+                                     int32_t* __restrict__ stop, double* __restrict__ end_ray_vec,
+                                     double* __restrict__ end_residuals, double* __restrict__ max_residuals) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n) return;
+  const bool refused = (st.flags[r] & kStateRefused) != 0;
+  const int nstep = st.nstep[r];
+  npoints[r] = nstep + 1;
+  stop[r] = st.stop_code[r];
+  for (int c = 0; c < nv; c++) end_ray_vec[(long long)r * nv + c] = refused ? 0. : st.v[(long long)r * nv + c];
+  end_residuals[r] = (!refused && nstep >= 1) ? st.resid[3ll * r + 1] : 0.;
+  max_residuals[r] = refused ? 0. : st.resid[3ll * r + 2];
+}
+}  // namespace rays
+
+int rays_hip_state_summary_device(const rays_params_t* p, int nray, const rays_ray_state_t* state, int32_t* d_npoints,
+                                  int32_t* d_stop_code, double* d_end_ray_vec, double* d_end_residuals,
+                                  double* d_max_residuals, void* hip_stream) {
+  int rc = rays_hip_check_params(p);
+  if (rc) return rc;
+  rc = refuse_state("rays_hip_state_summary_device", p, nray, state);
+  if (rc) return rc;
+  if (!d_npoints || !d_stop_code || !d_end_ray_vec || !d_end_residuals || !d_max_residuals)
+    return fail("rays_hip_state_summary_device: null device pointer");
+  if (nray == 0) return 0;
+  hipLaunchKernelGGL(rays::state_summary_kernel, dim3((nray + 255) / 256), dim3(256), 0, (hipStream_t)hip_stream, nray,
+                     (int)p->nv, state_of(state), d_npoints, d_stop_code, d_end_ray_vec, d_end_residuals, d_max_residuals);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(e, "rays_hip_state_summary_device");
+  return 0;
+}
+
+const char* rays_hip_window_kernel_name_for(const rays_params_t* p, int nray, int recording) {
+  if (!p || rays_hip_check_params(p)) return "";
+  const rays::KernelEntry* k = find_kernel(*p, nray, recording ? KernelVariant::Window : KernelVariant::WindowSummary);
+  return k ? k->name : "";
 }
 
 // Batched `call ode_solver(eqn_ray, nv, v, s, sout, ray_stop)` (ode_m.f90:218-254) + the check_save that
@@ -1256,6 +1385,127 @@ int rays_hip_trace_summary(const rays_params_t* p, int nray, const double* rvec0
     if (rc_b) return rc_b;
     HIP_TRY_AS("hipMemcpyAsync (summaries)", B.download(out, (size_t)p->nv));
     HIP_TRY(hipStreamSynchronize(B.st()));
+    B.bufs.release();
+    return 0;
+  });
+  if (rc) return rc;
+  if (elapsed_s)
+    *elapsed_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  return 0;
+}
+
+// The host form of windowed tracing: the outputs of rays_hip_trace, bit for bit, with device memory bounded by the ray
+// state plus two window slabs whatever nstep_max is.  One device (the first slot of the device list).  Window k is
+// copied out -- whole slabs through the slot's pinned staging, on a copy stream of the call's own -- and scattered
+// into the caller's arrays while window k + 1 runs.  A ray under way records exactly n_steps points per window, so the
+// fan has ended when no ray of a window did; the window launched ahead of that test finds every ray ended and changes
+// nothing.
+int rays_hip_trace_windowed(const rays_params_t* p, int nray, const double* rvec0, const double* rindex_vec0,
+                            int n_steps, double* ray_vec, double* residual, int32_t* npoints, int32_t* stop_code,
+                            double* end_ray_vec, double* end_residuals, double* max_residuals, double* elapsed_s) {
+  int rc = rays_hip_check_params(p);
+  if (rc) return rc;
+  if (nray < 0) return fail("rays_hip_trace_windowed: nray < 0");
+  if (n_steps < 1) return fail("rays_hip_trace_windowed: n_steps < 1");
+  if (nray > 0 && (!rvec0 || !rindex_vec0 || !ray_vec || !residual || !npoints || !stop_code))
+    return fail("rays_hip_trace_windowed: null array argument");
+  if ((long long)nray * n_steps > 0x7fffffffll) return fail("rays_hip_trace_windowed: nray * n_steps exceeds 2^31 - 1");
+  std::vector<int> devs;
+  if (call_devices(&devs)) return 3;
+  devs.resize(1);
+  drop_kept_result();  // the image of an earlier rays_hip_trace (if any) is not this call's result: it goes back
+  const auto t0 = std::chrono::steady_clock::now();
+  const size_t npt = (size_t)p->nstep_max + 1, nv = (size_t)p->nv, W = (size_t)n_steps;
+  std::deque<RayBlock> blk;
+  rc = run_blocks(devs, nray, &blk, [&](RayBlock& B) {
+    const int n = B.n();
+    if (n <= 0) return 0;
+    const size_t N = (size_t)n;
+    HIP_TRY_AS("hipSetDevice / hipStreamCreate", B.open());
+    const hipStream_t st = B.st();
+    SlotStream copy_stream;
+    HIP_TRY_AS("hipStreamCreate", copy_stream.open(kNoSlot));
+    const hipStream_t cs = copy_stream.get();
+    EventPair traced, copied;
+    HIP_TRY_AS("hipEventCreate", traced.create());
+    HIP_TRY_AS("hipEventCreate", copied.create());
+    rays_ray_state_t S = {};
+    TrajectoryArrays slab[2];
+    int32_t* d_npw[2] = {nullptr, nullptr};
+    const auto alloc_all = [&] {
+      hipError_t e = B.bufs.alloc(&S.v, nv * N);
+      if (e == hipSuccess) e = B.bufs.alloc(&S.s, N);
+      if (e == hipSuccess) e = B.bufs.alloc(&S.nstep, N);
+      if (e == hipSuccess) e = B.bufs.alloc(&S.stop_code, N);
+      if (e == hipSuccess) e = B.bufs.alloc(&S.resid, 3 * N);
+      if (e == hipSuccess) e = B.bufs.alloc(&S.sg_err, 2 * N);
+      if (e == hipSuccess) e = B.bufs.alloc(&S.flags, N);
+      for (int b = 0; b < 2 && e == hipSuccess; b++) {
+        e = slab[b].alloc(B.bufs, N, W, nv);
+        if (e == hipSuccess) e = B.bufs.alloc(&d_npw[b], N);
+      }
+      return e == hipSuccess ? B.d.alloc(B.bufs, N, nv, true) : e;
+    };
+    HIP_TRY_AS("hipMalloc (ray state, window slabs)", alloc_all());
+    HIP_TRY_AS("hipMalloc / hipMemcpyAsync (block inputs)", B.upload({rvec0, rindex_vec0}));
+    StagingBuffers* sb = staging_for_slot(B.slot, nv, (long long)(N * W));
+    if (!sb) return fail("rays_hip_trace_windowed: pinned staging buffers could not be allocated");
+    int rc_b = rays_hip_state_init_device(p, n, B.in.rvec0, B.in.rindex_vec0, &S, B.d.sv, st);
+    if (rc_b) return rc_b;
+    // point 1 of every ray: the start vector, residual 0
+    std::vector<double> start(nv * N);
+    HIP_TRY(hipMemcpyAsync(start.data(), B.d.sv, sizeof(double) * nv * N, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (size_t i = 0; i < N; i++) {
+      std::memcpy(ray_vec + npt * nv * (i + (size_t)B.r0), start.data() + nv * i, sizeof(double) * nv);
+      residual[npt * (i + (size_t)B.r0)] = 0.;
+    }
+    std::vector<int32_t> npw[2] = {std::vector<int32_t>(N), std::vector<int32_t>(N)};
+    std::vector<int32_t> have(N, 1);  // points of each ray in the caller's arrays so far
+    const auto launch = [&](int b) {
+      const int r = rays_hip_trace_window_device(p, n, &S, n_steps, slab[b].rv, slab[b].res, d_npw[b], st);
+      if (r) return r;
+      HIP_TRY(hipEventRecord(traced[b], st));
+      return 0;
+    };
+    rc_b = launch(0);
+    if (rc_b) return rc_b;
+    for (int k = 0;; k++) {
+      const int b = k & 1;
+      // window k: slab -> pinned staging on the copy stream, once its kernel has ended
+      HIP_TRY(hipEventSynchronize(traced[b]));
+      HIP_TRY(hipMemcpyAsync(sb->vec[b], slab[b].rv, sizeof(double) * nv * N * W, hipMemcpyDeviceToHost, cs));
+      HIP_TRY(hipMemcpyAsync(sb->res[b], slab[b].res, sizeof(double) * N * W, hipMemcpyDeviceToHost, cs));
+      HIP_TRY(hipMemcpyAsync(npw[b].data(), d_npw[b], sizeof(int32_t) * N, hipMemcpyDeviceToHost, cs));
+      HIP_TRY(hipEventRecord(copied[b], cs));
+      // window k + 1 into the other slab, whose copy (window k - 1) the host has already waited for
+      rc_b = launch(b ^ 1);
+      if (rc_b) return rc_b;
+      HIP_TRY(hipEventSynchronize(copied[b]));
+      bool any_full = false;
+      const int nt = 16;
+      std::vector<std::thread> th;
+      for (int t = 0; t < nt; t++)
+        th.emplace_back([&, t]() {
+          for (size_t i = (size_t)t; i < N; i += (size_t)nt) {
+            const size_t m = (size_t)npw[b][i];
+            if (m == 0) continue;
+            const size_t ray = i + (size_t)B.r0, at = (size_t)have[i];
+            std::memcpy(ray_vec + (npt * ray + at) * nv, sb->vec[b] + i * W * nv, sizeof(double) * nv * m);
+            std::memcpy(residual + npt * ray + at, sb->res[b] + i * W, sizeof(double) * m);
+            have[i] += (int32_t)m;
+          }
+        });
+      for (auto& x : th) x.join();
+      for (size_t i = 0; i < N; i++) any_full = any_full || npw[b][i] == n_steps;
+      if (!any_full) break;
+    }
+    rc_b = rays_hip_state_summary_device(p, n, &S, B.d.np, B.d.sc, B.d.ev, B.d.er, B.d.mr, st);
+    if (rc_b) return rc_b;
+    SummaryArrays out = {npoints, stop_code, nullptr, end_ray_vec, end_residuals, max_residuals};
+    HIP_TRY_AS("hipMemcpyAsync (summaries)", B.download(out, nv));
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipStreamSynchronize(cs));
     B.bufs.release();
     return 0;
   });

@@ -33,6 +33,11 @@ constexpr int kEqNoTraj = 32;
 // (rays_deposition.hpp: deposit_segment), so the absorbed-power profile exists without the trajectories.  Kernels with
 // the absorbed-power row only; own translation units (Makefile: dep_*.o), exact arithmetic only.
 constexpr int kEqDeposit = 64;
+// Continuation variant of a one-ray-per-lane trace kernel (windowed tracing; DESIGN.md 4.10): a ray starts from a saved
+// state instead of its launch point, is paused into that state after the launch's n_steps recorded steps, and its
+// points go to a window slab of n_steps points per ray (rays_trace.hpp: TraceArgs::state).  With kEqNoTraj: the same
+// without any recorded point.  Own translation units (Makefile: win_*.o, wsum_*.o), exact arithmetic only.
+constexpr int kEqContinue = 128;
 // Layout of the ODE vector (ode_m.f90:160-173, initialize_ode_vector.f90:25-54):
 //   v(1:6) = (r, k), v(7) = s, [v(8) = total absorbed power, [v(9:9+nspec) per species]], [5 gradient rows]
 template <bool MULTI, int NS, int NV>

@@ -9,6 +9,10 @@
 //   summary-only kernel that also bins every accepted point) of a slab or axisym_toroid group.  The same shape lists,
 //   cut down to the entries with the absorbed-power row (nv = 8 | 13; 8 + NS | 13 + NS in the MS groups) and to the
 //   one-ray-per-lane kernels: a damped configuration is traced fused exactly when it is traced at all.
+//   -DRAYS_INST_CONTINUE=1 [-DRAYS_INST_NOTRAJ=1]: the continuation variant (rays_device_arith.inc: kEqContinue;
+//   windowed tracing) of an exact group, recording or summary-only.  The same shape lists, cut down to the
+//   one-ray-per-lane kernels: a configuration is continued exactly when it is traced at all.  The recording objects
+//   also hold the state_init kernel of each shape (rays_trace.hpp), in the entries' `resume` slot.
 //   -DRAYS_INST_TOL=1 -DRAYS_TOL_FLAVOUR -ffp-contract=fast: the tolerance flavour of a cold RK4 group
 //   (rays_device.hpp: kEqTol; 1e-10 relative per step instead of bit-identity)
 // `make FULL=1` (-DRAYS_INST_FULL): each group instantiates the species counts NS = 1..6 (nspec = 0..5,
@@ -40,6 +44,12 @@
 #ifndef RAYS_INST_DEPOSIT
 #define RAYS_INST_DEPOSIT 0
 #endif
+#ifndef RAYS_INST_CONTINUE
+#define RAYS_INST_CONTINUE 0
+#endif
+#if RAYS_INST_CONTINUE && (RAYS_INST_TOL || RAYS_INST_DEPOSIT)
+#error "the continuation variant exists for the exact recording and summary-only kernels only"
+#endif
 #if RAYS_INST_NOTRAJ && RAYS_INST_TOL
 #error "the summary-only variant exists in the exact arithmetic only"
 #endif
@@ -56,7 +66,7 @@
 #define RAYS_CAT(a, b, c, d, e, f) RAYS_CAT_(a, b, c, d, e, f)
 // the kernels' EQ template argument, as a literal (it appears in the kernel names rocprof prints)
 #ifndef RAYS_INST_EQT
-#error "pass -DRAYS_INST_EQT=<RAYS_INST_EQ + 4 RAYS_INST_UE + 8 RAYS_INST_MS + 16 RAYS_INST_TOL + 32 RAYS_INST_NOTRAJ + 64 RAYS_INST_DEPOSIT>"
+#error "pass -DRAYS_INST_EQT=<RAYS_INST_EQ + 4 RAYS_INST_UE + 8 RAYS_INST_MS + 16 RAYS_INST_TOL + 32 RAYS_INST_NOTRAJ + 64 RAYS_INST_DEPOSIT + 128 RAYS_INST_CONTINUE>"
 #endif
 #define RAYS_STR_(x) #x
 #define RAYS_STR(x) RAYS_STR_(x)
@@ -67,7 +77,7 @@ namespace {
 constexpr int EQ = RAYS_INST_EQT;
 static_assert(EQ == (RAYS_INST_EQ | (RAYS_INST_UE ? kEqUnitExp : 0) | (RAYS_INST_MS ? kEqMultiSpec : 0) |
                      (RAYS_INST_TOL ? kEqTol : 0) | (RAYS_INST_NOTRAJ ? kEqNoTraj : 0) |
-                     (RAYS_INST_DEPOSIT ? kEqDeposit : 0)), "EQ encoding");
+                     (RAYS_INST_DEPOSIT ? kEqDeposit : 0) | (RAYS_INST_CONTINUE ? kEqContinue : 0)), "EQ encoding");
 constexpr int DERIV = RAYS_INST_DERIV;
 
 template <int NS, int NV, int OCC = 1>
@@ -100,7 +110,7 @@ hipError_t launch_one(const DevParams& P, const TraceArgs& A, hipStream_t stream
 #endif
 }
 
-#if RAYS_INST_SOLVER == 0 && RAYS_INST_DERIV == 0 && !RAYS_INST_TOL && !RAYS_INST_MS && !RAYS_INST_NOTRAJ
+#if RAYS_INST_SOLVER == 0 && RAYS_INST_DERIV == 0 && !RAYS_INST_TOL && !RAYS_INST_MS && !RAYS_INST_NOTRAJ && !RAYS_INST_CONTINUE
 // (not in a summary-only object: the hand-over reads residual(:))
 // the continuation of rays the tolerance twin of this shape hands over (rays_rk4.hpp: rk4_resume_kernel)
 template <int NS, int NV>
@@ -109,6 +119,14 @@ hipError_t resume_one(const DevParams& P, const TraceArgs& A, hipStream_t stream
   return hipGetLastError();
 }
 #define RAYS_RESUME(NS, NV) , &resume_one<NS, NV>
+#elif RAYS_INST_CONTINUE && !RAYS_INST_NOTRAJ
+// rays_hip_state_init_device's kernel for this shape (rays_trace.hpp: state_init_kernel), one lane per ray
+template <int NS, int NV>
+hipError_t state_init_one(const DevParams& P, const TraceArgs& A, hipStream_t stream) {
+  hipLaunchKernelGGL((state_init_kernel<EQ, NS, DERIV, NV>), dim3((A.nray + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, P, A);
+  return hipGetLastError();
+}
+#define RAYS_RESUME(NS, NV) , &state_init_one<NS, NV>
 #else
 #define RAYS_RESUME(NS, NV)
 #endif
@@ -160,6 +178,13 @@ struct DepEntry<NS, NV, true> {
 #define RAYS_ENTRY_OCC2(NS, NV) DepEntry<NS, 7>::get("")
 #undef RAYS_ENTRY_GROUP
 #define RAYS_ENTRY_GROUP(NS) DepEntry<NS, 7>::get("")
+#elif RAYS_INST_CONTINUE
+// The continuation objects walk the same lists and keep the one-ray-per-lane kernels: the two-waves-per-SIMD and
+// lane-group entries come out as entries no configuration matches (ns = 0), not as kernels.
+#define RAYS_ENTRY(NS, NV) RAYS_ENTRY_(NS, NV)
+#define RAYS_ENTRY_OCC2(NS, NV) KernelEntry{RAYS_INST_SOLVER, EQ, 0, DERIV, 0, 1, 0, 1, "", nullptr, nullptr}
+#undef RAYS_ENTRY_GROUP
+#define RAYS_ENTRY_GROUP(NS) KernelEntry{RAYS_INST_SOLVER, EQ, 0, DERIV, 0, 1, 0, 1, "", nullptr, nullptr}
 #else
 #define RAYS_ENTRY(NS, NV) RAYS_ENTRY_(NS, NV)
 #define RAYS_ENTRY_OCC2(NS, NV) RAYS_ENTRY_OCC2_(NS, NV)
@@ -237,6 +262,10 @@ extern "C" int RAYS_CAT(rays_debug_sg_profile, RAYS_INST_SOLVER, RAYS_INST_EQ, R
 #define RAYS_ENTRIES_NAME rays_entries_tol
 #elif RAYS_INST_DEPOSIT
 #define RAYS_ENTRIES_NAME rays_entries_dep
+#elif RAYS_INST_CONTINUE && RAYS_INST_NOTRAJ
+#define RAYS_ENTRIES_NAME rays_entries_wsum
+#elif RAYS_INST_CONTINUE
+#define RAYS_ENTRIES_NAME rays_entries_win
 #elif RAYS_INST_NOTRAJ
 #define RAYS_ENTRIES_NAME rays_entries_sum
 #else

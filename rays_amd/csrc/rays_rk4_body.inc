@@ -88,7 +88,13 @@
   const Recip R6 = const_recip(6.0, 1.0 / 6.0);  // RN(1/6); div() = the correctly rounded quotient
   typedef PointWindow<NV, RAYS_RK4_USE_WINDOW == 2> Window;  // rays_trace.hpp (2: residual(:) only)
   constexpr bool kNoTraj = (EQ & kEqNoTraj) != 0;  // summary-only variant: no point is recorded, no window exists
-  constexpr bool kWindow = RAYS_RK4_USE_WINDOW && Window::kAny && !kNoTraj;
+  // continuation variant (kEqContinue; DESIGN.md 4.10): rays start from the saved state and are paused into it after the
+  // launch's n_steps recorded steps; points are stored directly into the window slab [nray][n_steps].  (kIsContinue<EQ>,
+  // rays_trace.hpp: a constant of namespace scope -- one more local constant here moves instructions in the kernels
+  // that do not have the bit, and those are to come out of the compiler exactly as they were.)
+  static_assert(!kIsContinue<EQ> || (RAYS_RK4_LONG_FIRST && !(EQ & (kEqDeposit | kEqTol))),
+                "the continuation variant: an exact one-wave-per-SIMD kernel, recording or summary-only");
+  constexpr bool kWindow = RAYS_RK4_USE_WINDOW && Window::kAny && !kNoTraj && !kIsContinue<EQ>;
   // fused deposition variant (kEqDeposit; rays_deposition.hpp): an accepted point is binned into the ray's row of work.
   // The grid value and the absorbed power of the ray's last recorded point belong to the ray: set at its point 1.
   constexpr bool kDeposit = (EQ & kEqDeposit) != 0;
@@ -184,6 +190,7 @@
   // idle_acc += 4 * occupied - alive_sum.  Step for step the sum the threshold sees is what a ballot of the parked lanes
   // on every trip gave.
   int idle_acc = 0, alive_sum = 0, occupied = 0;
+  [[maybe_unused]] int win0 = 0;  // continuation variant: steps the ray had recorded when this window began
   // RAYS_RK4_LONG_FIRST (the one-wave-per-SIMD kernel): two loops -- the outer one is the pass (cold: a handful of
   // times per wave), the inner one the trips between two passes (hot) -- and the rays are handed out "long rays first"
   // (rays_trace.hpp: take_rays).  As ONE loop with that pass inside an `if`, the pass's registers (cursors, window
@@ -309,7 +316,10 @@
         // stage 3: w is the new state; check_save decides whether the step is recorded
         if (first) {
           // ray_tracing.f90:92-112: point 1 = initial state, residual(1) = 0
-          if constexpr (kNoTraj) {  // ... of which the summaries keep the state: start_ray_vec (ray_tracing.f90:259)
+          if constexpr (kIsContinue<EQ>) {
+            // a continued ray's first evaluation, at its saved point: the next step's first stage and nothing else -- the
+            // point was recorded (and passed check_save) by the launch that paused the ray there; cs_stop is not looked at
+          } else if constexpr (kNoTraj) {  // ... of which the summaries keep the state: start_ray_vec (ray_tracing.f90:259)
             const TraceArgs& A = cold_args(A_hot);
             double* const start = A.start_ray_vec();
             if (start)
@@ -323,7 +333,7 @@
           } else {
             record_point<NV>(A_hot, (long long)ray * npt, v, 0.);
           }
-          if (cs_stop) {  // ray did not start: npoints = 1, summary fields stay zero
+          if (!kIsContinue<EQ> && cs_stop) {  // ray did not start: npoints = 1, summary fields stay zero
             const TraceArgs& A = cold_args(A_hot);
             A.npoints[ray] = 1;
             A.stop_code[ray] = cs_flag;
@@ -355,6 +365,8 @@
                 const TraceArgs& A = cold_args(A_hot);
                 dep_trace_segment(P, *A.dep(), ray, A.nray, v, dep_x_prev, dep_q_prev);
               }
+            } else if constexpr (kIsContinue<EQ>) {  // the point's place in the window slab
+              record_point<NV>(A_hot, (long long)ray * A_hot.win_steps() + (nstep - win0 - 1), v, resid);
             } else if constexpr (kWindow) {
               int pv, pr;
               Window::phases(A_hot, ray, npt, pv, pr);
@@ -366,6 +378,14 @@
             if (fabs(last_resid) > maxr) maxr = fabs(last_resid);
             prev_resid = last_resid;
             last_resid = resid;
+            if constexpr (kIsContinue<EQ>) {
+              // the window's end: the ray is paused where trace_rays stands at ray_tracing.f90:116, before sout is
+              // advanced and before any of the next trip's three tests (the launch that continues it applies them)
+              if (nstep - win0 >= A_hot.win_steps()) {
+                stop = kStopPaused;
+                done = 1;
+              }
+            }
           }
         }
 #if RAYS_RK4_HANDOVER

@@ -17,7 +17,11 @@
         win.finish(A, (long long)ray * npt, nstep + 1, pv, pr);
       }
       const int stop = first;  // parked there by the trip that ended the ray
-      if (stop >= 0) {  // ray_tracing.f90:252-260
+      if constexpr (kIsContinue<EQ>) {
+        // ended or paused: the lane's values go back into the state, which holds the summaries too.  s is sout as the
+        // trip found it (the body assigns s = sout before it advances sout).
+        state_store<NV>(A, ray, v, s, nstep, stop, last_resid, prev_resid, maxr, win0);
+      } else if (stop >= 0) {  // ray_tracing.f90:252-260
         A.npoints[ray] = nstep + 1;
         A.stop_code[ray] = stop;
         if (A.end_ray_vec)
@@ -31,36 +35,42 @@
       pending = false;
       hungry = can_refill;
     }
-#if RAYS_RK4_LONG_FIRST
-    if (can_refill) {  // wave-uniform; the lanes that want a ray are served together (rays_trace.hpp: take_rays)
-      bool dry = false;
-      const int nxt = take_rays(Ac, total_lanes, S, hungry, (int)(threadIdx.x & 63u), dry);
-      if (hungry && nxt >= 0) {
-        ray = nxt;
-        need_init = true;
-        hungry = false;
-      }
-      if (dry) {  // no ray is left for anybody
-        can_refill = false;
-        hungry = false;
-      }
-    }
-#else
-    {  // index order, one atomic per lane
-      bool dry = false;
-      if (hungry) {
-        const unsigned nxt = atomicAdd(Ac.next_ray, 1u) + total_lanes;
-        if (nxt < (unsigned)Ac.nray) {
-          ray = (int)nxt;
-          need_init = true;
-        } else {
-          dry = true;
+    if constexpr (kIsContinue<EQ>) {
+      // (a ray that ended in an earlier window is not started -- it records nothing and costs no evaluation -- and its
+      // lane asks again at once)
+      bool skipped;
+      do {
+#include "rays_rk4_take.inc"
+        skipped = false;
+        if (need_init && Ac.stop_code[ray] != RAYS_STOP_NONE) {
+          Ac.npoints[ray] = 0;
+          if (S && sched_is_pilot((unsigned)ray, S)) atomicOr(Ac.sched + 4 + sched_neighbourhood((unsigned)ray, S), kSchedDone);
+          need_init = false;
+          hungry = can_refill;
+          skipped = hungry;
         }
-        hungry = false;
-      }
-      if (__any(dry)) can_refill = false;  // the counter only grows
+      } while (__any(skipped));
+    } else {
+#include "rays_rk4_take.inc"
     }
+    if constexpr (kIsContinue<EQ>) if (need_init) {  // the saved state (rays_trace.hpp: TraceArgs::state)
+      const TraceArgs::State st = Ac.state();
+#pragma unroll
+      for (int i = 0; i < NV; i++) w[i] = v[i] = st.v[(long long)ray * NV + i];
+      sout = st.s[ray];
+      ds_ray = P.ds;
+      nstep = win0 = st.nstep[ray];
+      s = sout;
+      last_resid = st.resid[3ll * ray];
+      prev_resid = st.resid[3ll * ray + 1];
+      maxr = st.resid[3ll * ray + 2];
+      first = 1;
+#if defined(RAYS_HOST_EMUL) && defined(RAYS_EMUL_CHECK_UNIFORM_STAGE)
+      j_lane = 3;
 #endif
+      need_init = false;
+      alive = true;
+    }
     if (need_init) {  // initialize_ode_vector + per-ray resets (ray_tracing.f90:77-93)
       const TraceArgs& A = cold_args(A_hot);
       start_ray<EQ, NS, NV>(P, A, ray, v, sout, ds_ray);

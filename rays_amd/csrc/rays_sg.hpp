@@ -484,6 +484,11 @@ sg_trace_kernel(const DevParams P_kernarg, const TraceArgs A_hot) {
   static_assert(!kDeposit || ((EQ & kEqNoTraj) != 0 && RayVec<(EQ & kEqMultiSpec) != 0, NS, NV>::DAMP),
                 "the fused deposition variant: a summary-only kernel with the absorbed-power row");
   [[maybe_unused]] double dep_x_prev = 0., dep_q_prev = 0.;
+  // continuation variant (kEqContinue): rays start from the saved state and are paused into it after the
+  // launch's n_steps recorded steps; points go into the window slab [nray][n_steps]
+  constexpr bool kContinue = (EQ & kEqContinue) != 0;
+  static_assert(!kContinue || !(EQ & (kEqDeposit | kEqTol)), "the continuation variant: recording or summary-only");
+  [[maybe_unused]] int win0 = 0;  // steps the ray had recorded when this window began
 
   // ---- per-lane integrator state (de / step locals that live across RHS evaluations) ----------
   double yy[NV], pp[NV];  // (yp of `step` is always the f of the current trip: not kept)
@@ -508,18 +513,50 @@ sg_trace_kernel(const DevParams P_kernarg, const TraceArgs A_hot) {
     SG_PROF(0);  // loop overhead, refill
     if (RAYS_RARE(need_init)) {  // ray_tracing.f90:77-93, SG_ode_m.f90:73-85
       const TraceArgs& A = cold_args(A_hot);  // rays_trace.hpp
-      start_ray<EQ, NS, NV>(P, A, ray, yy, sout, ds_ray);
-      sg_save_y<NV>(A_hot, yy);
-      pc = PC_CHECK;
-      resume = SEG_WAIT;
-      fl |= FL_FIRST;
-      nstep = 0;
-      t = sout;
-      last_resid = 0.;
-      prev_resid = 0.;
-      maxr = -1.7976931348623157e308;
-      rel_err = P.rel_err0;
-      abs_err = P.abs_err0;
+      if constexpr (kContinue) {
+        // a ray that ended in an earlier window is not started: it records nothing and costs no evaluation
+        while (need_init && A.stop_code[ray] != RAYS_STOP_NONE) {
+          A.npoints[ray] = 0;
+          const unsigned nxt = atomicAdd(A.next_ray, 1u) + total_lanes;
+          if (nxt < (unsigned)A.nray) {
+            ray = (int)nxt;
+          } else {
+            alive = false;
+            need_init = false;
+          }
+        }
+      }
+      if constexpr (kContinue) {
+        if (need_init) {  // the saved state (rays_trace.hpp: TraceArgs::state); rel_err / abs_err persist across output
+                          // steps (SG_ode_m.f90:115-126, :139-149) and are part of it
+          const TraceArgs::State st = A.state();
+#pragma unroll
+          for (int i = 0; i < NV; i++) yy[i] = st.v[(long long)ray * NV + i];
+          sout = st.s[ray];
+          ds_ray = P.ds;
+          nstep = win0 = st.nstep[ray];
+          last_resid = st.resid[3ll * ray];
+          prev_resid = st.resid[3ll * ray + 1];
+          maxr = st.resid[3ll * ray + 2];
+          rel_err = st.sg_err[2ll * ray];
+          abs_err = st.sg_err[2ll * ray + 1];
+        }
+      } else {
+        start_ray<EQ, NS, NV>(P, A, ray, yy, sout, ds_ray);
+        nstep = 0;
+        last_resid = 0.;
+        prev_resid = 0.;
+        maxr = -1.7976931348623157e308;
+        rel_err = P.rel_err0;
+        abs_err = P.abs_err0;
+      }
+      if (!kContinue || need_init) {
+        sg_save_y<NV>(A_hot, yy);
+        pc = PC_CHECK;
+        resume = SEG_WAIT;
+        fl |= FL_FIRST;
+        t = sout;
+      }
       need_init = false;
     }
 
@@ -600,7 +637,11 @@ sg_trace_kernel(const DevParams P_kernarg, const TraceArgs A_hot) {
     if (act) {
       if (pc == PC_CHECK) {
         seg = SEG_DE_BEGIN;
-        if (RAYS_RARE(fl & FL_FIRST)) {  // ray_tracing.f90:92-112
+        if (kContinue && RAYS_RARE(fl & FL_FIRST)) {
+          // a continued ray's first evaluation, at its saved point: the start-of-interval f and nothing else -- the
+          // point was recorded (and passed check_save) by the launch that paused the ray there
+          fl &= ~FL_FIRST;
+        } else if (RAYS_RARE(fl & FL_FIRST)) {  // ray_tracing.f90:92-112
           if constexpr ((EQ & kEqNoTraj) != 0) {  // summary-only: point 1 is kept as start_ray_vec (ray_tracing.f90:259)
             const TraceArgs& A = cold_args(A_hot);
             double* const start = A.start_ray_vec();
@@ -632,7 +673,12 @@ sg_trace_kernel(const DevParams P_kernarg, const TraceArgs A_hot) {
             seg = SEG_STOP;
           } else {
             nstep = nstep + 1;
-            if constexpr ((EQ & kEqNoTraj) == 0) record_point<NV>(cold_args(A_hot), (long long)ray * npt + nstep, yy, resid);
+            if constexpr (kContinue) {  // the point's place in the window slab [nray][n_steps]
+              if constexpr ((EQ & kEqNoTraj) == 0) {
+                const TraceArgs& A = cold_args(A_hot);
+                record_point<NV>(A, (long long)ray * A.win_steps() + (nstep - win0 - 1), yy, resid);
+              }
+            } else if constexpr ((EQ & kEqNoTraj) == 0) record_point<NV>(cold_args(A_hot), (long long)ray * npt + nstep, yy, resid);
             if constexpr (kDeposit) {  // the point is binned where the recording kernels store it
               const TraceArgs& A = cold_args(A_hot);
               dep_trace_segment(P, *A.dep(), ray, A.nray, yy, dep_x_prev, dep_q_prev);
@@ -640,6 +686,14 @@ sg_trace_kernel(const DevParams P_kernarg, const TraceArgs A_hot) {
             if (fabs(last_resid) > maxr) maxr = fabs(last_resid);
             prev_resid = last_resid;
             last_resid = resid;
+            if constexpr (kContinue) {
+              // the window's end: the ray is paused where trace_rays stands at ray_tracing.f90:116, before sout is
+              // advanced and before the next trip's tests (the launch that continues it applies them)
+              if (nstep - win0 >= cold_args(A_hot).win_steps()) {
+                stop = kStopPaused;
+                seg = SEG_STOP;
+              }
+            }
           }
         }
         if (seg == SEG_DE_BEGIN) {  // ray_tracing.f90:118-172
@@ -1103,7 +1157,17 @@ sg_trace_kernel(const DevParams P_kernarg, const TraceArgs A_hot) {
       }
 
       SG_PROF(11);
-      if (RAYS_RARE(done && stop >= 0)) {  // ray_tracing.f90:252-260
+      if constexpr (kContinue) {
+        if (RAYS_RARE(done)) {  // ended or paused: the lane's values go back into the state, which holds the summaries too
+          const TraceArgs& A = cold_args(A_hot);
+          double yend[NV];
+          sg_load_y<NV>(A_hot, yend);  // (a paused ray's y is its yy: the interpolation saved it)
+          state_store<NV>(A, ray, yend, sout, nstep, stop, last_resid, prev_resid, maxr, win0);
+          const TraceArgs::State st = A.state();
+          st.sg_err[2ll * ray] = rel_err;
+          st.sg_err[2ll * ray + 1] = abs_err;
+        }
+      } else if (RAYS_RARE(done && stop >= 0)) {  // ray_tracing.f90:252-260
         const TraceArgs& A = cold_args(A_hot);
         A.npoints[ray] = nstep + 1;
         A.stop_code[ray] = stop;

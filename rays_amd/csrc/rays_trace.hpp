@@ -79,7 +79,43 @@ struct TraceArgs {
   __host__ __device__ void set_dep(const DepTraceArgs* d) {
     ray_vec = reinterpret_cast<double*>(const_cast<DepTraceArgs*>(d));
   }
+  // Continuation kernels (kEqContinue) and the state_init kernel: the saved ray state (include/rays_hip.h:
+  // rays_ray_state_t) travels in slots these kernels have no other use for -- they write no per-ray summary (the state
+  // holds it), take no caller's v0 / s0 and run no fused scan -- so TraceArgs is not lengthened for it either:
+  //   end_ray_vec -> v[nray][nv]   end_residuals -> s[nray]    max_residuals -> resid[nray][3]
+  //   v0 -> sg_err[nray][2]        s0 -> flags[nray]           ds_run -> nstep[nray]         stop_code: the state's
+  //   rays_per_run -> the launch's n_steps;  npoints: npoints_win;  ray_vec / residual: the window slabs (or null)
+  struct State {
+    double* v;
+    double* s;
+    int* nstep;
+    int* stop_code;
+    double* resid;
+    double* sg_err;
+    int* flags;
+  };
+  __host__ __device__ State state() const {
+    return State{end_ray_vec, end_residuals, reinterpret_cast<int*>(const_cast<double*>(ds_run)), stop_code, max_residuals,
+                 const_cast<double*>(v0), reinterpret_cast<int*>(const_cast<double*>(s0))};
+  }
+  __host__ __device__ void set_state(const State& st, int n_steps) {
+    end_ray_vec = st.v;
+    end_residuals = st.s;
+    ds_run = reinterpret_cast<const double*>(st.nstep);
+    stop_code = st.stop_code;
+    max_residuals = st.resid;
+    v0 = st.sg_err;
+    s0 = reinterpret_cast<const double*>(st.flags);
+    rays_per_run = n_steps;
+  }
+  __host__ __device__ int win_steps() const { return rays_per_run; }
 };
+template <int EQ>
+inline constexpr bool kIsContinue = (EQ & kEqContinue) != 0;  // the kernel is a continuation variant
+// (continuation kernels) a lane parks with this code in `first` when its ray is paused at a window's end, not ended
+constexpr int kStopPaused = 1001;
+// rays_ray_state_t::flags, bit 0: the initial check_save refused the ray (npoints 1, every summary field zero)
+constexpr int kStateRefused = 1;
 static_assert(sizeof(TraceArgs) == 19 * 8, "TraceArgs: the layout the kernels' cold_args() offsets were compiled for");
 
 // ---- which ray a free lane traces next ---------------------------------------------------------------------------
@@ -366,10 +402,63 @@ struct PointWindow {
   }
 };
 
-// The window's share of an RK4 kernel's LDS: none in the summary-only variant (kEqNoTraj), which records no point.
+// The window's share of an RK4 kernel's LDS: none in the summary-only variant (kEqNoTraj), which records no point, and
+// none in the continuation variant (kEqContinue), which stores its points directly.
 template <int EQ, int NV>
 constexpr size_t window_lds_bytes() {
-  return (EQ & kEqNoTraj) ? 0 : PointWindow<NV>::kLdsBytes;
+  return (EQ & (kEqNoTraj | kEqContinue)) ? 0 : PointWindow<NV>::kLdsBytes;
+}
+
+// ---- windowed tracing: the saved ray state (kEqContinue) -----------------------------------------------
+// What rays_hip_state_init_device does for one ray: initialize_ode_vector, the initial check_save
+// (ray_tracing.f90:77-112) and the per-ray resets.  v0 is point 1 of the ray whether or not it is refused.
+template <int EQ, int NS, int DERIV, int NV>
+RAYS_DEV void state_init_ray(const DevParams& P, const TraceArgs& A, int ray) {
+  const TraceArgs::State st = A.state();
+  double v[NV], f[NV], resid = 0.;
+  int code = 0, cs_flag = 0;
+  bool cs_stop = false;
+  initialize_ode_vector<EQ, NS, NV>(P, A.rvec0 + 3ll * ray, A.rindex_vec0 + 3ll * ray, v);
+  rhs_eval<EQ, NS, DERIV, NV>(P, v, true, resid, cs_flag, cs_stop, code, f);
+  double* const start = A.start_ray_vec();
+#pragma unroll
+  for (int i = 0; i < NV; i++) {
+    st.v[(long long)ray * NV + i] = v[i];
+    if (start) start[(long long)ray * NV + i] = v[i];
+  }
+  st.s[ray] = 0.;
+  st.nstep[ray] = 0;
+  st.stop_code[ray] = cs_stop ? cs_flag : RAYS_STOP_NONE;
+  st.flags[ray] = cs_stop ? kStateRefused : 0;
+  st.resid[3ll * ray] = 0.;
+  st.resid[3ll * ray + 1] = 0.;
+  st.resid[3ll * ray + 2] = -1.7976931348623157e308;
+  if (st.sg_err) {  // SG_ode_m.f90: ray_init_ode_solver
+    st.sg_err[2ll * ray] = P.rel_err0;
+    st.sg_err[2ll * ray + 1] = P.abs_err0;
+  }
+}
+template <int EQ, int NS, int DERIV, int NV>
+__global__ void __launch_bounds__(256)
+state_init_kernel(const DevParams P, const TraceArgs A) {
+  const int ray = blockIdx.x * blockDim.x + threadIdx.x;
+  if (ray < A.nray) state_init_ray<EQ, NS, DERIV, NV>(P, A, ray);
+}
+
+// Pausing or ending a continued ray: the lane's values go back into the state.  `stop` is the lane's parked code.
+template <int NV>
+RAYS_DEV void state_store(const TraceArgs& A, int ray, const double v[NV], double s, int nstep, int stop,
+                          double last_resid, double prev_resid, double maxr, int win0) {
+  const TraceArgs::State st = A.state();
+#pragma unroll
+  for (int i = 0; i < NV; i++) st.v[(long long)ray * NV + i] = v[i];
+  st.s[ray] = s;
+  st.nstep[ray] = nstep;
+  st.stop_code[ray] = stop == kStopPaused ? RAYS_STOP_NONE : stop;
+  st.resid[3ll * ray] = last_resid;
+  st.resid[3ll * ray + 1] = prev_resid;
+  st.resid[3ll * ray + 2] = maxr;
+  A.npoints[ray] = nstep - win0;
 }
 
 // LDS for the staged 1-D spline tables of the eqdsk equilibrium (DevParams::a_lds_tab), behind the point

@@ -38,6 +38,8 @@ EXPORTED_SYMBOLS = (
     "rays_hip_summary_kernel_name_for",
     "rays_hip_trace_deposition_device", "rays_hip_trace_deposition", "rays_hip_deposition_kernel_name_for",
     "rays_hip_rk4_loop_for",
+    "rays_hip_state_init_device", "rays_hip_trace_window_device", "rays_hip_state_summary_device",
+    "rays_hip_window_kernel_name_for", "rays_hip_trace_windowed",
 )
 
 _lib = None
@@ -45,6 +47,15 @@ _lib = None
 
 class RaysHipError(RuntimeError):
     pass
+
+
+class RayStateStruct(C.Structure):
+    """rays_ray_state_t (include/rays_hip.h): device pointers of the saved ray state of windowed tracing"""
+    _fields_ = [("v", C.c_void_p), ("s", C.c_void_p), ("nstep", C.c_void_p), ("stop_code", C.c_void_p),
+                ("resid", C.c_void_p), ("sg_err", C.c_void_p), ("flags", C.c_void_p)]
+
+
+STATE_REFUSED = 1   # RAYS_STATE_REFUSED
 
 
 def load():
@@ -129,6 +140,19 @@ def load():
     if hasattr(lib, "rays_hip_rk4_loop_for"):
         lib.rays_hip_rk4_loop_for.restype = C.c_int
         lib.rays_hip_rk4_loop_for.argtypes = [pp, C.c_int]
+    # (likewise the windowed-tracing entries -- tools/window_trace_bench.py)
+    if hasattr(lib, "rays_hip_trace_window_device"):
+        sp = C.POINTER(RayStateStruct)
+        lib.rays_hip_state_init_device.restype = C.c_int
+        lib.rays_hip_state_init_device.argtypes = [pp, C.c_int, vp, vp, sp, vp, vp]
+        lib.rays_hip_trace_window_device.restype = C.c_int
+        lib.rays_hip_trace_window_device.argtypes = [pp, C.c_int, sp, C.c_int, vp, vp, vp, vp]
+        lib.rays_hip_state_summary_device.restype = C.c_int
+        lib.rays_hip_state_summary_device.argtypes = [pp, C.c_int, sp, vp, vp, vp, vp, vp, vp]
+        lib.rays_hip_window_kernel_name_for.restype = C.c_char_p
+        lib.rays_hip_window_kernel_name_for.argtypes = [pp, C.c_int, C.c_int]
+        lib.rays_hip_trace_windowed.restype = C.c_int
+        lib.rays_hip_trace_windowed.argtypes = [pp, C.c_int, dp, dp, C.c_int, dp, dp, ip, ip, dp, dp, dp, dp]
     lib.rays_hip_ode_step_device.restype = C.c_int
     lib.rays_hip_ode_step_device.argtypes = [pp, C.c_int, vp, vp, vp, vp, vp, vp]
     lib.rays_hip_pack_device.restype = C.c_int
@@ -678,6 +702,80 @@ def trace_deposition_host(p: RaysParams, rvec0, rindex_vec0, initial_ray_power, 
                                        _dp(out["end_ray_vec"]), _dp(out["end_residuals"]), _dp(out["max_residuals"]),
                                        _dp(out["work"]) if want_work else None, _dp(out["profile"]), C.byref(el))
     _check(rc, "rays_hip_trace_deposition")
+    out["elapsed_s"] = el.value
+    return out
+
+
+def window_kernel_name(p: RaysParams, nray: int = 0, recording: bool = True) -> str:
+    """Kernel a window of `nray` rays would launch (always exact, always the one-ray-per-lane kernel: the recording
+    kernel's name with EQ + 128, the summary-only kernel's for recording=False)."""
+    name = load().rays_hip_window_kernel_name_for(C.byref(p), int(nray), 1 if recording else 0).decode()
+    if not name:
+        check_params(p)
+        raise RaysHipError("rays_hip_window_kernel_name_for: no continuation kernel for this configuration")
+    return name
+
+
+def _state_struct(state) -> RayStateStruct:
+    """state: an object with the seven attributes of rays_ray_state_t as device tensors (sg_err may be None)."""
+    ptr = lambda t: None if t is None else (t.data_ptr() or None)
+    return RayStateStruct(ptr(state.v), ptr(state.s), ptr(state.nstep), ptr(state.stop_code), ptr(state.resid),
+                          ptr(state.sg_err), ptr(state.flags))
+
+
+def state_init_device(p: RaysParams, nray: int, d_rvec0: int, d_rindex_vec0: int, state, d_start_ray_vec: int = 0,
+                      stream: int = 0):
+    """rays_hip_state_init_device: the saved ray state of every ray at its launch point (initialize_ode_vector and the
+    initial check_save); d_start_ray_vec (may be 0) gets point 1.  Asynchronous on `stream`."""
+    ensure_tables(p)
+    st = _state_struct(state)
+    _check(load().rays_hip_state_init_device(C.byref(p), int(nray), d_rvec0 or None, d_rindex_vec0 or None, C.byref(st),
+                                             d_start_ray_vec or None, stream or None), "rays_hip_state_init_device")
+
+
+def trace_window_device(p: RaysParams, nray: int, state, n_steps: int, d_ray_vec_win: int, d_residual_win: int,
+                        d_npoints_win: int, stream: int = 0):
+    """rays_hip_trace_window_device: every ray under way advances by at most n_steps recorded steps; the state is updated
+    in place.  Both window arrays 0: a summary window.  Asynchronous on `stream`."""
+    ensure_tables(p)
+    st = _state_struct(state)
+    _check(load().rays_hip_trace_window_device(C.byref(p), int(nray), C.byref(st), int(n_steps), d_ray_vec_win or None,
+                                               d_residual_win or None, d_npoints_win or None, stream or None),
+           "rays_hip_trace_window_device")
+
+
+def state_summary_device(p: RaysParams, nray: int, state, d_npoints: int, d_stop_code: int, d_end_ray_vec: int,
+                         d_end_residuals: int, d_max_residuals: int, stream: int = 0):
+    """rays_hip_state_summary_device: the five per-ray summary arrays of a trace from the state."""
+    st = _state_struct(state)
+    _check(load().rays_hip_state_summary_device(C.byref(p), int(nray), C.byref(st), d_npoints or None, d_stop_code or None,
+                                                d_end_ray_vec or None, d_end_residuals or None, d_max_residuals or None,
+                                                stream or None), "rays_hip_state_summary_device")
+
+
+def trace_windowed_host(p: RaysParams, rvec0, rindex_vec0, n_steps: int, ngpu: int = 0, out: dict = None) -> dict:
+    """rays_hip_trace_windowed: trace_host's arguments and results, traced in windows of n_steps on one device -- the
+    device holds the ray state and two window slabs, never [nray][nstep_max + 1][nv]."""
+    lib = load()
+    rvec0 = np.ascontiguousarray(rvec0, dtype=np.float64)
+    rindex_vec0 = np.ascontiguousarray(rindex_vec0, dtype=np.float64)
+    nray, nv, npt = len(rvec0), p.nv, p.nstep_max + 1
+    if ngpu is not None and lib.rays_hip_init(int(ngpu)) < 0:
+        raise RaysHipError("rays_hip_init: " + last_error())
+    ensure_tables(p)
+    if out is None:
+        out = dict(
+            ray_vec=np.zeros((nray, npt, nv)), residual=np.zeros((nray, npt)),
+            npoints=np.zeros(nray, dtype=np.int32), stop_code=np.zeros(nray, dtype=np.int32),
+            end_ray_vec=np.zeros((nray, nv)), end_residuals=np.zeros(nray), max_residuals=np.zeros(nray))
+    elif out["ray_vec"].shape != (nray, npt, nv) or not out["ray_vec"].flags.c_contiguous:
+        raise ValueError("trace_windowed_host: `out` does not match this fan")
+    el = C.c_double(0.0)
+    rc = lib.rays_hip_trace_windowed(C.byref(p), nray, _dp(rvec0), _dp(rindex_vec0), int(n_steps), _dp(out["ray_vec"]),
+                                     _dp(out["residual"]), _ip(out["npoints"]), _ip(out["stop_code"]),
+                                     _dp(out["end_ray_vec"]), _dp(out["end_residuals"]), _dp(out["max_residuals"]),
+                                     C.byref(el))
+    _check(rc, "rays_hip_trace_windowed")
     out["elapsed_s"] = el.value
     return out
 

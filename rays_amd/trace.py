@@ -122,6 +122,56 @@ class RaySummaries:
         return int(np.maximum(self.npoints.astype(np.int64) - 1, 0).sum())
 
 
+class RayState:
+    """The saved ray state of windowed tracing (include/rays_hip.h: rays_ray_state_t) as torch tensors: everything a
+    fan needs to go on after a window -- v[nray][nv], s[nray], nstep[nray], stop_code[nray], resid[nray][3],
+    sg_err[nray][2], flags[nray].  Nothing in it is an address or depends on a launch: save() / load() take it to an
+    npz file and back, onto any device."""
+
+    FIELDS = (("v", "float64"), ("s", "float64"), ("nstep", "int32"), ("stop_code", "int32"), ("resid", "float64"),
+              ("sg_err", "float64"), ("flags", "int32"))
+
+    def __init__(self, nray: int, nv: int, device=None):
+        import torch
+
+        self.nray, self.nv = int(nray), int(nv)
+        shapes = dict(v=(nray, nv), s=(nray,), nstep=(nray,), stop_code=(nray,), resid=(nray, 3), sg_err=(nray, 2),
+                      flags=(nray,))
+        for name, dt in self.FIELDS:
+            setattr(self, name, torch.zeros(shapes[name], dtype=getattr(torch, dt), device=device))
+
+    @property
+    def device(self):
+        return self.v.device
+
+    def numpy(self) -> Dict[str, np.ndarray]:
+        return {name: getattr(self, name).cpu().numpy() for name, _ in self.FIELDS}
+
+    def save(self, path: str):
+        """np.savez of the seven arrays (blocking: the tensors are copied to the host)."""
+        np.savez(path, **self.numpy())
+
+    @classmethod
+    def load(cls, path: str, device=None) -> "RayState":
+        """A state saved by save(), in fresh tensors on `device`."""
+        import torch
+
+        with np.load(path, allow_pickle=False) as z:
+            nray, nv = z["v"].shape
+            st = cls(nray, nv, device=device)
+            for name, dt in cls.FIELDS:
+                a = np.ascontiguousarray(z[name], dtype=dt)
+                if a.shape != tuple(getattr(st, name).shape):
+                    raise ValueError(f"RayState.load: {name} has shape {a.shape}")
+                getattr(st, name).copy_(torch.as_tensor(a))
+        return st
+
+    @property
+    def under_way(self) -> int:
+        """Rays that have not ended (a synchronising copy)."""
+        return int((self.stop_code == 0).sum().item())
+
+
 @dataclasses.dataclass
 class RayDeposition:
     """What a fused trace + deposition returns (rays_hip_trace_deposition*): the per-ray summaries and one deposition
@@ -230,11 +280,20 @@ class RaysRun:
     def nray(self) -> int:
         return len(self.rvec0)
 
-    def trace_rays(self, ngpu: int = 1, trajectories: bool = True, deposition=None, want_work: bool = False):
-        """trajectories=False: the summary-only trace (RaySummaries; no trajectory array on the device or the host).
+    def trace_rays(self, ngpu: int = 1, trajectories: bool = True, deposition=None, want_work: bool = False,
+                   window: Optional[int] = None):
+        """window=n_steps: the same RayResults, traced in windows of n_steps on one device (hip.trace_windowed_host):
+        the device holds the ray state and two window slabs, and each window's points reach the host arrays through
+        pinned memory while the next window runs -- the way to trace a fan whose trajectories exceed the card.
+        trajectories=False: the summary-only trace (RaySummaries; no trajectory array on the device or the host).
         trajectories=False, deposition=(which, n_bins): the fused trace + deposition (RayDeposition: the summaries and
         the profile `which` of the launcher's power weights ray_pwr_wt -- initial_ray_power of the run's results -- with
         work[nray][n_bins] if want_work)."""
+        if window is not None:
+            if deposition is not None or not trajectories:
+                raise ValueError("RaysRun.trace_rays: window=... assembles the full trajectories; it goes with neither "
+                                 "trajectories=False nor deposition=...")
+            return RayResults(**hip.trace_windowed_host(self.params, self.rvec0, self.rindex_vec0, int(window), ngpu=ngpu))
         if deposition is not None:
             if trajectories:
                 raise ValueError("RaysRun.trace_rays: deposition=... is the fused trace without trajectories -- pass "
@@ -279,10 +338,17 @@ class DeviceTrace:
     trajectories=False, deposition=(which, n_bins, power): the fused trace + deposition (rays_hip_trace_deposition_device)
     -- additionally .work[n_bins][nray] (bin-major, zeroed by every launch) and .profile[n_bins] of the profile `which`
     with the per-ray power weights `power`; profile_in: a tensor[n_bins] of running sums the profile continues (the
-    block of rays before this one), None = from zero."""
+    block of rays before this one), None = from zero.
+    window=n_steps: windowed tracing (rays_hip_state_init_device / rays_hip_trace_window_device).  No tensor with an
+    nstep_max + 1 axis exists: .state is the saved RayState, .ray_vec / .residual are ONE window slab
+    [nray][n_steps][nv] / [nray][n_steps] (None with trajectories=False) and .npoints_win[nray] says how many points of
+    it each ray recorded in the last window.  launch() puts every ray at its launch point (start_ray_vec = point 1,
+    residual 0); advance() runs one window and returns (ray_vec_win, residual_win, npoints_win) -- the object's own
+    tensors, overwritten by the next advance(); results() gives the state's RaySummaries, rays under way included as
+    they stand.  state= continues a RayState saved earlier instead of allocating one."""
 
     def __init__(self, params: RaysParams, rvec0, rindex_vec0, device=None, trajectories: bool = True, deposition=None,
-                 profile_in=None):
+                 profile_in=None, window: Optional[int] = None, state: Optional[RayState] = None):
         import torch
 
         self.torch = torch
@@ -307,10 +373,28 @@ class DeviceTrace:
         nv, npt = params.nv, params.nstep_max + 1
         f64, i32 = torch.float64, torch.int32
         self.ray_vec = self.residual = self.start_ray_vec = None
+        self.window = None if window is None else int(window)
+        self.state = self.npoints_win = None
+        if self.window is not None:
+            if deposition is not None:
+                raise ValueError("DeviceTrace: window=... does not go with deposition=... (the fused variant is not continued)")
+            if self.window < 1:
+                raise ValueError("DeviceTrace: window must be >= 1")
+        elif state is not None:
+            raise ValueError("DeviceTrace: state= without window=...")
         with torch.cuda.device(self.device):
             self.rvec0 = torch.as_tensor(np.ascontiguousarray(rvec0), dtype=f64).to(self.device)
             self.rindex_vec0 = torch.as_tensor(np.ascontiguousarray(rindex_vec0), dtype=f64).to(self.device)
-            if self.trajectories:
+            if self.window is not None:
+                if state is not None and (state.nray != self.nray or state.nv != nv):
+                    raise ValueError("DeviceTrace: state= does not match this fan")
+                self.state = state if state is not None else RayState(self.nray, nv, device=self.device)
+                if self.trajectories:
+                    self.ray_vec = torch.zeros((self.nray, self.window, nv), dtype=f64, device=self.device)
+                    self.residual = torch.zeros((self.nray, self.window), dtype=f64, device=self.device)
+                self.npoints_win = torch.zeros(self.nray, dtype=i32, device=self.device)
+                self.start_ray_vec = torch.zeros((self.nray, nv), dtype=f64, device=self.device)
+            elif self.trajectories:
                 # zero-filled once, like initialize_ray_results_m (ray_results_m.f90:154-164)
                 self.ray_vec = torch.zeros((self.nray, npt, nv), dtype=f64, device=self.device)
                 self.residual = torch.zeros((self.nray, npt), dtype=f64, device=self.device)
@@ -332,6 +416,10 @@ class DeviceTrace:
     def launch(self, zero_fill: bool = True):
         t = self.torch
         stream = t.cuda.current_stream(self.device).cuda_stream
+        if self.window is not None:
+            hip.state_init_device(self.params, self.nray, self.rvec0.data_ptr(), self.rindex_vec0.data_ptr(), self.state,
+                                  self.start_ray_vec.data_ptr(), stream=stream)
+            return
         if self.deposition is not None:
             hip.trace_deposition_device(self.params, self.nray, self.rvec0.data_ptr(), self.rindex_vec0.data_ptr(),
                                         self.power.data_ptr(), self.deposition[0], self.deposition[1],
@@ -353,6 +441,29 @@ class DeviceTrace:
                          self.end_residuals.data_ptr(), self.max_residuals.data_ptr(),
                          stream=stream, zero_fill=zero_fill)
 
+    def advance(self, n_steps: Optional[int] = None, recording: Optional[bool] = None):
+        """One window: every ray under way advances by at most n_steps (default: the window length) recorded steps, and
+        .state is updated in place.  recording=False: a summary window (nothing is stored; possible at any time).
+        Returns (ray_vec_win, residual_win, npoints_win): the window's new points -- ray_vec_win[r, :npoints_win[r]] --
+        or (None, None, npoints_win).  Asynchronous on the current torch stream."""
+        if self.window is None:
+            raise RuntimeError("DeviceTrace.advance: this trace has no window (pass window=n_steps)")
+        n = self.window if n_steps is None else int(n_steps)
+        rec = self.trajectories if recording is None else bool(recording)
+        if rec and not self.trajectories:
+            raise ValueError("DeviceTrace.advance: recording=True on a trace built with trajectories=False")
+        if rec and n > self.window:
+            raise ValueError("DeviceTrace.advance: n_steps exceeds the window slab this trace allocated")
+        stream = self.torch.cuda.current_stream(self.device).cuda_stream
+        hip.trace_window_device(self.params, self.nray, self.state, n, self.ray_vec.data_ptr() if rec else 0,
+                                self.residual.data_ptr() if rec else 0, self.npoints_win.data_ptr(), stream=stream)
+        if not rec:
+            return None, None, self.npoints_win
+        # the slab of a shorter window is laid out with ITS stride: [nray][n][nv]
+        rv = self.ray_vec.view(-1)[:self.nray * n * self.params.nv].view(self.nray, n, self.params.nv)
+        res = self.residual.view(-1)[:self.nray * n].view(self.nray, n)
+        return rv, res, self.npoints_win
+
     def diagnostics(self, fields=None, packed: bool = False) -> Dict[str, Any]:
         """ray_detailed_diagnostics of the trace as it lies on the device (hip.ray_diagnostics_device): {field name:
         tensor[nray][nstep_max+1]} for `fields` (hip.DIAG_FIELDS; None = all) -- views of one [k][nray][nstep_max+1]
@@ -363,6 +474,8 @@ class DeviceTrace:
         allocate k * total doubles instead of k * nray * (nstep_max + 1) it reads offsets[nray] once before
         allocating: ONE 8-BYTE SYNCHRONISING COPY behind launch(); the diagnostics kernel itself is asynchronous."""
         t = self.torch
+        if self.window is not None:
+            raise RuntimeError("DeviceTrace.diagnostics: a windowed trace holds one window of points, not the trajectories")
         if not self.trajectories:
             raise RuntimeError("DeviceTrace.diagnostics: this trace is summary-only (trajectories=False) -- the per-point "
                                "diagnostics need the recorded points; trace with trajectories=True")
@@ -396,8 +509,16 @@ class DeviceTrace:
         return res
 
     def results(self):
+        if self.window is not None:
+            stream = self.torch.cuda.current_stream(self.device).cuda_stream
+            hip.state_summary_device(self.params, self.nray, self.state, self.npoints.data_ptr(), self.stop_code.data_ptr(),
+                                     self.end_ray_vec.data_ptr(), self.end_residuals.data_ptr(),
+                                     self.max_residuals.data_ptr(), stream=stream)
         self.torch.cuda.synchronize(self.device)
         c = lambda x: x.cpu().numpy()
+        if self.window is not None:
+            return RaySummaries(c(self.npoints), c(self.stop_code), c(self.start_ray_vec), c(self.end_ray_vec),
+                                c(self.end_residuals), c(self.max_residuals))
         if not self.trajectories:
             return RaySummaries(c(self.npoints), c(self.stop_code), c(self.start_ray_vec), c(self.end_ray_vec),
                                 c(self.end_residuals), c(self.max_residuals))

@@ -1,0 +1,294 @@
+"""CPU tier: windowed tracing (rays_hip_state_init_device / rays_hip_trace_window_device / rays_hip_state_summary_device /
+rays_hip_trace_windowed; kernels with kEqContinue in EQ) -- the product kernel sources in the continuation variant on
+the host emulation, one lane and whole waves; the host form and the device entries on the emulated runtime as a
+stand-alone program, plain and under ASan + UBSan; the Python state holder.  The reference is always the one-shot
+trace (the golden files or the oracle), never the windowed path itself, and every comparison is on bit patterns."""
+import os
+import struct
+import subprocess
+
+import numpy as np
+import pytest
+
+from rays_amd.params import copy_params
+from tests import oracle_lib
+from tests import summary_lib as sl
+from tests import window_lib as wl
+from tests.common import GOLDEN_CASES, ROOT, load_golden, stop_codes
+
+EMUL_DIR = os.path.join(ROOT, "tests", "hip_emul")
+SIZES = (7, 8, 9, 50)   # either side of the sector window's group of eight, and a long one
+
+
+def _lib_for(g):
+    lib = wl.emul_lib()
+    wl.set_axisym_tables(g, lib)
+    return lib
+
+
+def _assert_trajectories(out, ref_vec, ref_res, npoints, what, only_covered=False):
+    """Points 1..npoints of every ray are the reference's bytes; with only_covered the points no recording window
+    covered are skipped (and must still hold the nan they were initialised with)."""
+    for r, n in enumerate(npoints):
+        if only_covered:
+            c = out["covered"][r, :n]
+            assert np.isnan(out["residual"][r, :n][~c]).all(), what
+        else:
+            c = np.ones(n, dtype=bool)
+            assert out["covered"][r, :n].all() and not out["covered"][r, n:].any(), what
+        np.testing.assert_array_equal(out["ray_vec"][r, :n][c], ref_vec[r, :n][c], err_msg=f"{what}: ray_vec, ray {r}")
+        np.testing.assert_array_equal(out["residual"][r, :n][c], ref_res[r, :n][c], err_msg=f"{what}: residual, ray {r}")
+
+
+def _assert_summaries(out, ref, what):
+    for k in wl.SUMMARY_KEYS:
+        np.testing.assert_array_equal(out[k], ref[k], err_msg=f"{what}: {k}")
+
+
+# ---- 1. the fixtures on one emulated lane --------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", GOLDEN_CASES)
+def test_window_kernel_source_on_host_equals_reference(name):
+    """All 38 fixtures, window sizes 7, 8, 9 and 50: point 1 plus the windows' points are the golden ray_vec / residual /
+    npoints / stop codes and the state's summaries are the golden summaries -- with every window recording, with none
+    recording (the summary policy), and with the two alternating, where the recorded windows equal the matching slices."""
+    g, nml, p = load_golden(name)
+    lib = _lib_for(g)
+    ref = sl.golden_summaries(g)
+    for w in SIZES:
+        out = wl.trace_windowed(p, g["rvec0"], g["rindex_vec0"], [w], "record", lib=lib)
+        np.testing.assert_array_equal(out["npoints"], g["npoints"])
+        np.testing.assert_array_equal(out["stop_code"], stop_codes(g["stop_flag"]))
+        np.testing.assert_array_equal(out["start_ray_vec"], ref["start_ray_vec"])
+        _assert_trajectories(out, g["ray_vec"], g["residual"], g["npoints"], f"{name}, n_steps {w}")
+        _assert_summaries(out, ref, f"{name}, n_steps {w}")
+        _assert_summaries(wl.trace_windowed(p, g["rvec0"], g["rindex_vec0"], [w], "summary", lib=lib), ref,
+                          f"{name}, n_steps {w}, summary windows")
+        mixed = wl.trace_windowed(p, g["rvec0"], g["rindex_vec0"], [w], "mixed", lib=lib)
+        _assert_summaries(mixed, ref, f"{name}, n_steps {w}, mixed windows")
+        _assert_trajectories(mixed, g["ray_vec"], g["residual"], g["npoints"], f"{name}, n_steps {w}, mixed", only_covered=True)
+    # window lengths mixed freely
+    out = wl.trace_windowed(p, g["rvec0"], g["rindex_vec0"], [3, 1, 17, 2, 8], "record", lib=lib)
+    _assert_trajectories(out, g["ray_vec"], g["residual"], g["npoints"], f"{name}, mixed lengths")
+    _assert_summaries(out, ref, f"{name}, mixed lengths")
+
+
+# ---- 2. window size 1 to the end of every ray: every boundary is a pause -------------------------------------------------
+@pytest.mark.parametrize("name,every", [("cfg2_solovev1024_rk4", 64), ("gold_solovev64_sg_cold", 1),
+                                        ("gold_solovev64_sg_num", 1), ("gold_axisym64_eqdsk_damp_rk4", 1)])
+def test_window_of_one_step(name, every):
+    """An RK4 case (every 64th ray of the 1024-ray fan), an SG cold case, an SG finite-difference case and the damped
+    nv = 8 eqdsk case, one step per window, against the oracle's one-shot trace."""
+    g, nml, p = load_golden(name)
+    lib = _lib_for(g)
+    r0, n0 = g["rvec0_full"][::every].copy(), g["rindex_vec0_full"][::every].copy()
+    ref = oracle_lib.trace(p, r0, n0)
+    out = wl.trace_windowed(p, r0, n0, [1], "record", lib=lib)
+    _assert_trajectories(out, ref["ray_vec"], ref["residual"], ref["npoints"], name)
+    _assert_summaries(out, ref, name)
+    assert out["npoints"].max() > 20
+
+
+# ---- 3. the SG tolerances are state --------------------------------------------------------------------------------------
+def _sg_case_with_growing_tolerances():
+    """No fixture ray changes rel_err / abs_err and then goes on (in the fixtures the integrator's `iflag = 3` return,
+    SG_ode_m.f90:139-149, is always followed by the ray's end).  With rel_err0 and abs_err0 of gold_solovev64_sg_cold
+    tightened to the round-off level the integrator raises them on the way and the ray continues: the oracle is the
+    reference."""
+    g, nml, p = load_golden("gold_solovev64_sg_cold")
+    q = copy_params(p)
+    q.rel_err0, q.abs_err0 = 1e-15, 1e-15
+    q.nstep_max = 12   # (further along such a ray the integrator raises its tolerances thousands of times per output step)
+    return g, q, g["rvec0_full"][:6].copy(), g["rindex_vec0_full"][:6].copy()
+
+
+def test_sg_tolerances_are_carried_across_a_window_boundary():
+    """A window boundary right behind an output step in which rel_err / abs_err grew, on a ray that goes on: the next
+    window must start from the grown values.  Shown to bite: the same boundary with the tolerances put back to
+    rel_err0 / abs_err0 by hand gives another trajectory."""
+    g, q, r0, n0 = _sg_case_with_growing_tolerances()
+    lib = _lib_for(g)
+    ref = oracle_lib.trace(q, r0, n0)
+    # find the first output step after which a ray under way carries other tolerances than rel_err0 / abs_err0
+    st, _ = wl.state_init(q, r0, n0, lib=lib)
+    k_grow, grown = None, None
+    for k in range(1, q.nstep_max + 1):
+        wl.window(q, st, 1, False, lib=lib)
+        grown = (st["stop_code"] == 0) & ((st["sg_err"][:, 0] != q.rel_err0) | (st["sg_err"][:, 1] != q.abs_err0))
+        if grown.any():
+            k_grow = k
+            break
+    assert k_grow is not None, "no ray of the case grows its tolerances and goes on"
+    rays = np.nonzero(grown)[0]
+    assert (ref["npoints"][rays] > k_grow + 4).any()
+    out = wl.trace_windowed(q, r0, n0, [k_grow, q.nstep_max], "record", lib=lib)
+    _assert_trajectories(out, ref["ray_vec"], ref["residual"], ref["npoints"], "boundary behind the growing step")
+    _assert_summaries(out, ref, "boundary behind the growing step")
+    # by hand: what a variant that resets the tolerances at a window's start would compute
+    st, _ = wl.state_init(q, r0, n0, lib=lib)
+    wl.window(q, st, k_grow, False, lib=lib)
+    st["sg_err"][:, 0], st["sg_err"][:, 1] = q.rel_err0, q.abs_err0
+    rv, res, npw = wl.window(q, st, 4, True, lib=lib)
+    differs = [r for r in rays if npw[r] and not np.array_equal(rv[r, :npw[r]], ref["ray_vec"][r, k_grow + 1:k_grow + 1 + npw[r]])]
+    assert differs, "resetting the tolerances at the boundary changed nothing: the case does not test what it claims"
+
+
+# ---- 4. edge rays and whole emulated waves -------------------------------------------------------------------------------
+def _edge_fan():
+    """200 rays of the Solovev fan as in test_cpu_summary_trace.py::test_rk4_waves_with_refills (ray 7 is refused by the
+    initial check_save), and ray 9 launched from the last recorded point of ray 11: it passes the initial check and ends
+    on its very first step."""
+    g, nml, p = load_golden("cfg2_solovev1024_rk4")
+    r0, n0 = g["rvec0_full"][::5][:200].copy(), g["rindex_vec0_full"][::5][:200].copy()
+    n0[7] *= 3.0
+    first = oracle_lib.trace(p, r0[11:12], n0[11:12])
+    last = first["ray_vec"][0, first["npoints"][0] - 1]
+    k0 = first["ray_vec"][0, 0, 3] / n0[11, 0]
+    r0[9], n0[9] = last[:3], last[3:6] / k0
+    ref = oracle_lib.trace(p, r0, n0)
+    assert ref["npoints"][7] == 1 and not ref["end_ray_vec"][7].any()          # refused: all-zero summaries
+    assert ref["npoints"][9] == 1 and ref["end_ray_vec"][9].any()              # started, ended on its first step
+    assert len(set(ref["npoints"].tolist())) > 20
+    return g, p, r0, n0, ref
+
+
+_EDGE = {}
+
+
+def _edge():
+    if not _EDGE:
+        _EDGE["case"] = _edge_fan()
+    return _EDGE["case"]
+
+
+def test_edge_rays():
+    """A ray refused by the initial check (npoints 1, every summary field zero) and a ray that starts and ends on its
+    first step (npoints 1, end_ray_vec = its state) are told apart by the state; the windowed summaries of the fan
+    equal the one-shot ones; one more window after the end changes no byte of the state."""
+    g, p, r0, n0, ref = _edge()
+    lib = _lib_for(g)
+    for w, policy in ((16, "record"), (16, "summary"), (1000, "record")):
+        out = wl.trace_windowed(p, r0, n0, [w], policy, lib=lib)
+        _assert_summaries(out, ref, f"n_steps {w}, {policy}")
+        if policy == "record":
+            _assert_trajectories(out, ref["ray_vec"], ref["residual"], ref["npoints"], f"n_steps {w}")
+    st = out["state"]
+    assert st["flags"][7] & wl.REFUSED and not st["flags"][9] & wl.REFUSED
+    assert not out["end_ray_vec"][7].any() and out["max_residuals"][7] == 0.0
+    np.testing.assert_array_equal(out["end_ray_vec"][9], ref["end_ray_vec"][9])
+    # idempotent after the end
+    before = wl.state_bytes(st)
+    for rec in (True, False):
+        rv, res, npw = wl.window(p, st, 5, rec, lib=lib)
+        assert not npw.any() and wl.state_bytes(st) == before
+
+
+VARIANTS = {"default": [], "cost0": ["-DRAYS_REFILL_EVENT_COST=0"]}
+
+
+@pytest.mark.parametrize("variant", list(VARIANTS))
+def test_rk4_waves_with_refills(variant):
+    """The same 200 rays on ONE emulated wave (three times more rays than lanes: every lane is refilled, and from the
+    second window on most rays a lane is handed have ended already), n_steps = 16, in index order and "long rays first",
+    for both settings of RAYS_REFILL_EVENT_COST, against the oracle."""
+    g, p, r0, n0, ref = _edge()
+    lib = _lib_for(g)
+    wave = wl.emul_lib(wave=True, tag="" if variant == "default" else variant, defs=VARIANTS[variant])
+    for stride in (0, 2):
+        out = wl.trace_windowed(p, r0, n0, [16], "record", lib=lib, waves=("rk4", 1, stride), wave_lib=wave)
+        _assert_trajectories(out, ref["ray_vec"], ref["residual"], ref["npoints"], f"stride {stride}")
+        _assert_summaries(out, ref, f"stride {stride}")
+    out = wl.trace_windowed(p, r0, n0, [16], "mixed", lib=lib, waves=("rk4", 1, 2), wave_lib=wave)
+    _assert_summaries(out, ref, "mixed windows")
+    _assert_trajectories(out, ref["ray_vec"], ref["residual"], ref["npoints"], "mixed windows", only_covered=True)
+
+
+def test_sg_waves_with_refills():
+    """sg_trace_kernel's continuation variant: 160 rays of the Solovev fan on ONE wave, n_steps = 8."""
+    g, nml, p = load_golden("gold_solovev64_sg_cold")
+    reps = -(-160 // len(g["rvec0_full"]))
+    r0 = np.tile(g["rvec0_full"], (reps, 1))[:160].copy()
+    n0 = np.tile(g["rindex_vec0_full"], (reps, 1))[:160].copy()
+    n0[5] *= 3.0
+    q = copy_params(p)
+    q.nstep_max = min(q.nstep_max, 40)
+    ref = oracle_lib.trace(q, r0, n0)
+    assert ref["npoints"][5] == 1
+    out = wl.trace_windowed(q, r0, n0, [8], "record", lib=_lib_for(g), waves=("sg", 1, 0), wave_lib=wl.emul_lib(wave=True))
+    _assert_trajectories(out, ref["ray_vec"], ref["residual"], ref["npoints"], "sg waves")
+    _assert_summaries(out, ref, "sg waves")
+
+
+# ---- 5. save / load ---------------------------------------------------------------------------------------------------------
+def test_state_save_load_roundtrip(tmp_path):
+    """The state after window k goes to an npz file through rays_amd.trace.RayState, comes back into fresh buffers, and
+    the trace goes on from them: the same bytes as without the detour."""
+    torch = pytest.importorskip("torch")
+    from rays_amd.trace import RayState
+    g, nml, p = load_golden("gold_solovev64_sg_cold")
+    lib = _lib_for(g)
+    r0, n0 = g["rvec0"], g["rindex_vec0"]
+    ref = wl.trace_windowed(p, r0, n0, [6], "record", lib=lib)
+    st, start = wl.state_init(p, r0, n0, lib=lib)
+    wl.window(p, st, 6, True, lib=lib)
+    wl.window(p, st, 6, True, lib=lib)
+    holder = RayState(len(r0), p.nv)
+    for name, _ in RayState.FIELDS:
+        getattr(holder, name).copy_(torch.as_tensor(st[name]))
+    path = str(tmp_path / "state.npz")
+    holder.save(path)
+    back = RayState.load(path).numpy()
+    assert wl.state_bytes(back) == wl.state_bytes(st)
+    fresh = {k: np.ascontiguousarray(back[k]).copy() for k in wl.STATE_KEYS}
+    have = 1 + 12
+    while (fresh["stop_code"] == 0).any():
+        rv, res, npw = wl.window(p, fresh, 6, True, lib=lib)
+        for r in np.nonzero(npw)[0]:   # (a ray still under way has recorded every window in full)
+            assert have + npw[r] <= ref["npoints"][r]
+            np.testing.assert_array_equal(rv[r, :npw[r]], ref["ray_vec"][r, have:have + npw[r]])
+            np.testing.assert_array_equal(res[r, :npw[r]], ref["residual"][r, have:have + npw[r]])
+        have += 6
+    assert wl.state_bytes(fresh) == wl.state_bytes(ref["state"])
+
+
+# ---- 6. the C ABI on the emulated runtime, stand-alone -------------------------------------------------------------------------
+def _case_file(path):
+    g, nml, p = load_golden("cfg2_solovev1024_rk4")
+    q = copy_params(p)
+    q.nstep_max = 125
+    r0, n0 = g["rvec0_full"][:150].copy(), g["rindex_vec0_full"][:150].copy()
+    r0[17, 0] = 10.0      # launched outside the box: npoints = 1
+    n0[40] *= 3.0         # off the dispersion surface: stops at the initial check
+    full = oracle_lib.trace(q, r0, n0)
+    assert full["npoints"].min() == 1 and full["npoints"].max() == 126 and len(np.unique(full["npoints"])) > 5
+    with open(path, "wb") as f:
+        f.write(struct.pack("=3i", len(r0), q.nv, len(bytes(q))))
+        f.write(bytes(q))
+        for a in (r0, n0):
+            f.write(np.ascontiguousarray(a, dtype=np.float64).tobytes())
+        for k in wl.SUMMARY_KEYS:
+            f.write(np.ascontiguousarray(full[k], dtype=np.int32 if k in ("npoints", "stop_code") else np.float64).tobytes())
+        for k in ("ray_vec", "residual"):
+            f.write(np.concatenate([np.asarray(full[k], dtype=np.float64)[r, :n].ravel()
+                                    for r, n in enumerate(full["npoints"])]).tobytes())
+
+
+@pytest.mark.parametrize("sanitize", [False, True], ids=["plain", "asan_ubsan"])
+def test_c_abi_on_emulated_runtime(sanitize, tmp_path):
+    """rays_hip_trace_windowed against the oracle's trajectories with poisoned outputs that nothing past npoints may
+    touch, for window lengths 1, 7, 50 and one beyond nstep_max, on the first device of two device lists, with the
+    device bytes in use bounded by state + two slabs + inputs + summaries; the device entries with recording and
+    summary windows mixed, the state's summaries, idempotence after the end; every refusal by its message, nothing
+    launched by a refused call; the kernel names; after rays_hip_finalize the emulated driver holds nothing.  Once plain
+    and once as an ASan + UBSan executable with its own main (leak detection on)."""
+    subprocess.check_call(["make", "-s", "-j", str(min(4, os.cpu_count() or 1)), "-f", "Makefile.capi_window"] +
+                          (["SAN=1"] if sanitize else []), cwd=EMUL_DIR)
+    exe = os.path.join(EMUL_DIR, "build_capi_san/emul_window_capi_san" if sanitize else "build_capi/emul_window_capi")
+    case = str(tmp_path / "window_case.bin")
+    _case_file(case)
+    env = {k: v for k, v in os.environ.items() if k not in ("ASAN_OPTIONS", "UBSAN_OPTIONS", "LSAN_OPTIONS", "LD_PRELOAD")}
+    env.update(RAYS_EMUL_DEVICES="4")
+    if sanitize:
+        env.update(ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
+    r = subprocess.run([exe, case], env=env, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0 and "window capi ok" in r.stdout, (r.stdout + r.stderr)[-4000:]
+    assert "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
