@@ -33,52 +33,19 @@
 #include "rays_capi_resources.hpp"
 
 namespace rays {
-// The twelve (solver, equilibrium, derivative) kernel groups; each holds four entry lists (unit exponents x
-// multi_spec_damping).  The declarations here and find_kernel's table are generated from this one list.
-#define RAYS_GROUPS(X) \
-  X(0, 0, 0) X(0, 0, 1) X(0, 1, 0) X(0, 1, 1) X(0, 2, 0) X(0, 2, 1) \
-  X(1, 0, 0) X(1, 0, 1) X(1, 1, 0) X(1, 1, 1) X(1, 2, 0) X(1, 2, 1)
-#define RAYS_DECL_ENTRIES(attr, prefix, s, e, d) \
-  attr const KernelEntry* prefix##s##_##e##_##d##_0_0(int* n); \
-  attr const KernelEntry* prefix##s##_##e##_##d##_1_0(int* n); \
-  attr const KernelEntry* prefix##s##_##e##_##d##_0_1(int* n); \
-  attr const KernelEntry* prefix##s##_##e##_##d##_1_1(int* n);
-#define RAYS_DECL_REC(s, e, d) RAYS_DECL_ENTRIES(, rays_entries_, s, e, d)
-// the summary-only variants (rays_device.hpp: kEqNoTraj) of the same groups.  Weak: librays_hip.so holds all of them
-// (Makefile: SUM_OBJS); a library linked from this file and a few groups only -- the CPU tier's emulated C ABI --
-// finds the others null, and find_kernel then reports no summary kernel for them.
-#define RAYS_DECL_SUM(s, e, d) RAYS_DECL_ENTRIES(__attribute__((weak)), rays_entries_sum_, s, e, d)
-// the fused deposition variants (rays_device_arith.inc: kEqDeposit) of the slab and axisym_toroid groups (Makefile:
-// DEP_OBJS).  Weak for the same reason; no library defines those of the Solovev groups, which are null everywhere.
-#define RAYS_DECL_DEP(s, e, d) RAYS_DECL_ENTRIES(__attribute__((weak)), rays_entries_dep_, s, e, d)
-// the continuation variants (rays_device_arith.inc: kEqContinue; windowed tracing), recording and summary-only
-// (Makefile: WIN_OBJS).  Weak for the same reason.
-#define RAYS_DECL_WIN(s, e, d) RAYS_DECL_ENTRIES(__attribute__((weak)), rays_entries_win_, s, e, d)
-#define RAYS_DECL_WSUM(s, e, d) RAYS_DECL_ENTRIES(__attribute__((weak)), rays_entries_wsum_, s, e, d)
-RAYS_GROUPS(RAYS_DECL_REC)
-RAYS_GROUPS(RAYS_DECL_SUM)
-RAYS_GROUPS(RAYS_DECL_DEP)
-RAYS_GROUPS(RAYS_DECL_WIN)
-RAYS_GROUPS(RAYS_DECL_WSUM)
-#undef RAYS_DECL_WIN
-#undef RAYS_DECL_WSUM
-#undef RAYS_DECL_REC
-#undef RAYS_DECL_SUM
-#undef RAYS_DECL_DEP
-#undef RAYS_DECL_ENTRIES
-#define RAYS_DECL_TOL(e) \
-  const KernelEntry* rays_entries_tol_0_##e##_0_0_0(int* n); \
-  const KernelEntry* rays_entries_tol_0_##e##_0_1_0(int* n);
-RAYS_DECL_TOL(0)
-RAYS_DECL_TOL(1)
-RAYS_DECL_TOL(2)
+// The kernel groups linked into this library (rays_launch.hpp: KernelGroup).  The head is a plain pointer with a constant
+// initialiser, so it is in place before any object's static initialiser registers, whatever their order.
+KernelGroup* g_kernel_groups = nullptr;
+void register_kernel_group(KernelGroup* g) {
+  g->next = g_kernel_groups;
+  g_kernel_groups = g;
+}
 hipError_t launch_pack(bool pack, int nray, int nv, int nstep_max, const int32_t* npoints,
                        const long long* offsets, double* ray_vec, double* residual, double* packed_vec,
                        double* packed_res, hipStream_t stream);
 hipError_t launch_deposition(const DevParams& P, const DepArgs& D, const double* carry, double* profile,
                              hipStream_t s);
-// (rays_deposition.hip; weak like the fused kernels' entry lists: a library linked without them refuses the fused
-// entries by name)
+// (rays_deposition.hip; weak: a library linked without them refuses the fused entries by name)
 __attribute__((weak)) hipError_t launch_dep_trace_args(const DepTraceArgs& T, DepTraceArgs* d_out, hipStream_t s);
 __attribute__((weak)) hipError_t launch_profile_sum(int n_bins, int nray, const double* work, const double* carry,
                                                     double* profile, hipStream_t s);
@@ -171,6 +138,39 @@ std::atomic<int> g_numerics{initial_numerics()};
 //              the continuation variant (windowed tracing) of the exact kernel, recording or summary-only: always the
 //              one-ray-per-lane entry, whatever the fan size -- the only one built, and bit-identical to the others
 enum class KernelVariant { Recording, ExactTwin, Summary, Deposit, Window, WindowSummary };
+// The build of rays_inst.hip that holds a variant's kernels under the exact numerics (from Summary on the two
+// enumerations name the same builds in the same order).
+rays::KernelBuild build_of(KernelVariant v) {
+  static_assert((int)KernelVariant::Summary == (int)rays::KernelBuild::Summary &&
+                (int)KernelVariant::WindowSummary == (int)rays::KernelBuild::WindowSummary, "KernelVariant | KernelBuild");
+  return v < KernelVariant::Summary ? rays::KernelBuild::Recording : (rays::KernelBuild)(int)v;
+}
+
+// The registered kernel groups by [build][solver][equilibrium][derivative][unit exponents][multi_spec_damping], made
+// from the list on first use: a lookup is an array index.  Two groups under one key are a mistake of the build (an
+// object linked twice, or compiled with another object's switches): `duplicate` names the key, and every lookup fails.
+struct KernelIndex {
+  const rays::KernelGroup* g[rays::kKernelBuilds][2][3][2][2][2] = {};
+  std::string duplicate;
+};
+const KernelIndex& kernel_index() {
+  static const KernelIndex index = [] {
+    KernelIndex x;
+    for (const rays::KernelGroup* k = rays::g_kernel_groups; k; k = k->next) {
+      const rays::KernelGroup*& slot = x.g[(int)k->build][k->solver][k->eq_model][k->deriv][k->unit_exp != 0][k->multi_spec != 0];
+      if (slot) {
+        char key[160];
+        std::snprintf(key, sizeof key, "rays_hip: two kernel groups registered as build %d, solver %d, equilibrium %d, "
+                      "derivative %d, unit exponents %d, multi_spec_damping %d", (int)k->build, k->solver, k->eq_model,
+                      k->deriv, k->unit_exp, k->multi_spec);
+        x.duplicate = key;
+      }
+      slot = k;
+    }
+    return x;
+  }();
+  return index;
+}
 
 // nray: fan size (0 = unknown).  From two waves per SIMD worth of rays on, the two-waves-per-SIMD build
 // of the kernel is preferred where one exists (rays_rk4.hpp) -- under the tolerance flavour for the slab only: the
@@ -179,39 +179,16 @@ enum class KernelVariant { Recording, ExactTwin, Summary, Deposit, Window, Windo
 const rays::KernelEntry* find_kernel(const rays_params_t& p, long long nray = 0,
                                      KernelVariant variant = KernelVariant::Recording) {
   using namespace rays;
-  typedef const KernelEntry* (*Getter)(int*);
-  // [recording | summary | deposit | window | window summary][solver][equilibrium][derivative][unit exponents][multi_spec_damping]
-  struct Table {
-    Getter g[5][2][3][2][2][2];
-  };
-  static const Table table = [] {
-    Table t = {};
-#define RAYS_FILL(v, prefix, s, e, d)                                                                       \
-  t.g[v][s][e][d][0][0] = prefix##s##_##e##_##d##_0_0; t.g[v][s][e][d][0][1] = prefix##s##_##e##_##d##_0_1; \
-  t.g[v][s][e][d][1][0] = prefix##s##_##e##_##d##_1_0; t.g[v][s][e][d][1][1] = prefix##s##_##e##_##d##_1_1;
-#define RAYS_FILL_ALL(s, e, d) \
-  RAYS_FILL(0, rays_entries_, s, e, d) RAYS_FILL(1, rays_entries_sum_, s, e, d) RAYS_FILL(2, rays_entries_dep_, s, e, d) \
-  RAYS_FILL(3, rays_entries_win_, s, e, d) RAYS_FILL(4, rays_entries_wsum_, s, e, d)
-    RAYS_GROUPS(RAYS_FILL_ALL)
-#undef RAYS_FILL_ALL
-#undef RAYS_FILL
-    return t;
-  }();
-  // tolerance flavour of the cold RK4 groups [equilibrium][unit exponents]
-  static const Getter tol_getters[3][2] = {{rays_entries_tol_0_0_0_0_0, rays_entries_tol_0_0_0_1_0},
-                                           {rays_entries_tol_0_1_0_0_0, rays_entries_tol_0_1_0_1_0},
-                                           {rays_entries_tol_0_2_0_0_0, rays_entries_tol_0_2_0_1_0}};
-  int n = 0;
   const bool force_exact = variant == KernelVariant::ExactTwin;
   const bool tol = variant == KernelVariant::Recording && g_numerics.load() == RAYS_NUMERICS_TOLERANCE &&
                    p.ode_solver == RAYS_ODE_RK4 && p.ray_deriv == RAYS_DERIV_COLD && !p.multi_spec_damping;
-  const int row = variant == KernelVariant::Summary ? 1 : variant == KernelVariant::Deposit ? 2
-                  : variant == KernelVariant::Window ? 3 : variant == KernelVariant::WindowSummary ? 4 : 0;
-  const Getter getter = tol ? tol_getters[p.equilib_model][unit_exponents(p) ? 1 : 0]
-                            : table.g[row][p.ode_solver][p.equilib_model][p.ray_deriv][unit_exponents(p) ? 1 : 0]
-                                     [p.multi_spec_damping ? 1 : 0];
-  if (!getter) return nullptr;  // (a summary or deposit group this library was linked without)
-  const KernelEntry* e = getter(&n);
+  const KernelIndex& index = kernel_index();
+  if (!index.duplicate.empty()) return nullptr;  // (rays_hip_check_params reports it)
+  const KernelGroup* kg = index.g[(int)(tol ? KernelBuild::Tolerance : build_of(variant))][p.ode_solver][p.equilib_model]
+                                 [p.ray_deriv][unit_exponents(p) ? 1 : 0][p.multi_spec_damping ? 1 : 0];
+  if (!kg) return nullptr;  // (a group this library was linked without)
+  const KernelEntry* e = kg->entries;
+  const int n = kg->n;
   int ncu = 256;
   {
     int dev = 0;
@@ -623,6 +600,7 @@ int rays_hip_check_params(const rays_params_t* p) {
   }
   if (p->ode_solver == RAYS_ODE_SG && (p->rel_err0 < (double)1.e-10f || p->abs_err0 < (double)1.e-10f))
     return fail("initialize_SG_ode: rel_err0, abs_err0 too small");  // SG_ode_m.f90:63-66
+  if (!kernel_index().duplicate.empty()) return fail(kernel_index().duplicate);
   if (!find_kernel(*p)) {
     char msg[256];
     std::snprintf(msg, sizeof msg, "rays_hip: no kernel built for this configuration (%s, equilibrium %d, %d species, %s dD, "

@@ -1,8 +1,8 @@
 // rays_inst.hip -- kernel instantiations.  Compiled once per (solver, equilibrium, derivative,
 // unit-exponent) group:
 //   -DRAYS_INST_SOLVER={0,1} -DRAYS_INST_EQ={0,1,2} -DRAYS_INST_DERIV={0,1} -DRAYS_INST_UE={0,1} -DRAYS_INST_MS={0,1}
-//   -DRAYS_INST_EQT=<EQ + 4 UE + 8 MS + 16 TOL + 32 NOTRAJ + 64 DEPOSIT>  (the kernels' EQ template argument as a
-//   literal, for the kernel names)
+//   -DRAYS_INST_EQT=<the kernels' EQ template argument as a literal, for the kernel names>: computed in
+//   inst_rules.mk, which lists the variants below with their switches, and cross-checked here (static_assert)
 //   -DRAYS_INST_NOTRAJ=1: the summary-only variant of an exact group (rays_device.hpp: kEqNoTraj; no trajectory point
 //   is recorded).  The same shape lists below apply, so whatever the library traces it also traces summary-only.
 //   -DRAYS_INST_NOTRAJ=1 -DRAYS_INST_DEPOSIT=1: the fused deposition variant (rays_device_arith.inc: kEqDeposit; the
@@ -62,11 +62,9 @@
 #if !RAYS_INST_TOL && defined(RAYS_TOL_FLAVOUR)
 #error "-DRAYS_TOL_FLAVOUR without -DRAYS_INST_TOL=1: an exact kernel name would get tolerance arithmetic"
 #endif
-#define RAYS_CAT_(a, b, c, d, e, f) a##_##b##_##c##_##d##_##e##_##f
-#define RAYS_CAT(a, b, c, d, e, f) RAYS_CAT_(a, b, c, d, e, f)
 // the kernels' EQ template argument, as a literal (it appears in the kernel names rocprof prints)
 #ifndef RAYS_INST_EQT
-#error "pass -DRAYS_INST_EQT=<RAYS_INST_EQ + 4 RAYS_INST_UE + 8 RAYS_INST_MS + 16 RAYS_INST_TOL + 32 RAYS_INST_NOTRAJ + 64 RAYS_INST_DEPOSIT + 128 RAYS_INST_CONTINUE>"
+#error "pass -DRAYS_INST_EQT=<the kernels' EQ argument>: take the -D set of an object from inst_rules.mk (make print-defs)"
 #endif
 #define RAYS_STR_(x) #x
 #define RAYS_STR(x) RAYS_STR_(x)
@@ -142,8 +140,10 @@ hipError_t launch_group(const DevParams& P, const TraceArgs& A, hipStream_t stre
   return launch_persistent(sg_group_kernel<EQ, NS, RAYS_SG_GROUP_LANES>, GEO::kLdsBytes, P, A, stream, grid_blocks,
                            GEO::kRaysPerBlock);
 }
-#define RAYS_ENTRY_GROUP(NS) \
-  { RAYS_INST_SOLVER, EQ, NS, DERIV, 7, 1, sg_group_far_doubles_per_lane<RAYS_SG_GROUP_LANES>(), RAYS_SG_GROUP_LANES, "sg_group_kernel<" RAYS_STR(RAYS_INST_EQT) ", " #NS ", " RAYS_STR(RAYS_SG_GROUP_LANES) ">", &launch_group<NS> }
+#define RAYS_ENTRY_GROUP_(NS) \
+  { RAYS_INST_SOLVER, EQ, NS, DERIV, 7, 1, sg_group_far_doubles_per_lane<RAYS_SG_GROUP_LANES>(), RAYS_SG_GROUP_LANES, "sg_group_kernel<" RAYS_STR(RAYS_INST_EQT) ", " #NS ", " RAYS_STR(RAYS_SG_GROUP_LANES) ">", &launch_group<NS> },
+#else
+#define RAYS_ENTRY_GROUP_(NS)
 #endif
 #if RAYS_INST_SOLVER == 0
 #define RAYS_KNAME "rk4_trace_kernel"
@@ -155,17 +155,27 @@ hipError_t launch_group(const DevParams& P, const TraceArgs& A, hipStream_t stre
 #else
 #define RAYS_SG_FAR(NV) sg_far_doubles_per_lane<NV>()
 #endif
+// The entry macros carry their own trailing comma, so that a build which leaves a kernel out emits no record for it.
 #define RAYS_ENTRY_(NS, NV) \
-  { RAYS_INST_SOLVER, EQ, NS, DERIV, NV, 1, RAYS_SG_FAR(NV), 1, RAYS_KNAME "<" RAYS_STR(RAYS_INST_EQT) ", " #NS ", " RAYS_STR(RAYS_INST_DERIV) ", " #NV ">", &launch_one<NS, NV> RAYS_RESUME(NS, NV) }
+  { RAYS_INST_SOLVER, EQ, NS, DERIV, NV, 1, RAYS_SG_FAR(NV), 1, RAYS_KNAME "<" RAYS_STR(RAYS_INST_EQT) ", " #NS ", " RAYS_STR(RAYS_INST_DERIV) ", " #NV ">", &launch_one<NS, NV> RAYS_RESUME(NS, NV) },
 // two-waves-per-SIMD build of an RK4 kernel (large fans; rays_rk4.hpp)
 #define RAYS_ENTRY_OCC2_(NS, NV) \
-  { RAYS_INST_SOLVER, EQ, NS, DERIV, NV, 2, 0, 1, "rk4_trace_kernel_w2<" RAYS_STR(RAYS_INST_EQT) ", " #NS ", " RAYS_STR(RAYS_INST_DERIV) ", " #NV ">", &launch_one<NS, NV, 2> }
+  { RAYS_INST_SOLVER, EQ, NS, DERIV, NV, 2, 0, 1, "rk4_trace_kernel_w2<" RAYS_STR(RAYS_INST_EQT) ", " #NS ", " RAYS_STR(RAYS_INST_DERIV) ", " #NV ">", &launch_one<NS, NV, 2> },
+// Which entries of the lists below a build keeps: the fused deposition and the continuation objects leave out the
+// two-waves-per-SIMD and lane-group kernels (every shape has a one-ray-per-lane kernel, bit-identical to them).
+#if RAYS_INST_DEPOSIT || RAYS_INST_CONTINUE
+#define RAYS_ENTRY_OCC2(NS, NV)
+#define RAYS_ENTRY_GROUP(NS)
+#else
+#define RAYS_ENTRY_OCC2(NS, NV) RAYS_ENTRY_OCC2_(NS, NV)
+#define RAYS_ENTRY_GROUP(NS) RAYS_ENTRY_GROUP_(NS)
+#endif
 #if RAYS_INST_DEPOSIT
-// The fused deposition objects walk the same lists and keep the entries with the absorbed-power row: the others (and the
-// nv = 7 kernels of the other two families) come out as entries no configuration matches (ns = 0), not as kernels.
+// The fused deposition objects keep the shapes with the absorbed-power row (nv = 8 | 13; 8 + NS | 13 + NS in the MS
+// groups): a shape without it compiles no kernel and leaves a record without a launcher (ns = 0), which no lookup matches.
 template <int NS, int NV, bool DAMPED = RayVec<RAYS_INST_MS != 0, NS, NV>::DAMP>
 struct DepEntry {
-  static constexpr KernelEntry get(const char*) { return KernelEntry{RAYS_INST_SOLVER, EQ, 0, DERIV, 0, 1, 0, 1, "", nullptr, nullptr}; }
+  static constexpr KernelEntry get(const char*) { return KernelEntry{}; }
 };
 template <int NS, int NV>
 struct DepEntry<NS, NV, true> {
@@ -174,73 +184,56 @@ struct DepEntry<NS, NV, true> {
   }
 };
 #define RAYS_ENTRY(NS, NV) \
-  DepEntry<NS, NV>::get(RAYS_KNAME "<" RAYS_STR(RAYS_INST_EQT) ", " #NS ", " RAYS_STR(RAYS_INST_DERIV) ", " #NV ">")
-#define RAYS_ENTRY_OCC2(NS, NV) DepEntry<NS, 7>::get("")
-#undef RAYS_ENTRY_GROUP
-#define RAYS_ENTRY_GROUP(NS) DepEntry<NS, 7>::get("")
-#elif RAYS_INST_CONTINUE
-// The continuation objects walk the same lists and keep the one-ray-per-lane kernels: the two-waves-per-SIMD and
-// lane-group entries come out as entries no configuration matches (ns = 0), not as kernels.
-#define RAYS_ENTRY(NS, NV) RAYS_ENTRY_(NS, NV)
-#define RAYS_ENTRY_OCC2(NS, NV) KernelEntry{RAYS_INST_SOLVER, EQ, 0, DERIV, 0, 1, 0, 1, "", nullptr, nullptr}
-#undef RAYS_ENTRY_GROUP
-#define RAYS_ENTRY_GROUP(NS) KernelEntry{RAYS_INST_SOLVER, EQ, 0, DERIV, 0, 1, 0, 1, "", nullptr, nullptr}
+  DepEntry<NS, NV>::get(RAYS_KNAME "<" RAYS_STR(RAYS_INST_EQT) ", " #NS ", " RAYS_STR(RAYS_INST_DERIV) ", " #NV ">"),
 #else
 #define RAYS_ENTRY(NS, NV) RAYS_ENTRY_(NS, NV)
-#define RAYS_ENTRY_OCC2(NS, NV) RAYS_ENTRY_OCC2_(NS, NV)
 #endif
 
 const KernelEntry kEntries[] = {
 #if RAYS_INST_MS
     // multi_spec_damping: nv = 7 + 1 + (1 + nspec) (+ 5 with integrate_eq_gradients), ode_m.f90:160-173
 #if defined(RAYS_INST_FAST) || !defined(RAYS_INST_FULL)
-    RAYS_ENTRY(2, 10), RAYS_ENTRY(2, 15),
+    RAYS_ENTRY(2, 10) RAYS_ENTRY(2, 15)
 #else
-    RAYS_ENTRY(1, 9), RAYS_ENTRY(2, 10), RAYS_ENTRY(3, 11), RAYS_ENTRY(4, 12), RAYS_ENTRY(5, 13), RAYS_ENTRY(6, 14),
-    RAYS_ENTRY(1, 14), RAYS_ENTRY(2, 15), RAYS_ENTRY(3, 16), RAYS_ENTRY(4, 17), RAYS_ENTRY(5, 18), RAYS_ENTRY(6, 19),
+    RAYS_ENTRY(1, 9) RAYS_ENTRY(2, 10) RAYS_ENTRY(3, 11) RAYS_ENTRY(4, 12) RAYS_ENTRY(5, 13) RAYS_ENTRY(6, 14)
+    RAYS_ENTRY(1, 14) RAYS_ENTRY(2, 15) RAYS_ENTRY(3, 16) RAYS_ENTRY(4, 17) RAYS_ENTRY(5, 18) RAYS_ENTRY(6, 19)
 #endif
 #elif defined(RAYS_INST_FAST)  // developer builds (make FAST=1): electrons + one ion species only
-    RAYS_ENTRY(2, 7), RAYS_ENTRY(2, 8),
-#ifdef RAYS_INST_GROUP
-    RAYS_ENTRY_GROUP(2),
-#endif
+    RAYS_ENTRY(2, 7) RAYS_ENTRY(2, 8)
+    RAYS_ENTRY_GROUP(2)
 #if RAYS_INST_SOLVER == 0 && RAYS_INST_EQ != 2 && !defined(RAYS_HOST_EMUL)
-    RAYS_ENTRY_OCC2(2, 7),
+    RAYS_ENTRY_OCC2(2, 7)
 #endif
 #elif !defined(RAYS_INST_FULL)  // the default build: NS = 2 throughout + the shapes configs / fixtures reach
-    RAYS_ENTRY(2, 7), RAYS_ENTRY(2, 12), RAYS_ENTRY(2, 8), RAYS_ENTRY(2, 13),
-#ifdef RAYS_INST_GROUP
-    RAYS_ENTRY_GROUP(2),
-#endif
+    RAYS_ENTRY(2, 7) RAYS_ENTRY(2, 12) RAYS_ENTRY(2, 8) RAYS_ENTRY(2, 13)
+    RAYS_ENTRY_GROUP(2)
 #if RAYS_INST_SOLVER == 0 && RAYS_INST_EQ != 2
-    RAYS_ENTRY_OCC2(2, 7),
+    RAYS_ENTRY_OCC2(2, 7)
 #endif
 #if RAYS_INST_SOLVER == 0 && RAYS_INST_EQ == 0 && RAYS_INST_DERIV == 0 && RAYS_INST_UE == 1
-    RAYS_ENTRY(1, 7), RAYS_ENTRY_OCC2(1, 7),   // electrons only (gold_slab_ns1_rk4)
+    RAYS_ENTRY(1, 7) RAYS_ENTRY_OCC2(1, 7)   // electrons only (gold_slab_ns1_rk4)
 #endif
 #if RAYS_INST_SOLVER == 1 && RAYS_INST_EQ == 0 && RAYS_INST_DERIV == 1 && RAYS_INST_UE == 1
-    RAYS_ENTRY(3, 7), RAYS_ENTRY_GROUP(3),     // three species (gold_slab_shear_gauss_3spec_sg_num)
+    RAYS_ENTRY(3, 7) RAYS_ENTRY_GROUP(3)     // three species (gold_slab_shear_gauss_3spec_sg_num)
 #endif
 #if RAYS_INST_SOLVER == 0 && RAYS_INST_EQ == 1 && RAYS_INST_DERIV == 1 && RAYS_INST_UE == 1
-    RAYS_ENTRY(4, 7),                          // D + T + 3He (gold_solovev64_4spec_rk4_num)
+    RAYS_ENTRY(4, 7)                          // D + T + 3He (gold_solovev64_4spec_rk4_num)
 #endif
 #if RAYS_INST_SOLVER == 1 && RAYS_INST_EQ == 0 && RAYS_INST_DERIV == 0 && RAYS_INST_UE == 1
-    RAYS_ENTRY(6, 7),                          // five ion species (gold_slab_6spec_sg)
+    RAYS_ENTRY(6, 7)                          // five ion species (gold_slab_6spec_sg)
 #endif
 #else
-    RAYS_ENTRY(1, 7), RAYS_ENTRY(2, 7), RAYS_ENTRY(3, 7), RAYS_ENTRY(4, 7), RAYS_ENTRY(5, 7), RAYS_ENTRY(6, 7),
-    RAYS_ENTRY(1, 12), RAYS_ENTRY(2, 12), RAYS_ENTRY(3, 12), RAYS_ENTRY(4, 12), RAYS_ENTRY(5, 12), RAYS_ENTRY(6, 12),
+    RAYS_ENTRY(1, 7) RAYS_ENTRY(2, 7) RAYS_ENTRY(3, 7) RAYS_ENTRY(4, 7) RAYS_ENTRY(5, 7) RAYS_ENTRY(6, 7)
+    RAYS_ENTRY(1, 12) RAYS_ENTRY(2, 12) RAYS_ENTRY(3, 12) RAYS_ENTRY(4, 12) RAYS_ENTRY(5, 12) RAYS_ENTRY(6, 12)
     // nv = 8 | 13: + total-absorption row (damping_model = 'damp_fund_ECH', ode_m.f90:162-166)
-    RAYS_ENTRY(1, 8), RAYS_ENTRY(2, 8), RAYS_ENTRY(3, 8), RAYS_ENTRY(4, 8), RAYS_ENTRY(5, 8), RAYS_ENTRY(6, 8),
-    RAYS_ENTRY(1, 13), RAYS_ENTRY(2, 13), RAYS_ENTRY(3, 13), RAYS_ENTRY(4, 13), RAYS_ENTRY(5, 13), RAYS_ENTRY(6, 13),
-#ifdef RAYS_INST_GROUP
+    RAYS_ENTRY(1, 8) RAYS_ENTRY(2, 8) RAYS_ENTRY(3, 8) RAYS_ENTRY(4, 8) RAYS_ENTRY(5, 8) RAYS_ENTRY(6, 8)
+    RAYS_ENTRY(1, 13) RAYS_ENTRY(2, 13) RAYS_ENTRY(3, 13) RAYS_ENTRY(4, 13) RAYS_ENTRY(5, 13) RAYS_ENTRY(6, 13)
     // SG + finite-difference dD, nv = 7: one ray per group of lanes (rays_sg_group.hpp); preferred by find_kernel
-    RAYS_ENTRY_GROUP(1), RAYS_ENTRY_GROUP(2), RAYS_ENTRY_GROUP(3), RAYS_ENTRY_GROUP(4), RAYS_ENTRY_GROUP(5), RAYS_ENTRY_GROUP(6),
-#endif
+    RAYS_ENTRY_GROUP(1) RAYS_ENTRY_GROUP(2) RAYS_ENTRY_GROUP(3) RAYS_ENTRY_GROUP(4) RAYS_ENTRY_GROUP(5) RAYS_ENTRY_GROUP(6)
 #if RAYS_INST_SOLVER == 0 && RAYS_INST_EQ != 2
     // the common analytic-equilibrium shapes also built for two waves per SIMD (the eqdsk + damping
     // kernels lose at 128 VGPRs: 4.4 -> 7.0 ms on the 256k-ray eqdsk fan)
-    RAYS_ENTRY_OCC2(1, 7), RAYS_ENTRY_OCC2(2, 7), RAYS_ENTRY_OCC2(3, 7),
+    RAYS_ENTRY_OCC2(1, 7) RAYS_ENTRY_OCC2(2, 7) RAYS_ENTRY_OCC2(3, 7)
 #endif
 #endif
 };
@@ -248,6 +241,8 @@ const KernelEntry kEntries[] = {
 
 #if defined(RAYS_SG_PROFILE) && RAYS_INST_SOLVER == 1
 // developer builds only: per-section wave clocks of this group's SG kernels
+#define RAYS_CAT_(a, b, c, d, e, f) a##_##b##_##c##_##d##_##e##_##f
+#define RAYS_CAT(a, b, c, d, e, f) RAYS_CAT_(a, b, c, d, e, f)
 extern "C" int RAYS_CAT(rays_debug_sg_profile, RAYS_INST_SOLVER, RAYS_INST_EQ, RAYS_INST_DERIV, RAYS_INST_UE, RAYS_INST_MS)(unsigned long long* out, int reset) {
   if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_sg_prof), sizeof(unsigned long long) * 32) != hipSuccess) return 1;
   if (reset) {
@@ -258,22 +253,16 @@ extern "C" int RAYS_CAT(rays_debug_sg_profile, RAYS_INST_SOLVER, RAYS_INST_EQ, R
 }
 #endif
 
-#if RAYS_INST_TOL
-#define RAYS_ENTRIES_NAME rays_entries_tol
-#elif RAYS_INST_DEPOSIT
-#define RAYS_ENTRIES_NAME rays_entries_dep
-#elif RAYS_INST_CONTINUE && RAYS_INST_NOTRAJ
-#define RAYS_ENTRIES_NAME rays_entries_wsum
-#elif RAYS_INST_CONTINUE
-#define RAYS_ENTRIES_NAME rays_entries_win
-#elif RAYS_INST_NOTRAJ
-#define RAYS_ENTRIES_NAME rays_entries_sum
-#else
-#define RAYS_ENTRIES_NAME rays_entries
-#endif
-const KernelEntry* RAYS_CAT(RAYS_ENTRIES_NAME, RAYS_INST_SOLVER, RAYS_INST_EQ, RAYS_INST_DERIV, RAYS_INST_UE, RAYS_INST_MS)(int* n) {
-  *n = (int)(sizeof(kEntries) / sizeof(kEntries[0]));
-  return kEntries;
-}
+namespace {
+constexpr KernelBuild kBuild = RAYS_INST_TOL        ? KernelBuild::Tolerance
+                               : RAYS_INST_DEPOSIT  ? KernelBuild::Deposit
+                               : RAYS_INST_CONTINUE ? (RAYS_INST_NOTRAJ ? KernelBuild::WindowSummary : KernelBuild::Window)
+                               : RAYS_INST_NOTRAJ   ? KernelBuild::Summary
+                                                    : KernelBuild::Recording;
+// this object's record in the C ABI object's list (rays_launch.hpp), handed over when the library is loaded
+KernelGroup g_group = {kBuild, RAYS_INST_SOLVER, RAYS_INST_EQ, RAYS_INST_DERIV, RAYS_INST_UE, RAYS_INST_MS,
+                       kEntries, (int)(sizeof(kEntries) / sizeof(kEntries[0])), nullptr};
+const int g_registered = (register_kernel_group(&g_group), 0);
+}  // namespace
 
 }  // namespace rays

@@ -32,6 +32,29 @@ struct KernelEntry {
   hipError_t (*resume)(const DevParams&, const TraceArgs&, hipStream_t stream);
 };
 
+// Which build of rays_inst.hip an object is (inst_rules.mk lists them with their switches):
+//   Recording      the kernels record the trajectories, exact arithmetic
+//   Tolerance      the tolerance flavour of a cold RK4 group
+//   Summary        summary-only: no trajectory point recorded
+//   Deposit        fused deposition: the summary-only kernel that also bins every accepted point
+//   Window, WindowSummary
+//                  the continuation kernels of windowed tracing, recording and summary-only
+enum class KernelBuild { Recording, Tolerance, Summary, Deposit, Window, WindowSummary };
+constexpr int kKernelBuilds = 6;
+
+// The entry list of one object of rays_inst.hip.  Every object holds one and hands it to register_kernel_group from a
+// static initialiser; rays_capi.hip looks kernels up in the list of what registered, so a group that is not linked in is
+// simply absent.  This relies on every object being named on the link line, as all our links do: an object pulled from
+// a static archive would be dropped unreferenced, and its kernels with it.
+struct KernelGroup {
+  KernelBuild build;
+  int solver, eq_model, deriv, unit_exp, multi_spec;
+  const KernelEntry* entries;
+  int n;
+  KernelGroup* next;
+};
+void register_kernel_group(KernelGroup* g);  // (defined once, in the C ABI object: rays_capi.hip)
+
 constexpr int kBlock = 256;
 
 // Compute units of a device, asked once per process (hipGetDeviceProperties is slow; this sits on the

@@ -17,10 +17,6 @@ hipError_t launch_ray_init(int, int, const DevParams&, const FanArgs&, int, doub
                            hipStream_t) { return hipErrorNotSupported; }
 int ray_init_block() { return 256; }
 void probe_kernel(const DevParams, int, int, int, int, const double*, double*, double*, double*, double*, int*) {}
-
-// kernel groups without an emulated build
-#define RAYS_NO_GROUP(name) const KernelEntry* name(int* n) { *n = 0; return nullptr; }
-#include "emul_capi_groups.inc"
 }  // namespace rays
 
 // test hooks of the emulated runtime

@@ -1,6 +1,6 @@
 // TEST INFRASTRUCTURE ONLY: the host form of the fused trace + deposition (rays_hip_trace_deposition,
 // rays_amd/csrc/rays_capi.hip) as a stand-alone program on the emulated HIP runtime with four devices -- for plain and
-// for sanitizer runs (tests/hip_emul/Makefile.capi_fused; tests/test_cpu_fused_deposition.py writes the case file and
+// for sanitizer runs (tests/hip_emul/Makefile.capi, target fused; tests/test_cpu_fused_deposition.py writes the case file and
 // starts it).
 //   emul_fused_capi <case file>
 // Case file (native endianness): int32 nray, nv, n_bins, which, nx, sizeof(rays_params_t); the parameter block; real64

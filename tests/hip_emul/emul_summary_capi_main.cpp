@@ -1,6 +1,6 @@
 // TEST INFRASTRUCTURE ONLY: the host form of summary-only tracing (rays_hip_trace_summary, rays_amd/csrc/rays_capi.hip)
 // as a stand-alone program on the emulated HIP runtime with four devices -- for plain and for sanitizer runs
-// (tests/hip_emul/Makefile.capi_summary; tests/test_cpu_summary_trace.py writes the case file and starts it).
+// (tests/hip_emul/Makefile.capi, target summary; tests/test_cpu_summary_trace.py writes the case file and starts it).
 //   emul_summary_capi <case file>
 // Case file (native endianness): int32 nray, nv, sizeof(rays_params_t); the parameter block; rvec0[nray][3],
 // rindex_vec0[nray][3]; then the oracle's summaries of these rays: npoints[nray], stop_code[nray] (int32),

@@ -1,7 +1,7 @@
 // TEST INFRASTRUCTURE ONLY: windowed tracing through the product's C ABI (rays_hip_state_init_device,
 // rays_hip_trace_window_device, rays_hip_state_summary_device, rays_hip_trace_windowed; rays_amd/csrc/rays_capi.hip) as a
 // stand-alone program on the emulated HIP runtime -- for plain and for sanitizer runs (tests/hip_emul/
-// Makefile.capi_window; tests/test_cpu_window_trace.py writes the case file and starts it).
+// Makefile.capi, target window; tests/test_cpu_window_trace.py writes the case file and starts it).
 //   emul_window_capi <case file>
 // Case file (native endianness): int32 nray, nv, sizeof(rays_params_t); the parameter block; rvec0[nray][3],
 // rindex_vec0[nray][3]; then the oracle's summaries of these rays: npoints[nray], stop_code[nray] (int32),

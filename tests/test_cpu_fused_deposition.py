@@ -175,7 +175,7 @@ def test_host_entry_on_emulated_devices(sanitize, tmp_path):
     one-lane emulation's, the profile chained over the blocks equals the single block's ray-ordered sum; the named
     refusals; after rays_hip_finalize the emulated driver reports no live allocation, pinned block, stream or event.
     Once plain and once as an ASan + UBSan executable with its own main (leak detection on)."""
-    subprocess.check_call(["make", "-s", "-j", str(min(4, os.cpu_count() or 1)), "-f", "Makefile.capi_fused"] +
+    subprocess.check_call(["make", "-s", "-j", str(min(4, os.cpu_count() or 1)), "-f", "Makefile.capi", "fused"] +
                           (["SAN=1"] if sanitize else []), cwd=EMUL_DIR)
     exe = os.path.join(EMUL_DIR, "build_capi_san/emul_fused_capi_san" if sanitize else "build_capi/emul_fused_capi")
     case = str(tmp_path / "fused_case.bin")

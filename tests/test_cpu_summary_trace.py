@@ -150,7 +150,7 @@ def test_host_entry_on_emulated_devices(sanitize, tmp_path):
     rays_hip_trace on the same device lists and on one that repeats a device, with and without the kept result, and
     rays_hip_trace_gather on one device reproduce the oracle's trajectories bit for bit and write nothing else.
     Once plain and once as an ASan + UBSan executable with its own main (leak detection on)."""
-    subprocess.check_call(["make", "-s", "-j", str(min(4, os.cpu_count() or 1)), "-f", "Makefile.capi_summary"] +
+    subprocess.check_call(["make", "-s", "-j", str(min(4, os.cpu_count() or 1)), "-f", "Makefile.capi", "summary"] +
                           (["SAN=1"] if sanitize else []), cwd=EMUL_DIR)
     exe = os.path.join(EMUL_DIR, "build_capi_san/emul_summary_capi_san" if sanitize else "build_capi/emul_summary_capi")
     case = str(tmp_path / "summary_case.bin")

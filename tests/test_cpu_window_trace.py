@@ -280,7 +280,7 @@ def test_c_abi_on_emulated_runtime(sanitize, tmp_path):
     summary windows mixed, the state's summaries, idempotence after the end; every refusal by its message, nothing
     launched by a refused call; the kernel names; after rays_hip_finalize the emulated driver holds nothing.  Once plain
     and once as an ASan + UBSan executable with its own main (leak detection on)."""
-    subprocess.check_call(["make", "-s", "-j", str(min(4, os.cpu_count() or 1)), "-f", "Makefile.capi_window"] +
+    subprocess.check_call(["make", "-s", "-j", str(min(4, os.cpu_count() or 1)), "-f", "Makefile.capi", "window"] +
                           (["SAN=1"] if sanitize else []), cwd=EMUL_DIR)
     exe = os.path.join(EMUL_DIR, "build_capi_san/emul_window_capi_san" if sanitize else "build_capi/emul_window_capi")
     case = str(tmp_path / "window_case.bin")

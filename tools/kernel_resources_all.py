@@ -10,12 +10,13 @@ CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
 BASE = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wall", "-Wno-unused-function",
         "-DRAYS_INST_FAST", "-Rpass-analysis=kernel-resource-usage", "-c", "rays_inst.hip", "-o", "/dev/null"]
 EXACT = ["-ffp-contract=off"]
-TOL = ["-ffp-contract=fast-honor-pragmas", "-fassociative-math", "-fno-signed-zeros", "-fno-trapping-math", "-DRAYS_TOL_FLAVOUR", "-DRAYS_INST_TOL=1"]
+TOL = ["-ffp-contract=fast-honor-pragmas", "-fassociative-math", "-fno-signed-zeros", "-fno-trapping-math", "-DRAYS_TOL_FLAVOUR"]
 
 
 def group(solver, eq, deriv, ue, tol=False):
-    defs = [f"-DRAYS_INST_SOLVER={solver}", f"-DRAYS_INST_EQ={eq}", f"-DRAYS_INST_DERIV={deriv}", f"-DRAYS_INST_UE={ue}",
-            "-DRAYS_INST_MS=0", f"-DRAYS_INST_EQT={eq + 4 * ue + (16 if tol else 0)}"]
+    # the object's -D set, from the one list of the variants (rays_amd/csrc/inst_rules.mk)
+    defs = subprocess.check_output(["make", "-s", "-f", "inst_rules.mk", "print-defs", "VARIANT=" + ("tol" if tol else "inst"),
+                                    f"GROUP={solver}_{eq}_{deriv}_{ue}_0"], cwd=CSRC, text=True).split()
     out = subprocess.run(BASE + (TOL if tol else EXACT) + defs, cwd=CSRC, capture_output=True, text=True).stderr
     rows, cur = [], None
     for line in out.splitlines():

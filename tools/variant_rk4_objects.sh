@@ -9,11 +9,13 @@ NAME=$1; SRC=$2; shift 2
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=/tmp/var_$NAME; mkdir -p $OUT
 BASE="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-function -DRAYS_INST_FAST $*"
-TOL="-ffp-contract=fast -fassociative-math -fno-signed-zeros -fno-trapping-math -DRAYS_TOL_FLAVOUR -DRAYS_INST_TOL=1"
+TOL="-ffp-contract=fast -fassociative-math -fno-signed-zeros -fno-trapping-math -DRAYS_TOL_FLAVOUR"
+# the objects' -D sets: the one list of the variants (inst_rules.mk)
+defs() { make -s -f $ROOT/rays_amd/csrc/inst_rules.mk print-defs VARIANT=$1 GROUP=$2; }
 cd $SRC
 for e in 0 1 2; do
-  /opt/rocm/bin/hipcc $BASE -ffp-contract=off -DRAYS_INST_SOLVER=0 -DRAYS_INST_EQ=$e -DRAYS_INST_DERIV=0 -DRAYS_INST_UE=1 -DRAYS_INST_MS=0 -DRAYS_INST_EQT=$((e + 4)) -c rays_inst.hip -o $OUT/inst_0_${e}_0_1_0.o &
-  /opt/rocm/bin/hipcc $BASE $TOL -DRAYS_INST_SOLVER=0 -DRAYS_INST_EQ=$e -DRAYS_INST_DERIV=0 -DRAYS_INST_UE=1 -DRAYS_INST_MS=0 -DRAYS_INST_EQT=$((e + 20)) -c rays_inst.hip -o $OUT/tol_${e}_1.o &
+  /opt/rocm/bin/hipcc $BASE -ffp-contract=off $(defs inst 0_${e}_0_1_0) -c rays_inst.hip -o $OUT/inst_0_${e}_0_1_0.o &
+  /opt/rocm/bin/hipcc $BASE $TOL $(defs tol ${e}_1) -c rays_inst.hip -o $OUT/tol_${e}_1.o &
 done
 wait
 OBJS=""
