@@ -4,11 +4,12 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
-from rays_amd.params import AxisymTables, RaysFan, RaysParams, axisym_tables_struct
+from rays_amd.params import RaysFan, RaysParams
+from tests import emul_build as eb
+from tests.emul_build import d as _d, i as _i
 
 _ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _DIR = os.path.join(_ROOT, "tests", "hip_emul")
@@ -23,51 +24,22 @@ _tiers_lib = None
 
 
 def build(sanitize: bool = False, out: str = None, defs=()):
-    global _LIB
-    _LIB_SAVE = _LIB
-    if out is not None:
-        _LIB = out
-    try:
-        _build(sanitize, list(defs))
-    finally:
-        _LIB = _LIB_SAVE
-
-
-def _build(sanitize, defs):
-    srcs = [os.path.join(_DIR, "emul_trace.cpp"), os.path.join(_DIR, "hip", "hip_runtime.h")]
-    srcs += [os.path.join(_ROOT, "rays_amd", "csrc", f) for f in
-             ("rays_libm.hpp", "rays_libm_tables.inc", "rays_device.hpp", "rays_device_arith.inc", "rays_trace.hpp", "rays_rk4.hpp", "rays_rk4_body.inc", "rays_rk4_pass.inc", "rays_sg.hpp", "rays_dev_params.inc",
-              "rays_ray_init.hpp", "rays_fan_setup.inc", "rays_deposition.hpp")]
-    if os.path.exists(_LIB) and all(os.path.getmtime(_LIB) >= os.path.getmtime(s) for s in srcs):
-        return
-    cmd = ["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fno-extern-tls-init", "-fPIC", "-shared",
-           "-w", *defs, "-I", _DIR, srcs[0], "-o", _LIB]
-    if sanitize:
-        cmd[1:1] = ["-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-g"]
-    subprocess.check_call(cmd)
-
-
-def _set_zfun(fn):
-    """Z-function spline table for damp_fund_ECH: the data file cut from the reference's
-    initialize_spline_coeffs (rays_amd/data/zfun_spline_re.npz)."""
-    z = np.load(os.path.join(_ROOT, "rays_amd", "data", "zfun_spline_re.npz"))
-    f = np.ascontiguousarray(z["fspl_re"], dtype=np.float64)
-    fn(f.ctypes.data_as(C.POINTER(C.c_double)), len(f), float(z["x_min"]), float(z["x_max"]))
+    eb.build("emul_trace.cpp", _LIB if out is None else out, defs, sanitize)
 
 
 def _load(path):
-    if True:
-        _lib = C.CDLL(path)
-        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
-        _lib.rays_emul_trace.restype = C.c_int
-        _lib.rays_emul_trace.argtypes = [C.POINTER(RaysParams), C.c_int, dp, dp, dp, dp, ip, ip, dp, dp, dp]
-        _lib.rays_emul_trace_ex.restype = C.c_int
-        _lib.rays_emul_trace_ex.argtypes = [C.POINTER(RaysParams), C.c_int, dp, dp, dp, dp, ip, ip, dp, dp, dp,
-                                            dp, dp, dp, C.c_int]
-        _lib.rays_emul_set_zfun_table.restype = C.c_int
-        _lib.rays_emul_set_zfun_table.argtypes = [dp, C.c_int, C.c_double, C.c_double]
-        _set_zfun(_lib.rays_emul_set_zfun_table)
-    return _lib
+    lib = eb.load(path)
+    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    lib.rays_emul_trace.restype = C.c_int
+    lib.rays_emul_trace.argtypes = [C.POINTER(RaysParams), C.c_int, dp, dp, dp, dp, ip, ip, dp, dp, dp]
+    lib.rays_emul_trace_ex.restype = C.c_int
+    lib.rays_emul_trace_ex.argtypes = [C.POINTER(RaysParams), C.c_int, dp, dp, dp, dp, ip, ip, dp, dp, dp,
+                                       dp, dp, dp, C.c_int]
+    lib.rays_emul_ray_init.restype = C.c_int
+    lib.rays_emul_ray_init.argtypes = [C.POINTER(RaysParams), C.POINTER(RaysFan), C.c_int, dp, dp, ip]
+    lib.rays_emul_deposition.restype = C.c_int
+    lib.rays_emul_deposition.argtypes = [C.POINTER(RaysParams), C.c_int, C.c_int, C.c_int, dp, ip, dp, dp, dp, C.c_int, dp, dp]
+    return lib
 
 
 def lib():
@@ -87,12 +59,7 @@ def tiers_lib():
 
 
 def set_axisym_tables(tab: dict, small_tiers: bool = False):
-    t, keep = axisym_tables_struct(tab)
-    fn = (tiers_lib() if small_tiers else lib()).rays_emul_set_axisym_tables
-    fn.restype = C.c_int
-    fn.argtypes = [C.POINTER(AxisymTables), C.c_int, C.c_double, C.c_double]
-    lin = "lin_psi" in tab   # 'eqdsk_magnetics_lin_interp'
-    fn(C.byref(t), int(lin), float(tab["lin_dR"]) if lin else 0.0, float(tab["lin_dZ"]) if lin else 0.0)
+    eb.set_axisym_tables(tiers_lib() if small_tiers else lib(), tab)
 
 
 def _offset_zeros(shape, offset):
@@ -109,34 +76,18 @@ def trace(p: RaysParams, rvec0, rindex_vec0, small_tiers: bool = False, vec_offs
     rvec0 = np.ascontiguousarray(rvec0, dtype=np.float64)
     rindex_vec0 = np.ascontiguousarray(rindex_vec0, dtype=np.float64)
     nray, nv, npt = len(rvec0), p.nv, p.nstep_max + 1
-    out = dict(
-        ray_vec=_offset_zeros((nray, npt, nv), vec_offset), residual=_offset_zeros((nray, npt), res_offset),
-        npoints=np.zeros(nray, dtype=np.int32), stop_code=np.zeros(nray, dtype=np.int32),
-        end_ray_vec=np.zeros((nray, nv)), end_residuals=np.zeros(nray), max_residuals=np.zeros(nray))
-    d = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
-    i = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
-    rc = (tiers_lib() if small_tiers else lib()).rays_emul_trace(C.byref(p), nray, d(rvec0), d(rindex_vec0), d(out["ray_vec"]),
-                               d(out["residual"]), i(out["npoints"]), i(out["stop_code"]),
-                               d(out["end_ray_vec"]), d(out["end_residuals"]), d(out["max_residuals"]))
+    out = eb.trace_outputs(nray, nv, npt)
+    out["ray_vec"], out["residual"] = _offset_zeros((nray, npt, nv), vec_offset), _offset_zeros((nray, npt), res_offset)
+    rc = (tiers_lib() if small_tiers else lib()).rays_emul_trace(C.byref(p), nray, _d(rvec0), _d(rindex_vec0),
+                                                                 *eb.trace_args(out))
     if rc:
         raise RuntimeError(f"rays_emul_trace rc={rc}")
     return out
 
 
-def _out(nray, nv, npt):
-    return dict(ray_vec=np.zeros((nray, npt, nv)), residual=np.zeros((nray, npt)),
-                npoints=np.zeros(nray, dtype=np.int32), stop_code=np.zeros(nray, dtype=np.int32),
-                end_ray_vec=np.zeros((nray, nv)), end_residuals=np.zeros(nray), max_residuals=np.zeros(nray))
-
-
 def _trace_ex(p, nray, rvec0, rindex_vec0, out, v0=None, s0=None, ds_run=None, rays_per_run=0):
-    dp = C.POINTER(C.c_double)
-    d = lambda a: None if a is None else a.ctypes.data_as(dp)
-    i = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
-    rc = lib().rays_emul_trace_ex(C.byref(p), nray, d(rvec0), d(rindex_vec0), d(out["ray_vec"]), d(out["residual"]),
-                                  i(out["npoints"]), i(out["stop_code"]), d(out["end_ray_vec"]),
-                                  d(out["end_residuals"]), d(out["max_residuals"]), d(v0), d(s0), d(ds_run),
-                                  int(rays_per_run))
+    rc = lib().rays_emul_trace_ex(C.byref(p), nray, _d(rvec0), _d(rindex_vec0), *eb.trace_args(out), _d(v0), _d(s0),
+                                  _d(ds_run), int(rays_per_run))
     if rc:
         raise RuntimeError(f"rays_emul_trace_ex rc={rc}")
 
@@ -148,7 +99,7 @@ def scan(p: RaysParams, rvec0, rindex_vec0, ds_values) -> dict:
     rindex_vec0 = np.ascontiguousarray(rindex_vec0, dtype=np.float64)
     ds = np.ascontiguousarray(ds_values, dtype=np.float64)
     nray, R = len(rvec0), len(ds)
-    out = _out(R * nray, p.nv, p.nstep_max + 1)
+    out = eb.trace_outputs(R * nray, p.nv, p.nstep_max + 1)
     _trace_ex(p, R * nray, rvec0, rindex_vec0, out, ds_run=ds, rays_per_run=nray)
     return {k: v.reshape((R, nray) + v.shape[1:]) for k, v in out.items()}
 
@@ -163,7 +114,7 @@ def ode_step(p: RaysParams, v0, s0=None):
     q.nstep_max = 1
     q.s_max = 1.7976931348623157e308
     n = len(v0)
-    out = _out(n, p.nv, 2)
+    out = eb.trace_outputs(n, p.nv, 2)
     _trace_ex(q, n, v0, v0, out, v0=v0, s0=s0)
     ok = out["npoints"] == 2
     return (np.where(ok[:, None], out["ray_vec"][:, 1], 0.0), np.where(ok, out["residual"][:, 1], 0.0),
@@ -175,11 +126,7 @@ def ray_init(p: RaysParams, fan: RaysFan, nray_max: int):
     n = int(nray_max)
     rvec0, rindex_vec0 = np.zeros((n, 3)), np.zeros((n, 3))
     nray = C.c_int32(0)
-    fn = lib().rays_emul_ray_init
-    fn.restype = C.c_int
-    dp = C.POINTER(C.c_double)
-    fn.argtypes = [C.POINTER(RaysParams), C.POINTER(RaysFan), C.c_int, dp, dp, C.POINTER(C.c_int32)]
-    rc = fn(C.byref(p), C.byref(fan), n, rvec0.ctypes.data_as(dp), rindex_vec0.ctypes.data_as(dp), C.byref(nray))
+    rc = lib().rays_emul_ray_init(C.byref(p), C.byref(fan), n, _d(rvec0), _d(rindex_vec0), C.byref(nray))
     if rc:
         raise RuntimeError(f"rays_emul_ray_init rc={rc}")
     return rvec0[:nray.value].copy(), rindex_vec0[:nray.value].copy()
@@ -195,13 +142,8 @@ def deposition(p: RaysParams, which: int, n_bins: int, ray_vec, npoints, power, 
     rho_grid = np.ascontiguousarray(rho_grid, dtype=np.float64)
     rho_fspl = np.ascontiguousarray(rho_fspl, dtype=np.float64)
     work, profile = np.zeros((nray, n_bins)), np.zeros(n_bins)
-    fn = lib().rays_emul_deposition
-    fn.restype = C.c_int
-    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
-    fn.argtypes = [C.POINTER(RaysParams), C.c_int, C.c_int, C.c_int, dp, ip, dp, dp, dp, C.c_int, dp, dp]
-    d = lambda a: a.ctypes.data_as(dp)
-    rc = fn(C.byref(p), which, n_bins, nray, d(ray_vec), npoints.ctypes.data_as(ip), d(power), d(rho_grid),
-            d(rho_fspl), len(rho_grid), d(work), d(profile))
+    rc = lib().rays_emul_deposition(C.byref(p), which, n_bins, nray, _d(ray_vec), _i(npoints), _d(power), _d(rho_grid),
+                                    _d(rho_fspl), len(rho_grid), _d(work), _d(profile))
     if rc:
         raise RuntimeError(f"rays_emul_deposition rc={rc}")
     return work, profile

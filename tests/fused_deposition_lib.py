@@ -5,14 +5,13 @@ DepTraceArgs block, as in the product's launches)."""
 from __future__ import annotations
 
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
 from rays_amd.params import RaysParams
+from tests import emul_build as eb
 from tests import summary_lib as sl
-from tests.common import ROOT, stop_codes
+from tests.common import stop_codes
 
 # the fixtures with dep_work / dep_profile / dep_q_sum of the reference post-processor (tests/golden/make_golden.py)
 DEP_FIXTURES = ["gold_axisym16_eqdsk_zexit_rk4", "gold_axisym64_eqdsk129_tspline_damp_rk4",
@@ -21,8 +20,6 @@ DEP_FIXTURES = ["gold_axisym16_eqdsk_zexit_rk4", "gold_axisym64_eqdsk129_tspline
                 "gold_axisym64_solmag_damp_rk4", "gold_axisym64_solmag_sg_num", "gold_slab16_damp_multi_grad_rk4",
                 "gold_slab16_damp_rk4"]
 WHICH = {"Ptotal_psi": 0, "Ptotal_rho": 1, "Ptotal_x": 2}
-_DIR = os.path.join(ROOT, "tests", "hip_emul")
-_CSRC = os.path.join(ROOT, "rays_amd", "csrc")
 
 
 def profile_names(g):
@@ -63,23 +60,7 @@ def assert_golden_deposition(work_rows, profile, g, i: int, what: str):
 
 
 # ---- host emulation of the fused kernels -------------------------------------------------------------------------------
-_libs = {}
-_SRCS = ["emul_fused_deposition.cpp", "emul_trace.cpp", "emul_group.cpp", "hip/hip_runtime.h", "hip/hip_wave_emul.h"]
-_PRODUCT = sl._PRODUCT + ["rays_deposition.hpp"]
-
-
-def emul_lib(wave: bool = False, tag: str = "", defs=()):
-    """librays_emul_fused[_wave][_<tag>].so, built on first use (extra -D switches get a library of their own)."""
-    key = (wave, tag)
-    if key in _libs:
-        return _libs[key]
-    path = os.path.join(_DIR, "librays_emul_fused" + ("_wave" if wave else "") + (f"_{tag}" if tag else "") + ".so")
-    srcs = [os.path.join(_DIR, f) for f in _SRCS] + [os.path.join(_CSRC, f) for f in _PRODUCT]
-    if not os.path.exists(path) or any(os.path.getmtime(s) > os.path.getmtime(path) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fno-extern-tls-init",
-                               "-fPIC", "-shared", "-w", "-DRAYS_RK4_NO_HANDOVER",
-                               *(["-DRAYS_EMUL_DEPOSIT_WAVE=1"] if wave else []), *defs, "-I", _DIR, srcs[0], "-o", path])
-    lib = C.CDLL(path)
+def _declare(lib, wave):
     dp, ip, pp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(RaysParams)
     tail = [dp, C.c_int, C.c_int, dp, dp, C.c_int, ip, ip, dp, dp, dp, dp, dp, dp, dp]
     if wave:
@@ -88,23 +69,23 @@ def emul_lib(wave: bool = False, tag: str = "", defs=()):
     else:
         lib.rays_emul_fused_deposition.restype = C.c_int
         lib.rays_emul_fused_deposition.argtypes = [pp, C.c_int, dp, dp] + tail
-    lib.rays_emul_set_zfun_table.restype = C.c_int
-    lib.rays_emul_set_zfun_table.argtypes = [dp, C.c_int, C.c_double, C.c_double]
-    from tests.emul_lib import _set_zfun
-    _set_zfun(lib.rays_emul_set_zfun_table)
-    _libs[key] = lib
-    return lib
+
+
+def emul_lib(wave: bool = False, tag: str = "", defs=()):
+    """librays_emul_fused[_wave][_<tag>].so, built on first use (extra -D switches get a library of their own)."""
+    return eb.variant_lib("emul_fused_deposition.cpp", "fused", ["-DRAYS_RK4_NO_HANDOVER"], "-DRAYS_EMUL_DEPOSIT_WAVE=1",
+                          wave, tag, defs, _declare)
 
 
 def _outputs(n, nv, n_bins):
-    out = sl._outputs(n, nv)   # poisoned: every element has to be written by the kernel
+    out = eb.summary_outputs(n, nv)   # poisoned: every element has to be written by the kernel
     out["work"] = np.full((n_bins, n), np.nan)   # bin-major, as on the device (zeroed by the launch)
     out["profile"] = np.full(n_bins, np.nan)
     return out
 
 
 def _tail(out, power, which, n_bins, rho, profile_in):
-    d, i = sl._d, sl._i
+    d, i = eb.d, eb.i
     grid, fspl = rho if rho is not None else (None, None)
     return [d(power), WHICH[which], int(n_bins), d(grid), d(fspl), 0 if grid is None else len(grid), i(out["npoints"]),
             i(out["stop_code"]), d(out["start_ray_vec"]), d(out["end_ray_vec"]), d(out["end_residuals"]),
@@ -119,7 +100,7 @@ def emul_fused(p: RaysParams, rvec0, rindex_vec0, power, which: str, n_bins: int
     power = np.ascontiguousarray(power, dtype=np.float64)
     pin = None if profile_in is None else np.ascontiguousarray(profile_in, dtype=np.float64)
     out = _outputs(len(rvec0), p.nv, n_bins)
-    rc = (lib or emul_lib()).rays_emul_fused_deposition(C.byref(p), len(rvec0), sl._d(rvec0), sl._d(rindex_vec0),
+    rc = (lib or emul_lib()).rays_emul_fused_deposition(C.byref(p), len(rvec0), eb.d(rvec0), eb.d(rindex_vec0),
                                                         *_tail(out, power, which, n_bins, rho, pin))
     if rc:
         raise RuntimeError(f"rays_emul_fused_deposition rc={rc}")
@@ -135,7 +116,7 @@ def emul_fused_waves(p: RaysParams, rvec0, rindex_vec0, power, which: str, n_bin
     power = np.ascontiguousarray(power, dtype=np.float64)
     out = _outputs(len(rvec0), p.nv, n_bins)
     rc = (lib or emul_lib(wave=True)).rays_emul_fused_deposition_waves(
-        C.byref(p), sl.WAVE_KINDS[kind], int(blocks), int(stride), len(rvec0), sl._d(rvec0), sl._d(rindex_vec0),
+        C.byref(p), sl.WAVE_KINDS[kind], int(blocks), int(stride), len(rvec0), eb.d(rvec0), eb.d(rindex_vec0),
         *_tail(out, power, which, n_bins, rho, None))
     if rc:
         raise RuntimeError(f"rays_emul_fused_deposition_waves rc={rc}")

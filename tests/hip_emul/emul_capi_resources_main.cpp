@@ -9,9 +9,7 @@ RAYS_EMUL_DEFINE_GLOBALS
 
 using namespace rays::host;
 
-static int failures = 0;
-#define CHECK(cond) \
-  do { if (!(cond)) { std::fprintf(stderr, "%s:%d: check failed: %s\n", __FILE__, __LINE__, #cond); failures++; } } while (0)
+#include "emul_capi_check.hpp"
 
 static long long live_device() {
   hip_emul::State& s = hip_emul::state();

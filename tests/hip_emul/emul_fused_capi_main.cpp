@@ -12,13 +12,7 @@
 // the devices equal the single block.  After rays_hip_finalize the emulated driver holds nothing.
 #include <hip/hip_runtime.h>
 
-#include <cstdint>
-#include <cstdio>
-#include <cstring>
-#include <string>
-#include <vector>
-
-#include "../../include/rays_hip.h"
+#include "emul_capi_check.hpp"
 #include "../../rays_amd/csrc/rays_deposition.hpp"
 
 // The two launchers of rays_deposition.hip (not part of the emulated build: its kernels use wave intrinsics), on the host:
@@ -40,22 +34,6 @@ hipError_t launch_profile_sum(int n_bins, int nray, const double* work, const do
 
 extern "C" void rays_emul_runtime_stats(long long* launches, long long* wrong_device, long long* live_allocations);
 extern "C" void rays_emul_runtime_live(long long* pinned, long long* streams, long long* events);
-
-static int failures = 0;
-#define CHECK(cond) \
-  do { if (!(cond)) { std::fprintf(stderr, "%s:%d: check failed: %s\n", __FILE__, __LINE__, #cond); failures++; } } while (0)
-
-template <class T>
-static bool read_n(std::FILE* f, std::vector<T>& v, size_t n) {
-  v.resize(n);
-  return n == 0 || std::fread(v.data(), sizeof(T), n, f) == n;
-}
-static std::string last_error() {
-  char buf[512];
-  rays_hip_last_error(buf, (int)sizeof buf);
-  return buf;
-}
-static bool refused(int rc, const char* text) { return rc != 0 && last_error().find(text) != std::string::npos; }
 
 int main(int argc, char** argv) {
   if (argc != 2) { std::fprintf(stderr, "usage: %s <case file>\n", argv[0]); return 2; }

@@ -18,22 +18,13 @@
 namespace {
 constexpr int FD = rays::kEqNoTraj | rays::kEqDeposit;
 
-int fused_tables(const rays_params_t* p, rays::DevParams& D) {
-  if (p->damping_model) {
-    if (g_zfun.empty()) return 2;
-    D.zf_fspl = g_zfun.data(); D.zf_nx = g_zf_nx; D.zf_xmin = g_zf_xmin; D.zf_xmax = g_zf_xmax;
-  }
-  if (p->equilib_model != RAYS_EQ_AXISYM) return 0;
-  if (p->axisym.magnetics_model == RAYS_AXI_MAG_EQDSK_SPLINE && (g_axi[2].empty() || g_axi_lin)) return 3;
-  if (p->axisym.magnetics_model == RAYS_AXI_MAG_EQDSK_LIN && (g_axi[2].empty() || !g_axi_lin)) return 3;
-  D.a_lin_dR = g_axi_dR; D.a_lin_dZ = g_axi_dZ;
-  D.a_nr = g_axi_n[0]; D.a_nz = g_axi_n[1]; D.a_n_rb = g_axi_n[2]; D.a_n_ne = g_axi_n[3]; D.a_n_te = g_axi_n[4]; D.a_n_ti = g_axi_n[5];
-  D.a_r_grid = g_axi[0].data(); D.a_z_grid = g_axi[1].data(); D.a_psi_fspl = g_axi[2].data();
-  D.a_rb_grid = g_axi[3].data(); D.a_rb_fspl = g_axi[4].data(); D.a_ne_grid = g_axi[5].data(); D.a_ne_fspl = g_axi[6].data();
-  D.a_te_grid = g_axi[7].data(); D.a_te_fspl = g_axi[8].data(); D.a_ti_grid = g_axi[9].data(); D.a_ti_fspl = g_axi[10].data();
-  set_spline_axes(D, D.a_r_grid, D.a_z_grid, D.a_rb_grid, D.a_ne_grid, D.a_te_grid, D.a_ti_grid);
-  return 0;
-}
+// the shapes with a fused build.  One lane: two species with damping (nv = 8 | 13) in the slab and axisym_toroid, and
+// the slab's multi_spec_damping kernel; whole waves: the unit-exponent kernels with nv = 8
+struct FusedShapes {
+  template <int EQ, int DERIV, int NS, int NV>
+  static constexpr bool lane = (EQ & rays::kEqMultiSpec) ? (EQ & 7) == 4 : (EQ & 1) == 0 && NS == 2 && (NV == 8 || NV == 13);
+  template <class S> static constexpr bool wave = (S::EQ & 4) != 0 && S::NV == 8;
+};
 
 // the launch's argument blocks as rays_capi.hip: trace_deposition_launch fills them; work[n_bins][nray] zeroed here
 rays::DepTraceArgs fused_block(const rays_params_t* p, int nray, int which, int n_bins, const double* power,
@@ -49,10 +40,9 @@ rays::DepTraceArgs fused_block(const rays_params_t* p, int nray, int which, int 
 rays::TraceArgs fused_args(int nray, const double* rvec0, const double* rindex_vec0, int32_t* npoints, int32_t* stop_code,
                            double* start_ray_vec, double* end_ray_vec, double* end_residuals, double* max_residuals,
                            unsigned* counter, const rays::DepTraceArgs* T) {
-  rays::TraceArgs A = rays::TraceArgs();  // residual = nullptr
-  A.nray = nray; A.rvec0 = rvec0; A.rindex_vec0 = rindex_vec0;
-  A.npoints = npoints; A.stop_code = stop_code; A.set_start_ray_vec(start_ray_vec); A.end_ray_vec = end_ray_vec;
-  A.end_residuals = end_residuals; A.max_residuals = max_residuals; A.next_ray = counter;
+  rays::TraceArgs A = emul_trace_args(nray, rvec0, rindex_vec0,   // residual = nullptr, ray_vec: the block
+                                      EmulOut{nullptr, nullptr, npoints, stop_code, start_ray_vec, end_ray_vec,
+                                              end_residuals, max_residuals}, counter);
   A.set_dep(T);
   return A;
 }
@@ -84,24 +74,14 @@ extern "C" int rays_emul_fused_deposition(const rays_params_t* p, int nray, cons
   const rays::DepTraceArgs T = fused_block(p, nray, which, n_bins, power, rho_grid, rho_fspl, n_rho, work);
   rays::TraceArgs A = fused_args(nray, rvec0, rindex_vec0, npoints, stop_code, start_ray_vec, end_ray_vec, end_residuals,
                                  max_residuals, &counter, &T);
-  std::vector<double> sg_far(512, 0.0);  // one lane: the SG kernels' upper-tier workspace
-  A.sg_far = sg_far.data(); A.sg_far_lanes = 1;
+  std::vector<double> sg_far;
+  emul_one_lane_far(A, sg_far);
   rays::DevParams D = make_dev_params(*p);
-  if (int rc = fused_tables(p, D)) return rc;
-  const int e = p->equilib_model | (unit_exponents(*p) ? rays::kEqUnitExp : 0), d = p->ray_deriv, s = p->ode_solver;
-  const rays::DevParams& D_ = D;
-  int rc = 4;
-  if (p->multi_spec_damping) {
-    if (e == 4 && d == 0) rc = run_ms<4 | rays::kEqMultiSpec | FD, 0>(s, p->nspec + 1, p->nv, D_, A);
-  } else if (p->nspec + 1 == 2 && (p->nv == 8 || p->nv == 13)) {
-    const int nv = p->nv;
-#define RAYS_EMUL_CASE(E, DV)                                                      \
-  if (e == E && d == DV)                                                           \
-    rc = nv == 8 ? run1<E | FD, DV, 2, 8>(s, D_, A) : run1<E | FD, DV, 2, 13>(s, D_, A);
-    RAYS_EMUL_CASE(0, 0) RAYS_EMUL_CASE(0, 1) RAYS_EMUL_CASE(2, 0) RAYS_EMUL_CASE(2, 1)
-    RAYS_EMUL_CASE(4, 0) RAYS_EMUL_CASE(4, 1) RAYS_EMUL_CASE(6, 0) RAYS_EMUL_CASE(6, 1)
-#undef RAYS_EMUL_CASE
-  }
+  if (int rc = emul_attach_tables(p, D, kTabAll)) return rc;
+  const int rc = emul_lane_dispatch<FusedShapes>(p, [&](auto sh) {
+    typedef decltype(sh) S;
+    return run1<S::EQ | FD, S::DERIV, S::NS, S::NV>(p->ode_solver, D, A);
+  });
   if (rc) return rc;
   fused_profile(n_bins, nray, work, profile_in, profile);
   return 0;
@@ -122,22 +102,17 @@ extern "C" int rays_emul_fused_deposition_waves(const rays_params_t* p, int kind
   rays::TraceArgs A = fused_args(nray, rvec0, rindex_vec0, npoints, stop_code, start_ray_vec, end_ray_vec, end_residuals,
                                  max_residuals, &counter, &T);
   std::vector<unsigned> sched;
-  if (kind == 0 && stride > 1) {
-    sched.assign(4 + (size_t)rays::sched_pilots((unsigned)nray, stride), 0u);
-    A.sched = sched.data();
-    A.sched_stride = stride;
-  }
+  if (kind == 0) emul_sched(A, sched, stride);
   rays::DevParams D = make_dev_params(*p);
-  if (int rc = fused_tables(p, D)) return rc;
-  const int e = p->equilib_model | (unit_exponents(*p) ? rays::kEqUnitExp : 0), ns = p->nspec + 1, nv = p->nv;
-  int rc = 4;
-  if (kind == 0) {
-    g_rk4_w2_body = 0;
-    if (e == 6 && ns == 2 && nv == 8) rc = run_rk4_waves<6 | FD, 2, 8>(D, A, blocks);
-    else if (e == 4 && ns == 2 && nv == 8) rc = run_rk4_waves<4 | FD, 2, 8>(D, A, blocks);
-  } else {
-    if (e == 6 && ns == 2 && nv == 8) rc = run_sg_waves<6 | FD, 2, 8>(D, A, blocks);
-  }
+  if (int rc = emul_attach_tables(p, D, kTabAll)) return rc;
+  g_rk4_w2_body = 0;
+  const int rc = kind == 0 ? emul_wave_dispatch<FusedShapes>(Rk4WaveShapes{}, p, [&](auto sh) {
+    typedef decltype(sh) S;
+    return run_rk4_waves<S::EQ | FD, S::NS, S::NV>(D, A, blocks);
+  }) : emul_wave_dispatch<FusedShapes>(SgWaveShapes{}, p, [&](auto sh) {
+    typedef decltype(sh) S;
+    return run_sg_waves<S::EQ | FD, S::NS, S::NV>(D, A, blocks);
+  });
   if (rc) return rc;
   fused_profile(n_bins, nray, work, profile_in, profile);
   return 0;

@@ -16,35 +16,19 @@
 #endif
 
 namespace {
-struct SummaryOut {
-  int32_t *npoints, *stop_code;
-  double *start_ray_vec, *end_ray_vec, *end_residuals, *max_residuals;
-};
-rays::TraceArgs summary_args(int nray, const double* rvec0, const double* rindex_vec0, const SummaryOut& o,
-                             unsigned* counter) {
-  rays::TraceArgs A = rays::TraceArgs();  // ray_vec = residual = nullptr
-  A.nray = nray; A.rvec0 = rvec0; A.rindex_vec0 = rindex_vec0;
-  A.npoints = o.npoints; A.stop_code = o.stop_code; A.set_start_ray_vec(o.start_ray_vec); A.end_ray_vec = o.end_ray_vec;
-  A.end_residuals = o.end_residuals; A.max_residuals = o.max_residuals; A.next_ray = counter;
-  return A;
-}
-int summary_tables(const rays_params_t* p, rays::DevParams& D) {
-  if (p->damping_model) {
-    if (g_zfun.empty()) return 2;
-    D.zf_fspl = g_zfun.data(); D.zf_nx = g_zf_nx; D.zf_xmin = g_zf_xmin; D.zf_xmax = g_zf_xmax;
-  }
-  if (p->equilib_model != RAYS_EQ_AXISYM) return 0;
-  if (p->axisym.magnetics_model == RAYS_AXI_MAG_EQDSK_SPLINE && (g_axi[2].empty() || g_axi_lin)) return 3;
-  if (p->axisym.magnetics_model == RAYS_AXI_MAG_EQDSK_LIN && (g_axi[2].empty() || !g_axi_lin)) return 3;
-  D.a_lin_dR = g_axi_dR; D.a_lin_dZ = g_axi_dZ;
-  D.a_nr = g_axi_n[0]; D.a_nz = g_axi_n[1]; D.a_n_rb = g_axi_n[2]; D.a_n_ne = g_axi_n[3]; D.a_n_te = g_axi_n[4]; D.a_n_ti = g_axi_n[5];
-  D.a_r_grid = g_axi[0].data(); D.a_z_grid = g_axi[1].data(); D.a_psi_fspl = g_axi[2].data();
-  D.a_rb_grid = g_axi[3].data(); D.a_rb_fspl = g_axi[4].data(); D.a_ne_grid = g_axi[5].data(); D.a_ne_fspl = g_axi[6].data();
-  D.a_te_grid = g_axi[7].data(); D.a_te_fspl = g_axi[8].data(); D.a_ti_grid = g_axi[9].data(); D.a_ti_fspl = g_axi[10].data();
-  set_spline_axes(D, D.a_r_grid, D.a_z_grid, D.a_rb_grid, D.a_ne_grid, D.a_te_grid, D.a_ti_grid);
-  return 0;
-}
 constexpr int NT = rays::kEqNoTraj;
+// ray_vec = residual = nullptr
+rays::TraceArgs summary_args(int nray, const double* rvec0, const double* rindex_vec0, int32_t* npoints, int32_t* stop_code,
+                             double* start_ray_vec, double* end_ray_vec, double* end_residuals, double* max_residuals,
+                             unsigned* counter) {
+  return emul_trace_args(nray, rvec0, rindex_vec0,
+                         EmulOut{nullptr, nullptr, npoints, stop_code, start_ray_vec, end_ray_vec, end_residuals,
+                                 max_residuals}, counter);
+}
+// the lane-group kernels with a summary-only build
+struct SummaryGroups {
+  template <class S> static constexpr bool wave = (S::EQ == 4 && S::NS == 3) || (S::EQ == 5 && S::NS == 2);
+};
 }  // namespace
 
 #ifndef RAYS_EMUL_SUMMARY_WAVE
@@ -55,26 +39,17 @@ extern "C" int rays_emul_summary_trace(const rays_params_t* p, int nray, const d
                                        double* end_residuals, double* max_residuals, const double* ds_run,
                                        int rays_per_run) {
   unsigned counter = 0;
-  rays::TraceArgs A = summary_args(nray, rvec0, rindex_vec0,
-                                   SummaryOut{npoints, stop_code, start_ray_vec, end_ray_vec, end_residuals, max_residuals},
-                                   &counter);
+  rays::TraceArgs A = summary_args(nray, rvec0, rindex_vec0, npoints, stop_code, start_ray_vec, end_ray_vec, end_residuals,
+                                   max_residuals, &counter);
   A.ds_run = ds_run; A.rays_per_run = rays_per_run;
-  std::vector<double> sg_far(512, 0.0);  // one lane: the SG kernels' upper-tier workspace
-  A.sg_far = sg_far.data(); A.sg_far_lanes = 1;
+  std::vector<double> sg_far;
+  emul_one_lane_far(A, sg_far);
   rays::DevParams D = make_dev_params(*p);
-  if (int rc = summary_tables(p, D)) return rc;
-  const int e = p->equilib_model | (unit_exponents(*p) ? rays::kEqUnitExp : 0), d = p->ray_deriv, s = p->ode_solver;
-  const rays::DevParams& D_ = D;
-  if (p->multi_spec_damping) {
-    if (e == 5 && d == 0) return run_ms<5 | rays::kEqMultiSpec | NT, 0>(s, p->nspec + 1, p->nv, D_, A);
-    if (e == 4 && d == 0) return run_ms<4 | rays::kEqMultiSpec | NT, 0>(s, p->nspec + 1, p->nv, D_, A);
-    return 4;
-  }
-#define RAYS_EMUL_CASE(E, D) if (e == E && d == D) return run<E | NT, D>(s, p->nspec + 1, p->nv, D_, A); else
-  RAYS_EMUL_CASE(0, 0) RAYS_EMUL_CASE(0, 1) RAYS_EMUL_CASE(1, 0) RAYS_EMUL_CASE(1, 1) RAYS_EMUL_CASE(2, 0) RAYS_EMUL_CASE(2, 1)
-  RAYS_EMUL_CASE(4, 0) RAYS_EMUL_CASE(4, 1) RAYS_EMUL_CASE(5, 0) RAYS_EMUL_CASE(5, 1) RAYS_EMUL_CASE(6, 0) RAYS_EMUL_CASE(6, 1)
-  return 4;
-#undef RAYS_EMUL_CASE
+  if (int rc = emul_attach_tables(p, D, kTabAll)) return rc;
+  return emul_lane_dispatch<AllShapes>(p, [&](auto sh) {
+    typedef decltype(sh) S;
+    return run1<S::EQ | NT, S::DERIV, S::NS, S::NV>(p->ode_solver, D, A);
+  });
 }
 #else
 // Whole emulated waves.  kind 0: rk4_trace_kernel, 1: rk4_trace_kernel_w2's body, 2: sg_trace_kernel (`blocks` waves of
@@ -88,32 +63,27 @@ extern "C" int rays_emul_summary_waves(const rays_params_t* p, int kind, int blo
   if (p->ode_solver != (kind <= 1 ? RAYS_ODE_RK4 : RAYS_ODE_SG)) return 1;
   if (p->ray_deriv != (kind == 3 ? RAYS_DERIV_NUM : RAYS_DERIV_COLD)) return 1;
   unsigned counter = 0;
-  rays::TraceArgs A = summary_args(nray, rvec0, rindex_vec0,
-                                   SummaryOut{npoints, stop_code, start_ray_vec, end_ray_vec, end_residuals, max_residuals},
-                                   &counter);
+  rays::TraceArgs A = summary_args(nray, rvec0, rindex_vec0, npoints, stop_code, start_ray_vec, end_ray_vec, end_residuals,
+                                   max_residuals, &counter);
   std::vector<unsigned> sched;
-  if (kind == 0 && stride_or_G > 1) {
-    sched.assign(4 + (size_t)rays::sched_pilots((unsigned)nray, stride_or_G), 0u);
-    A.sched = sched.data();
-    A.sched_stride = stride_or_G;
-  }
+  if (kind == 0) emul_sched(A, sched, stride_or_G);
   rays::DevParams D = make_dev_params(*p);
-  if (int rc = summary_tables(p, D)) return rc;
-  const int e = p->equilib_model | (unit_exponents(*p) ? rays::kEqUnitExp : 0), ns = p->nspec + 1, nv = p->nv;
+  if (int rc = emul_attach_tables(p, D, kTabAll)) return rc;
   if (kind <= 1) {
     g_rk4_w2_body = kind;
-#define RAYS_RK4W_CASE(E, N, V) if (e == E && ns == N && nv == V) return run_rk4_waves<E | NT, N, V>(D, A, blocks);
-    RAYS_RK4W_CASE(4, 2, 7) RAYS_RK4W_CASE(5, 2, 7) RAYS_RK4W_CASE(6, 2, 8)
-#undef RAYS_RK4W_CASE
-  } else if (kind == 2) {
-#define RAYS_SGW_CASE(E, N, V) if (e == E && ns == N && nv == V) return run_sg_waves<E | NT, N, V>(D, A, blocks);
-    RAYS_SGW_CASE(5, 2, 7) RAYS_SGW_CASE(6, 2, 8)
-#undef RAYS_SGW_CASE
-  } else if (nv == 7) {
-#define RAYS_GRP_CASE(E, N) if (e == E && ns == N) return run_group_g<E | NT, N>(stride_or_G, D, A, blocks);
-    RAYS_GRP_CASE(4, 3) RAYS_GRP_CASE(5, 2)
-#undef RAYS_GRP_CASE
+    return emul_wave_dispatch<UnitExpWaves>(Rk4WaveShapes{}, p, [&](auto sh) {
+      typedef decltype(sh) S;
+      return run_rk4_waves<S::EQ | NT, S::NS, S::NV>(D, A, blocks);
+    });
   }
-  return 4;
+  if (kind == 2)
+    return emul_wave_dispatch<UnitExpWaves>(SgWaveShapes{}, p, [&](auto sh) {
+      typedef decltype(sh) S;
+      return run_sg_waves<S::EQ | NT, S::NS, S::NV>(D, A, blocks);
+    });
+  return emul_wave_dispatch<SummaryGroups>(GroupShapes{}, p, [&](auto sh) {
+    typedef decltype(sh) S;
+    return run_group_g<S::EQ | NT, S::NS>(stride_or_G, D, A, blocks);
+  });
 }
 #endif

@@ -14,25 +14,8 @@
 #else
 #include "emul_trace.cpp"
 #endif
-#include <type_traits>
 
 namespace {
-int window_tables(const rays_params_t* p, rays::DevParams& D) {
-  if (p->damping_model) {
-    if (g_zfun.empty()) return 2;
-    D.zf_fspl = g_zfun.data(); D.zf_nx = g_zf_nx; D.zf_xmin = g_zf_xmin; D.zf_xmax = g_zf_xmax;
-  }
-  if (p->equilib_model != RAYS_EQ_AXISYM) return 0;
-  if (p->axisym.magnetics_model == RAYS_AXI_MAG_EQDSK_SPLINE && (g_axi[2].empty() || g_axi_lin)) return 3;
-  if (p->axisym.magnetics_model == RAYS_AXI_MAG_EQDSK_LIN && (g_axi[2].empty() || !g_axi_lin)) return 3;
-  D.a_lin_dR = g_axi_dR; D.a_lin_dZ = g_axi_dZ;
-  D.a_nr = g_axi_n[0]; D.a_nz = g_axi_n[1]; D.a_n_rb = g_axi_n[2]; D.a_n_ne = g_axi_n[3]; D.a_n_te = g_axi_n[4]; D.a_n_ti = g_axi_n[5];
-  D.a_r_grid = g_axi[0].data(); D.a_z_grid = g_axi[1].data(); D.a_psi_fspl = g_axi[2].data();
-  D.a_rb_grid = g_axi[3].data(); D.a_rb_fspl = g_axi[4].data(); D.a_ne_grid = g_axi[5].data(); D.a_ne_fspl = g_axi[6].data();
-  D.a_te_grid = g_axi[7].data(); D.a_te_fspl = g_axi[8].data(); D.a_ti_grid = g_axi[9].data(); D.a_ti_fspl = g_axi[10].data();
-  set_spline_axes(D, D.a_r_grid, D.a_z_grid, D.a_rb_grid, D.a_ne_grid, D.a_te_grid, D.a_ti_grid);
-  return 0;
-}
 constexpr int CT = rays::kEqContinue, NT = rays::kEqNoTraj;
 
 // the saved ray state as the caller's seven arrays (include/rays_hip.h: rays_ray_state_t)
@@ -47,12 +30,10 @@ struct StateArrays {
 rays::TraceArgs window_args(int mode, int nray, const double* rvec0, const double* rindex_vec0, const StateArrays& s,
                             int n_steps, double* ray_vec_win, double* residual_win, int32_t* npoints_win,
                             double* start_ray_vec, unsigned* counter) {
-  rays::TraceArgs A = rays::TraceArgs();
-  A.nray = nray; A.rvec0 = rvec0; A.rindex_vec0 = rindex_vec0; A.next_ray = counter;
-  A.ray_vec = mode == 1 ? ray_vec_win : nullptr;
-  A.residual = mode == 1 ? residual_win : nullptr;
-  A.npoints = npoints_win;
-  A.set_start_ray_vec(start_ray_vec);
+  // a recording window alone has the two window arrays; no per-ray summary is written (the state carries them)
+  rays::TraceArgs A = emul_trace_args(nray, rvec0, rindex_vec0,
+                                      EmulOut{mode == 1 ? ray_vec_win : nullptr, mode == 1 ? residual_win : nullptr,
+                                              npoints_win, nullptr, start_ray_vec, nullptr, nullptr, nullptr}, counter);
   A.set_state(rays::TraceArgs::State{s.v, s.s, s.nstep, s.stop_code, s.resid, s.sg_err, s.flags}, n_steps);
   return A;
 }
@@ -74,21 +55,6 @@ int window1(int mode, int solver, const rays::DevParams& D, const rays::TraceArg
   }
   return 0;
 }
-// the shapes emul_trace.cpp instantiates (run<> / run_ms<> there)
-template <int EQ, int DERIV>
-int window_shape(int mode, int solver, int ns, int nv, const rays::DevParams& D, const rays::TraceArgs& A) {
-#define RAYS_W1(N, V) if (ns == N && nv == V) return window1<EQ, DERIV, N, V>(mode, solver, D, A);
-  if constexpr ((EQ & rays::kEqMultiSpec) != 0) {
-    if constexpr ((EQ & 3) == 1) { RAYS_W1(2, 10) }
-    if constexpr ((EQ & 3) == 0) { RAYS_W1(2, 15) }
-  } else {
-    RAYS_W1(2, 7) RAYS_W1(2, 8) RAYS_W1(2, 12) RAYS_W1(2, 13)
-    if constexpr ((EQ & 3) == 0) { RAYS_W1(1, 7) RAYS_W1(3, 7) RAYS_W1(6, 7) }
-    if constexpr ((EQ & 3) == 1) { RAYS_W1(4, 7) }
-  }
-#undef RAYS_W1
-  return 1;
-}
 }  // namespace
 
 extern "C" int rays_emul_window(const rays_params_t* p, int mode, int nray, const double* rvec0,
@@ -100,35 +66,16 @@ extern "C" int rays_emul_window(const rays_params_t* p, int mode, int nray, cons
   rays::TraceArgs A = window_args(mode, nray, rvec0, rindex_vec0,
                                   StateArrays{st_v, st_s, st_nstep, st_stop_code, st_resid, st_sg_err, st_flags}, n_steps,
                                   ray_vec_win, residual_win, npoints_win, start_ray_vec, &counter);
-  std::vector<double> sg_far(512, 0.0);  // one lane: the SG kernels' upper-tier workspace
-  A.sg_far = sg_far.data(); A.sg_far_lanes = 1;
+  std::vector<double> sg_far;
+  emul_one_lane_far(A, sg_far);
   rays::DevParams D = make_dev_params(*p);
-  if (int rc = window_tables(p, D)) return rc;
-  const int e = p->equilib_model | (unit_exponents(*p) ? rays::kEqUnitExp : 0), d = p->ray_deriv, s = p->ode_solver;
-  const int ns = p->nspec + 1, nv = p->nv;
-  if (p->multi_spec_damping) {
-    if (e == 5 && d == 0) return window_shape<5 | rays::kEqMultiSpec, 0>(mode, s, ns, nv, D, A);
-    if (e == 4 && d == 0) return window_shape<4 | rays::kEqMultiSpec, 0>(mode, s, ns, nv, D, A);
-    return 4;
-  }
-#define RAYS_EMUL_CASE(E, DV) if (e == E && d == DV) return window_shape<E, DV>(mode, s, ns, nv, D, A); else
-  RAYS_EMUL_CASE(0, 0) RAYS_EMUL_CASE(0, 1) RAYS_EMUL_CASE(1, 0) RAYS_EMUL_CASE(1, 1) RAYS_EMUL_CASE(2, 0) RAYS_EMUL_CASE(2, 1)
-  RAYS_EMUL_CASE(4, 0) RAYS_EMUL_CASE(4, 1) RAYS_EMUL_CASE(5, 0) RAYS_EMUL_CASE(5, 1) RAYS_EMUL_CASE(6, 0) RAYS_EMUL_CASE(6, 1)
-  return 4;
-#undef RAYS_EMUL_CASE
+  if (int rc = emul_attach_tables(p, D, kTabAll)) return rc;
+  return emul_lane_dispatch<AllShapes>(p, [&](auto sh) {
+    typedef decltype(sh) S;
+    return window1<S::EQ, S::DERIV, S::NS, S::NV>(mode, p->ode_solver, D, A);
+  });
 }
 #else
-// emul_group.cpp's run_rk4_waves without its second arm: the two-waves-per-SIMD body has no continuation variant
-template <int EQ, int NS, int NV>
-static int run_rk4_window_waves(const rays::DevParams& D, const rays::TraceArgs& A, int nwaves) {
-  gridDim.x = (unsigned)nwaves;
-  blockDim.x = 64;
-  for (int b = 0; b < nwaves; b++) {
-    blockIdx.x = (unsigned)b;
-    wave_emul::run_wave(0u, [&] { rays::rk4_trace_kernel<EQ, NS, 0, NV>(D, A); }, threadIdx);
-  }
-  return 0;
-}
 // Whole emulated waves, window launches only (modes 1 and 2).  kind 0: rk4_trace_kernel, 2: sg_trace_kernel, `blocks`
 // waves of 64 lanes each; stride: the "long rays first" neighbourhood size of the RK4 kernel (0 | 1: index order).
 extern "C" int rays_emul_window_waves(const rays_params_t* p, int mode, int kind, int blocks, int stride, int nray,
@@ -142,24 +89,20 @@ extern "C" int rays_emul_window_waves(const rays_params_t* p, int mode, int kind
                                   StateArrays{st_v, st_s, st_nstep, st_stop_code, st_resid, st_sg_err, st_flags}, n_steps,
                                   ray_vec_win, residual_win, npoints_win, nullptr, &counter);
   std::vector<unsigned> sched;
-  if (kind == 0 && stride > 1) {
-    sched.assign(4 + (size_t)rays::sched_pilots((unsigned)nray, stride), 0u);
-    A.sched = sched.data();
-    A.sched_stride = stride;
-  }
+  if (kind == 0) emul_sched(A, sched, stride);
   rays::DevParams D = make_dev_params(*p);
-  if (int rc = window_tables(p, D)) return rc;
-  const int e = p->equilib_model | (unit_exponents(*p) ? rays::kEqUnitExp : 0), ns = p->nspec + 1, nv = p->nv;
-#define RAYS_WW_CASE(RUN, E, N, V)                                              \
-  if (e == E && ns == N && nv == V)                                             \
-    return mode == 1 ? RUN<E | CT, N, V>(D, A, blocks) : RUN<E | CT | NT, N, V>(D, A, blocks);
-  if (kind == 0) {
-    RAYS_WW_CASE(run_rk4_window_waves, 4, 2, 7) RAYS_WW_CASE(run_rk4_window_waves, 5, 2, 7)
-    RAYS_WW_CASE(run_rk4_window_waves, 6, 2, 8)
-  } else {
-    RAYS_WW_CASE(run_sg_waves, 5, 2, 7) RAYS_WW_CASE(run_sg_waves, 6, 2, 8)
-  }
-#undef RAYS_WW_CASE
-  return 4;
+  if (int rc = emul_attach_tables(p, D, kTabAll)) return rc;
+  // (run_rk4_waves leaves the two-waves-per-SIMD body and the hand-over out of a continuation build)
+  if (kind == 0)
+    return emul_wave_dispatch<UnitExpWaves>(Rk4WaveShapes{}, p, [&](auto sh) {
+      typedef decltype(sh) S;
+      return mode == 1 ? run_rk4_waves<S::EQ | CT, S::NS, S::NV>(D, A, blocks)
+                       : run_rk4_waves<S::EQ | CT | NT, S::NS, S::NV>(D, A, blocks);
+    });
+  return emul_wave_dispatch<UnitExpWaves>(SgWaveShapes{}, p, [&](auto sh) {
+    typedef decltype(sh) S;
+    return mode == 1 ? run_sg_waves<S::EQ | CT, S::NS, S::NV>(D, A, blocks)
+                     : run_sg_waves<S::EQ | CT | NT, S::NS, S::NV>(D, A, blocks);
+  });
 }
 #endif

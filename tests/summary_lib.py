@@ -4,17 +4,15 @@ fixture or from a full trace, and the ctypes wrappers around the host emulation 
 from __future__ import annotations
 
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-from rays_amd.params import AxisymTables, RaysParams, axisym_tables_struct
-from tests.common import ROOT, stop_codes
+from rays_amd.params import RaysParams
+from tests import emul_build as eb
+from tests.common import stop_codes
+from tests.emul_build import d as _d, i as _i, summary_outputs as _outputs
 
 KEYS = ("npoints", "stop_code", "start_ray_vec", "end_ray_vec", "end_residuals", "max_residuals")
-_DIR = os.path.join(ROOT, "tests", "hip_emul")
-_CSRC = os.path.join(ROOT, "rays_amd", "csrc")
 _NO_STEP = -1.7976931348623157e308   # maxval of an empty array: a ray that started and recorded no step
 
 
@@ -49,25 +47,7 @@ def assert_same(out: dict, ref: dict, what: str = ""):
 
 
 # ---- host emulation of the summary-only kernels ----------------------------------------------------------------------
-_libs = {}
-_SRCS = ["emul_summary.cpp", "emul_trace.cpp", "emul_group.cpp", "hip/hip_runtime.h", "hip/hip_wave_emul.h"]
-_PRODUCT = ["rays_libm.hpp", "rays_libm_tables.inc", "rays_device.hpp", "rays_device_arith.inc", "rays_trace.hpp",
-            "rays_rk4.hpp", "rays_rk4_body.inc", "rays_rk4_pass.inc", "rays_sg.hpp", "rays_sg_group.hpp",
-            "rays_dev_params.inc"]
-
-
-def emul_lib(wave: bool = False, tag: str = "", defs=()):
-    """librays_emul_summary[_wave][_<tag>].so, built on first use (extra -D switches get a library of their own)."""
-    key = (wave, tag)
-    if key in _libs:
-        return _libs[key]
-    path = os.path.join(_DIR, "librays_emul_summary" + ("_wave" if wave else "") + (f"_{tag}" if tag else "") + ".so")
-    srcs = [os.path.join(_DIR, f) for f in _SRCS] + [os.path.join(_CSRC, f) for f in _PRODUCT]
-    if not os.path.exists(path) or any(os.path.getmtime(s) > os.path.getmtime(path) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fno-extern-tls-init",
-                               "-fPIC", "-shared", "-w", "-DRAYS_RK4_NO_HANDOVER",
-                               *(["-DRAYS_EMUL_SUMMARY_WAVE=1"] if wave else []), *defs, "-I", _DIR, srcs[0], "-o", path])
-    lib = C.CDLL(path)
+def _declare(lib, wave):
     dp, ip, pp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(RaysParams)
     if wave:
         lib.rays_emul_summary_waves.restype = C.c_int
@@ -75,40 +55,19 @@ def emul_lib(wave: bool = False, tag: str = "", defs=()):
     else:
         lib.rays_emul_summary_trace.restype = C.c_int
         lib.rays_emul_summary_trace.argtypes = [pp, C.c_int, dp, dp, ip, ip, dp, dp, dp, dp, dp, C.c_int]
-    lib.rays_emul_set_zfun_table.restype = C.c_int
-    lib.rays_emul_set_zfun_table.argtypes = [dp, C.c_int, C.c_double, C.c_double]
-    from tests.emul_lib import _set_zfun
-    _set_zfun(lib.rays_emul_set_zfun_table)
-    _libs[key] = lib
-    return lib
+
+
+def emul_lib(wave: bool = False, tag: str = "", defs=()):
+    """librays_emul_summary[_wave][_<tag>].so, built on first use (extra -D switches get a library of their own)."""
+    return eb.variant_lib("emul_summary.cpp", "summary", ["-DRAYS_RK4_NO_HANDOVER"], "-DRAYS_EMUL_SUMMARY_WAVE=1", wave,
+                          tag, defs, _declare)
 
 
 def set_axisym_tables(g, lib):
     """Hands a fixture's eqdsk / profile tables (if it has any) to an emulation library."""
-    tab = {k[4:]: (float(g[k]) if g[k].ndim == 0 else g[k]) for k in g.files if k.startswith("axi_")}
-    if not any(np.size(tab.get(k, ())) for k in ("r_grid", "ne_grid", "te_grid", "ti_grid")):
-        return
-    t, keep = axisym_tables_struct(tab)
-    fn = lib.rays_emul_set_axisym_tables
-    fn.restype = C.c_int
-    fn.argtypes = [C.POINTER(AxisymTables), C.c_int, C.c_double, C.c_double]
-    lin = "lin_psi" in tab
-    fn(C.byref(t), int(lin), float(tab["lin_dR"]) if lin else 0.0, float(tab["lin_dZ"]) if lin else 0.0)
-
-
-def _outputs(n, nv):
-    # poisoned, not zeroed: every element has to be written by the kernel
-    return dict(npoints=np.full(n, -7, dtype=np.int32), stop_code=np.full(n, -7, dtype=np.int32),
-                start_ray_vec=np.full((n, nv), np.nan), end_ray_vec=np.full((n, nv), np.nan),
-                end_residuals=np.full(n, np.nan), max_residuals=np.full(n, np.nan))
-
-
-def _d(a):
-    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
-
-
-def _i(a):
-    return a.ctypes.data_as(C.POINTER(C.c_int32))
+    tab = eb.axisym_tables_of(g)
+    if tab is not None:
+        eb.set_axisym_tables(lib, tab)
 
 
 def emul_trace(p: RaysParams, rvec0, rindex_vec0, ds_values=None, lib=None) -> dict:

@@ -16,7 +16,7 @@ EMUL_DIR = os.path.join(ROOT, "tests", "hip_emul")
 def build_sanitized_resources():
     exe = os.path.join(EMUL_DIR, "emul_capi_resources_san")
     srcs = [os.path.join(EMUL_DIR, "emul_capi_resources_main.cpp"), os.path.join(EMUL_DIR, "hip", "hip_runtime.h"),
-            os.path.join(EMUL_DIR, "hip", "hip_runtime_api_emul.h"),
+            os.path.join(EMUL_DIR, "hip", "hip_runtime_api_emul.h"), os.path.join(EMUL_DIR, "emul_capi_check.hpp"),
             os.path.join(ROOT, "rays_amd", "csrc", "rays_capi_resources.hpp")]
     if not os.path.exists(exe) or any(os.path.getmtime(s) > os.path.getmtime(exe) for s in srcs):
         subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-w", "-fsanitize=address,undefined",

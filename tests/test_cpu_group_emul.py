@@ -9,6 +9,7 @@ from rays_amd.params import copy_params
 from tests import group_emul_lib as ge
 from tests import oracle_lib
 from tests.common import load_golden
+from tests.emul_build import axisym_tables_of
 
 ARRAYS = ("npoints", "stop_code", "ray_vec", "residual", "end_ray_vec", "end_residuals", "max_residuals")
 # SG + finite-difference dD.  The two axisym fixtures carry damping (nv = 8: the one-ray-per-lane kernel's shape); their
@@ -18,8 +19,8 @@ CASES = ["gold_solovev64_sg_num", "gold_slab_shear_gauss_3spec_sg_num", "gold_ax
 
 
 def _tables(g):
-    tab = {k[4:]: (float(g[k]) if g[k].ndim == 0 else g[k]) for k in g.files if k.startswith("axi_")}
-    if any(np.size(tab.get(k, ())) for k in ("r_grid", "ne_grid", "te_grid", "ti_grid")):
+    tab = axisym_tables_of(g)
+    if tab is not None:
         ge.set_axisym_tables(tab)
 
 

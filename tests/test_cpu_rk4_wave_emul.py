@@ -9,6 +9,7 @@ from rays_amd.params import copy_params
 from tests import group_emul_lib as ge
 from tests import oracle_lib
 from tests.common import load_golden
+from tests.emul_build import axisym_tables_of
 
 ARRAYS = ("npoints", "stop_code", "ray_vec", "residual", "end_ray_vec", "end_residuals", "max_residuals")
 # RAYS_REFILL_EVENT_COST (idle lane-trips that trigger a pass): the default and "at the next stage-3 trip"
@@ -20,8 +21,8 @@ def _lib(variant):
 
 
 def _tables(g, library):
-    tab = {k[4:]: (float(g[k]) if g[k].ndim == 0 else g[k]) for k in g.files if k.startswith("axi_")}
-    if any(np.size(tab.get(k, ())) for k in ("r_grid", "ne_grid", "te_grid", "ti_grid")):
+    tab = axisym_tables_of(g)
+    if tab is not None:
         ge.set_axisym_tables(tab, library)
 
 

@@ -5,40 +5,19 @@ from __future__ import annotations
 
 import ctypes as C
 import itertools
-import os
-import subprocess
 
 import numpy as np
 
 from rays_amd.params import RaysParams
-from tests.common import ROOT
+from tests import emul_build as eb
+from tests.emul_build import d as _d, i as _i
 from tests.summary_lib import set_axisym_tables  # noqa: F401  (the same entry of the emulation libraries)
 
-_DIR = os.path.join(ROOT, "tests", "hip_emul")
-_CSRC = os.path.join(ROOT, "rays_amd", "csrc")
 STATE_KEYS = ("v", "s", "nstep", "stop_code", "resid", "sg_err", "flags")
 SUMMARY_KEYS = ("npoints", "stop_code", "end_ray_vec", "end_residuals", "max_residuals")
 REFUSED = 1   # include/rays_hip.h: RAYS_STATE_REFUSED
 
-_libs = {}
-_SRCS = ["emul_window.cpp", "emul_trace.cpp", "emul_group.cpp", "hip/hip_runtime.h", "hip/hip_wave_emul.h"]
-_PRODUCT = ["rays_libm.hpp", "rays_libm_tables.inc", "rays_device.hpp", "rays_device_arith.inc", "rays_trace.hpp",
-            "rays_rk4.hpp", "rays_rk4_body.inc", "rays_rk4_pass.inc", "rays_rk4_take.inc", "rays_sg.hpp", "rays_sg_group.hpp",
-            "rays_dev_params.inc"]
-
-
-def emul_lib(wave: bool = False, tag: str = "", defs=()):
-    """librays_emul_window[_wave][_<tag>].so, built on first use (extra -D switches get a library of their own)."""
-    key = (wave, tag)
-    if key in _libs:
-        return _libs[key]
-    path = os.path.join(_DIR, "librays_emul_window" + ("_wave" if wave else "") + (f"_{tag}" if tag else "") + ".so")
-    srcs = [os.path.join(_DIR, f) for f in _SRCS] + [os.path.join(_CSRC, f) for f in _PRODUCT]
-    if not os.path.exists(path) or any(os.path.getmtime(s) > os.path.getmtime(path) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fno-extern-tls-init",
-                               "-fPIC", "-shared", "-w", "-DRAYS_RK4_NO_HANDOVER",
-                               *(["-DRAYS_EMUL_WINDOW_WAVE=1"] if wave else []), *defs, "-I", _DIR, srcs[0], "-o", path])
-    lib = C.CDLL(path)
+def _declare(lib, wave):
     dp, ip, pp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(RaysParams)
     state = [dp, dp, ip, ip, dp, dp, ip]
     if wave:
@@ -47,20 +26,12 @@ def emul_lib(wave: bool = False, tag: str = "", defs=()):
     else:
         lib.rays_emul_window.restype = C.c_int
         lib.rays_emul_window.argtypes = [pp, C.c_int, C.c_int, dp, dp, *state, C.c_int, dp, dp, ip, dp]
-    lib.rays_emul_set_zfun_table.restype = C.c_int
-    lib.rays_emul_set_zfun_table.argtypes = [dp, C.c_int, C.c_double, C.c_double]
-    from tests.emul_lib import _set_zfun
-    _set_zfun(lib.rays_emul_set_zfun_table)
-    _libs[key] = lib
-    return lib
 
 
-def _d(a):
-    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
-
-
-def _i(a):
-    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))
+def emul_lib(wave: bool = False, tag: str = "", defs=()):
+    """librays_emul_window[_wave][_<tag>].so, built on first use (extra -D switches get a library of their own)."""
+    return eb.variant_lib("emul_window.cpp", "window", ["-DRAYS_RK4_NO_HANDOVER"], "-DRAYS_EMUL_WINDOW_WAVE=1", wave, tag,
+                          defs, _declare)
 
 
 def new_state(nray: int, nv: int) -> dict:
