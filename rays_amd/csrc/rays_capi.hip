@@ -1956,7 +1956,16 @@ int rays_hip_probe(const rays_params_t* p, int n, const double* v, double* cold7
                    double* dvds, double* resid, int32_t* codes) {
   int rc = rays_hip_check_params(p);
   if (rc) return rc;
+  // what probe_kernel (rays_probe.hip) evaluates: the nv = 7 rows of the three equilibria with two or three species --
+  // any other shape returns from the kernel with nothing written
+  if (p->nv != 7 || (p->nspec + 1 != 2 && p->nspec + 1 != 3) || p->equilib_model < 0 || p->equilib_model > 2) {
+    char msg[200];
+    std::snprintf(msg, sizeof msg, "rays_hip_probe: no kernel built for this configuration (equilibrium %d, %d species, "
+                  "nv = %d): the probe evaluates nv = 7 with 2 or 3 species", p->equilib_model, p->nspec + 1, p->nv);
+    return fail(msg);
+  }
   if (n <= 0) return 0;
+  if (!v || !cold7 || !num7 || !dvds || !resid || !codes) return fail("rays_hip_probe: null pointer");
   const size_t nv = (size_t)p->nv;
   DeviceBuffers bufs;
   double *d_v = nullptr, *d_c = nullptr, *d_n = nullptr, *d_f = nullptr, *d_r = nullptr;

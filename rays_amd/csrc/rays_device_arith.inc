@@ -1538,11 +1538,13 @@ RAYS_DEV int ray_equations(const DevParams& P, const EqPoint<NS>& eq, const doub
     double vu[3];
 #pragma unroll
     for (int i = 0; i < 3; i++) vu[i] = div(vg[i], Rvg0);
+    // sum() starts from +0: a row whose three terms are all -0 (Bx = 0 and a group velocity with negative components)
+    // is +0 in the reference, and the leading 0. keeps it so here
 #pragma unroll
     for (int j = 0; j < 3; j++)
-      dvds[NV0 + j] = dsd * vu[0] * eq.gbt[0][j] + dsd * vu[1] * eq.gbt[1][j] + dsd * vu[2] * eq.gbt[2][j];
-    dvds[NV0 + 3] = dsd * vu[0] * eq.gradns[0][0] + dsd * vu[1] * eq.gradns[0][1] + dsd * vu[2] * eq.gradns[0][2];
-    dvds[NV0 + 4] = dsd * vu[0] * eq.gradts0[0] + dsd * vu[1] * eq.gradts0[1] + dsd * vu[2] * eq.gradts0[2];
+      dvds[NV0 + j] = 0. + dsd * vu[0] * eq.gbt[0][j] + dsd * vu[1] * eq.gbt[1][j] + dsd * vu[2] * eq.gbt[2][j];
+    dvds[NV0 + 3] = 0. + dsd * vu[0] * eq.gradns[0][0] + dsd * vu[1] * eq.gradns[0][1] + dsd * vu[2] * eq.gradns[0][2];
+    dvds[NV0 + 4] = 0. + dsd * vu[0] * eq.gradts0[0] + dsd * vu[1] * eq.gradts0[1] + dsd * vu[2] * eq.gradts0[2];
   }
   return 0;
 }

@@ -33,7 +33,7 @@ __device__ void probe_one(const DevParams& P, const double* vin, double* cold7, 
   bool cs_stop;
   rhs_eval<EQ, NS, RAYS_DERIV_COLD, NV>(P, v, true, r, cs_flag, cs_stop, code, f);
 #pragma unroll
-  for (int i = 0; i < NV; i++) dvds[i] = f[i];
+  for (int i = 0; i < NV; i++) dvds[i] = code ? 0. : f[i];  // eqn_ray returns before it sets dvds: the caller's zeros stay
   *resid = r;
   codes[1] = code;
   codes[2] = cs_flag;

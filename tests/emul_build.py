@@ -35,14 +35,30 @@ def stale(lib, deps=None):
     return any(os.path.getmtime(d) > built for d in (dependencies() if deps is None else deps))
 
 
-def command(src, out, defs=(), sanitize=False):
-    return ["g++", *(SANITIZE if sanitize else []), *FLAGS, *defs, "-I", DIR, os.path.join(DIR, src), "-o", out]
+def command(src, out, defs=(), sanitize=False, directory=DIR):
+    return ["g++", *(SANITIZE if sanitize else []), *FLAGS, *defs, "-I", directory, os.path.join(directory, src), "-o", out]
 
 
-def build(src, out, defs=(), sanitize=False):
-    """Compiles tests/hip_emul/<src> with the -D switches `defs` into the library `out`, unless it is up to date."""
-    if stale(out):
-        subprocess.check_call(command(src, out, defs, sanitize))
+def build(src, out, defs=(), sanitize=False, directory=DIR):
+    """Compiles tests/hip_emul/<src> with the -D switches `defs` into the library `out`, unless it is up to date.
+    `directory`: the tests/hip_emul of a copy of the source tree (mutated_tree) -- always built."""
+    if directory != DIR or stale(out):
+        subprocess.check_call(command(src, out, defs, sanitize, directory))
+
+
+def mutated_tree(dst, file, old, new, count=1):
+    """A copy of everything an emulation library reads (rays_amd/csrc, include, tests/hip_emul) under `dst`, with `old`
+    replaced by `new` in rays_amd/csrc/<file>: `old` has to occur exactly `count` times.  Returns the copy's
+    tests/hip_emul, for build(..., directory=)."""
+    import shutil
+    for d in (os.path.join("rays_amd", "csrc"), "include", os.path.join("tests", "hip_emul")):
+        shutil.copytree(os.path.join(ROOT, d), os.path.join(dst, d),
+                        ignore=shutil.ignore_patterns("*.so", "*.o", "build", "*.hip", "__pycache__"))
+    path = os.path.join(dst, "rays_amd", "csrc", file)
+    text = open(path).read()
+    assert text.count(old) == count, f"{file}: {text.count(old)} occurrences of {old!r}, expected {count}"
+    open(path, "w").write(text.replace(old, new))
+    return os.path.join(dst, "tests", "hip_emul")
 
 
 def d(a):

@@ -6,7 +6,9 @@ Runs oracle/_ref/rays_ref_dump (the reference RAYS_project hot path compiled fro
 configs/, and cuts small fixtures (inputs + expected outputs, data only) from its raw dump.
 Only runs where /root/reference was available to build the binary; the committed .npz files are
 what the tests read.  tests/golden/deposition_binner_cases.npz comes from oracle/_ref/ref_binner (the reference's
-binner_real alone) on the synthetic rays of tests/deposition_cases.py.
+binner_real alone) on the synthetic rays of tests/deposition_cases.py, tests/golden/rhs_state_cases.npz from
+oracle/_ref/ref_states (the reference's right-hand side and one ode_solver step) at the synthetic states of
+tests/rhs_state_cases.py.
 
     python tests/golden/make_golden.py [fixture names ...]    (re)generate
     python tests/golden/make_golden.py --check                 regenerate everything into a scratch directory and
@@ -195,6 +197,45 @@ def binner_fixture(out_root):
           f"-> {os.path.getsize(path) / 1e3:.0f} kB")
 
 
+RHS_STATES_FIXTURE = os.path.join("tests", "golden", "rhs_state_cases.npz")
+REF_STATES = os.path.join(ROOT, "oracle", "_ref", "ref_states")
+
+
+def rhs_states_fixture(out_root):
+    """tests/golden/rhs_state_cases.npz: the synthetic states of tests/rhs_state_cases.py (thresholds of the box tests, the
+    plasma edge, the damping argument, check_save, refused RK4 stages) and what the reference's own equilibrium,
+    deriv_cold, deriv_num, eqn_ray, check_save and ode_solver make of them (oracle/_ref/ref_states =
+    oracle/ref_states_driver.f90 on the reference's objects): one child process per case.  Where the reference's
+    equilibrium returns with an error its eq_point is undefined: such a record keeps its flags and is blanked otherwise
+    (tests/refdump.py: blank_undefined)."""
+    from tests import rhs_state_cases as rc
+    from tests.refdump import blank_undefined, read_states, write_states
+    out, total = {}, 0
+    for case, (v, s, label, side) in rc.all_states().items():
+        cfg = case + ".in"
+        check_deterministic(cfg)
+        with tempfile.TemporaryDirectory() as d:
+            shutil.copy(os.path.join(ROOT, "configs", cfg), os.path.join(d, "rays.in"))
+            for f in os.listdir(os.path.join(ROOT, "configs")):
+                if f.endswith(".geqdsk"):
+                    shutil.copy(os.path.join(ROOT, "configs", f), d)
+            write_states(os.path.join(d, "states.bin"), v, s)
+            env = dict(os.environ, RAYS_STATES_IN="states.bin", RAYS_STATES_OUT="records.bin")
+            run = subprocess.run([REF_STATES], cwd=d, env=env, stdout=subprocess.DEVNULL)
+            assert run.returncode == 0, f"{case}: the reference stopped (exit status {run.returncode}): drop or move a state"
+            probe, step = read_states(os.path.join(d, "records.bin"))
+        assert len(probe) == len(v) and step is not None and same_bits(probe["v"], v), case
+        geom = rc.reference_undefined(case, v)
+        probe, step = blank_undefined(probe, step, rc.integrates_numerically(case), geom)
+        out[case + ":s"], out[case + ":label"], out[case + ":side"], out[case + ":geom"] = s, label, side, geom
+        out[case + ":probe"], out[case + ":step"] = probe, step
+        total += len(v)
+    out["cases"] = np.array(list(rc.CASES))
+    path = os.path.join(out_root, RHS_STATES_FIXTURE)
+    np.savez_compressed(path, **out)
+    print(f"rhs_state_cases: {total} states of {len(rc.CASES)} cases -> {os.path.getsize(path) / 1e3:.0f} kB")
+
+
 def same_bits(a, b):
     """Two arrays of a fixture: same dtype, shape and bytes (floats compared through their bit patterns)."""
     a, b = np.asarray(a), np.asarray(b)
@@ -224,6 +265,8 @@ def generate(out_root, only=()):
         deposition_file_fixture(out_root)
     if not only or "deposition_binner_cases" in only:
         binner_fixture(out_root)
+    if not only or "rhs_state_cases" in only:
+        rhs_states_fixture(out_root)
     host_tabs = {}
     for name, cfg, subset, stride, nprobe in CASES:
         if only and name not in only:
@@ -326,7 +369,7 @@ def check():
     diffs = []
     with tempfile.TemporaryDirectory() as d:
         generate(d)
-        for name in [c[0] + ".npz" for c in CASES] + [os.path.basename(BINNER_FIXTURE)]:
+        for name in [c[0] + ".npz" for c in CASES] + [os.path.basename(BINNER_FIXTURE), os.path.basename(RHS_STATES_FIXTURE)]:
             a, b = np.load(os.path.join(d, "tests", "golden", name)), np.load(os.path.join(ROOT, "tests", "golden", name))
             if set(a.files) != set(b.files):
                 diffs.append(f"{name}: keys differ: only regenerated {sorted(set(a.files) - set(b.files))}, "
@@ -350,6 +393,8 @@ def main():
         sys.exit("oracle/_ref/rays_ref_dump missing: run `bash oracle/build_ref.sh` first")
     if not os.path.exists(REF_BINNER):
         sys.exit("oracle/_ref/ref_binner missing: run `bash oracle/build_ref.sh` first")
+    if not os.path.exists(REF_STATES):
+        sys.exit("oracle/_ref/ref_states missing: run `bash oracle/build_ref.sh` first")
     if "--check" in args:
         diffs = check()
         for x in diffs:

@@ -50,6 +50,86 @@ def read_dump(path: str) -> dict:
     return out
 
 
+STATES_MAGIC = 0x52485353
+
+
+def write_states(path: str, v, s):
+    """The input of oracle/ref_states_driver.f90: int32 n, nv, then (s, v(1:nv)) per state."""
+    v = np.ascontiguousarray(v, dtype="<f8")
+    n, nv = v.shape
+    rows = np.concatenate([np.asarray(s, dtype="<f8").reshape(n, 1), v], axis=1)
+    with open(path, "wb") as f:
+        f.write(np.array([n, nv], dtype="<i4").tobytes())
+        f.write(np.ascontiguousarray(rows).tobytes())
+
+
+def read_states(path: str):
+    """What oracle/ref_states_driver.f90 wrote: (probe records, step records or None).  Probe records carry the fields of
+    read_dump's `probes` (without iray / j) plus the flag texts equilibrium, eqn_ray and check_save left and the
+    stop_ode each of the two set; step records v1, resid, the flags and stop_ode of ode_solver and of the check_save
+    behind it, and the flag equilibrium leaves at v1."""
+    b = open(path, "rb").read()
+    magic, n, nv, nspec, rk4 = (int(x) for x in np.frombuffer(b, dtype="<i4", count=5))
+    assert magic == STATES_MAGIC, hex(magic)
+    neq = 28 + 12 * (nspec + 1)
+    probe = [("v", "<f8", (nv,)), ("eq_flag", "S60"), ("eq", "<f8", (neq,)), ("cold", "<f8", (7,)), ("num", "<f8", (7,)),
+             ("dvds", "<f8", (nv,)), ("resid", "<f8"), ("rhs_flag", "S30"), ("rhs_stop", "<i4"), ("cs_flag", "S30"),
+             ("cs_stop", "<i4"), ("num_undef", "<i4")]
+    step = [("v1", "<f8", (nv,)), ("resid1", "<f8"), ("step_flag", "S30"), ("step_stop", "<i4"), ("cs1_flag", "S30"),
+            ("cs1_stop", "<i4"), ("step_num_undef", "<i4"), ("eq1_flag", "S60")]
+    rec = np.dtype(probe + (step if rk4 else []))
+    assert 20 + rec.itemsize * n == len(b), (n, rec.itemsize, len(b))
+    a = np.frombuffer(b, dtype=rec, count=n, offset=20)
+    pr = np.zeros(n, dtype=np.dtype(probe))
+    for name, kind, *_ in probe:
+        pr[name] = np.char.rstrip(a[name]) if kind[0] == "S" else a[name]     # (Fortran pads with blanks)
+    if not rk4:
+        return pr, None
+    st = np.zeros(n, dtype=np.dtype(step))
+    for name, kind, *_ in step:
+        st[name] = np.char.rstrip(a[name]) if kind[0] == "S" else a[name]
+    return pr, st
+
+
+def defined_masks(probe, step, numerical, geom):
+    """Which parts of a state's records are facts of the reference (boolean arrays by name):
+      flags   the flag equilibrium left (and eqn_ray's, which repeats it)          -- not where geom == 2
+      values  eq, cold, resid and check_save's flag and stop_ode                   -- equilibrium returned no error, geom == 0
+      num     deriv_num's result                   -- values, and none of the six points it displaces r to is refused
+      rhs     dvds and the flag eqn_ray left       -- values (and num, where the configuration integrates with deriv_num)
+      step    v1 and the flag ode_solver left      -- flags, geom == 0 (and no stage state with a refused displaced point)
+      step_cs resid and flags of the check_save behind the step -- step, no stage refused, equilibrium accepts v1
+    Where equilibrium returns with an error the reference stores no eq_point (equilibrium_m.f90:198-202): what the
+    routines then compute with is what the state before left behind.  geom marks the states at which the reference
+    reads a variable it never set or memory outside an array (tests/rhs_state_cases.py: reference_undefined)."""
+    flags = geom != 2
+    values = (probe["eq_flag"] == b"") & (geom == 0)
+    num = values & (probe["num_undef"] == 0)
+    rhs = num if numerical else values
+    st = flags & (geom == 0) & (step["step_num_undef"] == 0)
+    st_cs = st & (step["step_stop"] == 0) & (step["eq1_flag"] == b"")
+    return dict(flags=flags, values=values, num=num, rhs=rhs, step=st, step_cs=st_cs)
+
+
+def blank_undefined(probe, step, numerical, geom):
+    """The records with everything that is no fact of the reference (defined_masks) zeroed: flags '', stop_ode -1."""
+    probe, step = probe.copy(), step.copy()
+    m = defined_masks(probe, step, numerical, geom)
+    for k in ("eq", "cold", "resid"):
+        probe[k][~m["values"]] = 0.0
+    probe["cs_flag"][~m["values"]], probe["cs_stop"][~m["values"]] = b"", -1
+    probe["num"][~m["num"]] = 0.0
+    probe["dvds"][~m["rhs"]] = 0.0
+    no_rhs_flag = ~(m["rhs"] | (m["flags"] & (probe["eq_flag"] != b"")))
+    probe["rhs_flag"][no_rhs_flag], probe["rhs_stop"][no_rhs_flag] = b"", -1
+    probe["eq_flag"][~m["flags"]] = b"?"
+    step["v1"][~m["step"]] = 0.0
+    step["step_flag"][~m["step"]], step["step_stop"][~m["step"]] = b"", -1
+    step["resid1"][~m["step_cs"]], step["cs1_flag"][~m["step_cs"]], step["cs1_stop"][~m["step_cs"]] = 0.0, b"", -1
+    step["eq1_flag"][~m["step"]] = b""
+    return probe, step
+
+
 def read_axisym_tables(path: str) -> dict:
     """Spline tables written by ref_dump_driver.f90 (RAYS_DUMP_AXISYM)."""
     b = open(path, "rb").read()

@@ -12,6 +12,7 @@ NO_HANDOVER = ["-DRAYS_RK4_NO_HANDOVER"]
 # every (main source, -D switches) the CPU tier builds a library from (the -D variants of a library read the same files)
 LIBRARIES = {
     "trace": ("emul_trace.cpp", []),
+    "probe": ("emul_probe.cpp", []),
     "group": ("emul_group.cpp", []),
     "summary": ("emul_summary.cpp", NO_HANDOVER),
     "summary_wave": ("emul_summary.cpp", NO_HANDOVER + ["-DRAYS_EMUL_SUMMARY_WAVE=1"]),
