@@ -12,6 +12,9 @@
 #   oracle/_ref/ref_states      the reference's initialize, then equilibrium / deriv_cold / deriv_num / eqn_ray / check_save
 #                               and one ode_solver step at states read from a file (oracle/ref_states_driver.f90) -- the
 #                               reference for tests/golden/rhs_state_cases.npz
+#   oracle/_ref/ref_launch      the reference's initialize and nothing after it: the fan its ray launcher leaves in
+#                               ray_init_m (oracle/ref_launch_driver.f90) -- the reference for
+#                               tests/golden/launch_cases.npz
 #   oracle/_ref/rays_hip_dropin reference host (initialize/ray_results/...) with trace_rays
 #                               REPLACED by fortran/trace_rays_hip.f90, the three ray launchers by
 #                               fortran/{solovev,simple_slab,axisym_toroid}_ray_init_hip.f90 and the
@@ -135,6 +138,10 @@ $FC $FFLAGS -o "$OUT/ref_binner" ref_binner_driver.o bin_to_uniform_grid_m.o
 # ---- (1d) the reference's right-hand side at states read from a file (no tracing), under a driver of this repo ----
 $FC $FFLAGS -c "$HERE/ref_states_driver.f90" -o ref_states_driver.o
 $FC $FFLAGS -o "$OUT/ref_states" ref_states_driver.o $LIBOBJS
+
+# ---- (1e) the reference's initialize alone (its ray launchers), the fan written out, under a driver of this repo ----
+$FC $FFLAGS -c "$HERE/ref_launch_driver.f90" -o ref_launch_driver.o
+$FC $FFLAGS -o "$OUT/ref_launch" ref_launch_driver.o $LIBOBJS
 
 # ---- (2) drop-in: same host objects, trace_rays replaced by the HIP shim --------------------
 LIBHIP=$ROOT/rays_amd/lib/librays_hip.so

@@ -1938,12 +1938,13 @@ int rays_hip_ray_init(const rays_params_t* p, const rays_fan_t* fan, int nray_ma
     for (size_t i = 0; i < n; i++) ray_pwr_wt[i] = 1.0 / (double)n;
   } else {
     // solovev_ray_init_nphi_ntheta_m.f90:196: only ray_pwr_wt(count) = 1. after each r-launch
-    // loop; the other entries are left unset by the reference (zero here)
+    // loop, and the whole array divided by nray at the end (:206); the other entries are left
+    // unset by the reference (zero here)
     for (size_t i = 0; i < n; i++) ray_pwr_wt[i] = 0.;
     const int nl = (int)first.size();
     for (int ir = 0; per_r > 0 && ir < nl / per_r; ir++) {
       const int end = (ir + 1) * per_r < nl ? first[(ir + 1) * per_r] : (int)n;  // count after this r loop
-      if (end >= 1) ray_pwr_wt[end - 1] = 1.;
+      if (end >= 1) ray_pwr_wt[end - 1] = 1. / (double)n;
     }
   }
   return 0;

@@ -70,9 +70,13 @@ RAYS_DEV void rlsdp_cold(const double alpha[NS], const double gamma[NS], double&
 // Real n1 of the requested mode, or evanescent (returns false).  The reference works in complex
 // arithmetic; for a real discriminant >= 0 every imaginary part is an exact zero and the complex
 // quotients are compiler-rt __divdc3 with zero imaginary parts (divdc3_re).
+// nan_is_kept: the callers' tests of Im(n1).  The slab and Solovev launchers drop a launch when
+// `Im /= 0.`, which a NaN satisfies; the axisym launcher when `abs(Im) > 10*tiny`
+// (axisym_toroid_ray_init_R_Z_nphi_ntheta_m.f90:196), which a NaN does not: a launch whose n2, n3
+// are NaN (the magnetic axis under solovev_magnetics: grad psi = 0) is kept there, with NaN n1.
 template <int NS>
 RAYS_DEV bool solve_n1_vs_n2_n3(const double alpha[NS], const double gamma[NS], int wave_mode, int k_sign,
-                                double n2, double n3, double& n1) {
+                                double n2, double n3, bool nan_is_kept, double& n1) {
   double S, D, Pp, R, L;
   rlsdp_cold<NS>(alpha, gamma, S, D, Pp, R, L);
   const double n3sq = n3 * n3;
@@ -80,7 +84,7 @@ RAYS_DEV bool solve_n1_vs_n2_n3(const double alpha[NS], const double gamma[NS], 
   const double b = -R * L - Pp * S + n3sq * (Pp + S);
   const double c = Pp * (n3sq - R) * (n3sq - L);
   const double discr = b * b - 4.0 * a * c;
-  if (!(discr >= 0.0)) return false;
+  if (nan_is_kept ? discr < 0.0 : !(discr >= 0.0)) return false;
   const double sd = sqrt(discr);
   const bool neg = copysign(1.0, b) < 0.0;
   // sgn(b) < 0: plus = (-b + sd)/(2a), minus = 2c/(-b + sd); else minus = (-b - sd)/(2a), plus = 2c/(-b - sd)
@@ -93,7 +97,7 @@ RAYS_DEV bool solve_n1_vs_n2_n3(const double alpha[NS], const double gamma[NS], 
   const double nperp_sq = wave_mode == WAVE_PLUS ? plus : wave_mode == WAVE_MINUS ? minus
                           : wave_mode == WAVE_FAST ? fast : slow;
   const double arg = nperp_sq - n2 * n2;
-  if (!(arg >= 0.0)) return false;
+  if (nan_is_kept ? arg < 0.0 : !(arg >= 0.0)) return false;
   n1 = (double)k_sign * sqrt(fabs(arg));
   return true;
 }
@@ -144,7 +148,7 @@ RAYS_DEV bool fan_member(const DevParams& P, const FanArgs& F, const double rvec
     const double n2 = ny * eq.bunit[2] - nz * eq.bunit[1];
     const double n3 = ny * eq.bunit[1] + nz * eq.bunit[2];
     double nx;
-    if (!solve_n1_vs_n2_n3<NS>(eq.alpha, eq.gamma, F.wave_mode, F.k0_sign, n2, n3, nx)) return false;
+    if (!solve_n1_vs_n2_n3<NS>(eq.alpha, eq.gamma, F.wave_mode, F.k0_sign, n2, n3, false, nx)) return false;
     rindex0[0] = nx;
     rindex0[1] = ny;
     rindex0[2] = nz;
@@ -168,7 +172,8 @@ RAYS_DEV bool fan_member(const DevParams& P, const FanArgs& F, const double rvec
   const double n3 = (bu[0] * rv[0] + bu[1] * rv[1]) + bu[2] * rv[2];
   const double n2 = (trans[0] * rv[0] + trans[1] * rv[1]) + trans[2] * rv[2];
   double npsi;
-  if (!solve_n1_vs_n2_n3<NS>(eq.alpha, eq.gamma, F.wave_mode, F.k0_sign, n2, n3, npsi)) return false;
+  if (!solve_n1_vs_n2_n3<NS>(eq.alpha, eq.gamma, F.wave_mode, F.k0_sign, n2, n3, (EQ & 3) == RAYS_EQ_AXISYM, npsi))
+    return false;
 #pragma unroll
   for (int i = 0; i < 3; i++) rindex0[i] = rv[i] - npsi * psi_unit[i];
   return true;

@@ -244,6 +244,15 @@ def _rlsdp_cold(alpha, gamma):
 
 def solve_n1_vs_n2_n3(alpha, gamma, wave_mode: str, k_sign: int, n2, n3):
     """Real n1 (NaN where evanescent) -- dispersion_solvers_m.f90:49-112 + disp_solve_cold_n1sq_vs_n3."""
+    n1, keep = _solve_n1_keep(alpha, gamma, wave_mode, k_sign, n2, n3)
+    return np.where(keep, n1, np.nan)
+
+
+def _solve_n1_keep(alpha, gamma, wave_mode: str, k_sign: int, n2, n3, nan_is_kept: bool = False):
+    """(n1, keep): the real n1 and which launches the caller keeps.  The slab and Solovev launchers drop a launch when
+    `Im(n1) /= 0.`, which a NaN satisfies; the axisym launcher when `abs(Im(n1)) > 10*tiny`
+    (axisym_toroid_ray_init_R_Z_nphi_ntheta_m.f90:196), which a NaN does not (nan_is_kept): a launch whose n2, n3 are
+    NaN is kept there, with NaN n1."""
     modes = {"plus": 0, "minus": 1, "fast": 2, "slow": 3}
     if wave_mode.strip() not in modes:
         raise ConfigError(f"solve_disp: improper wave_mode = {wave_mode!r}")
@@ -255,8 +264,8 @@ def solve_n1_vs_n2_n3(alpha, gamma, wave_mode: str, k_sign: int, n2, n3):
     b = -R * L - P * S + n3sq * (P + S)
     c = P * (n3sq - R) * (n3sq - L)
     discr = b * b - 4.0 * a * c
-    ok = discr >= 0.0
     with np.errstate(invalid="ignore", divide="ignore"):
+        ok = ~(discr < 0.0) if nan_is_kept else discr >= 0.0
         sd = np.sqrt(np.where(ok, discr, np.nan))
         neg = np.copysign(1.0, b) < 0.0
         # sgn_b < 0: plus=(-b+sd)/(2a), minus=2c/(-b+sd) ; else minus=(-b-sd)/(2a), plus=2c/(-b-sd)
@@ -269,8 +278,9 @@ def solve_n1_vs_n2_n3(alpha, gamma, wave_mode: str, k_sign: int, n2, n3):
         slow = np.where(np.abs(plus) <= np.abs(minus), minus, plus)
         nperp_sq = [plus, minus, fast, slow][modes[wave_mode.strip()]]
         arg = nperp_sq - n2 * n2
-        n1 = np.where(ok & (arg >= 0.0), float(k_sign) * np.sqrt(np.abs(arg)), np.nan)
-    return n1
+        keep = ok & (~(arg < 0.0) if nan_is_kept else arg >= 0.0)
+        n1 = float(k_sign) * np.sqrt(np.abs(arg))
+    return n1, keep
 
 
 # ---- fans ---------------------------------------------------------------------------------------
@@ -370,12 +380,12 @@ def ray_init_solovev_nphi_ntheta(p: RaysParams, nml: Dict[str, Dict[str, Any]]):
         raise ConfigError("No successful ray initializations")
     rvec0 = np.ascontiguousarray(np.concatenate(rv, axis=0))
     rindex_vec0 = np.ascontiguousarray(np.concatenate(nv, axis=0))
-    # the reference sets only ray_pwr_wt(count) = 1. after each r-launch loop (:196) and leaves the
-    # other entries of the freshly allocated array unset (zero here)
+    # the reference sets only ray_pwr_wt(count) = 1. after each r-launch loop (:196), divides the array by nray
+    # at the end (:206) and leaves the other entries of the freshly allocated array unset (zero here)
     ray_pwr_wt = np.zeros(len(rvec0))
     for c in marks:
         if c >= 1:
-            ray_pwr_wt[c - 1] = 1.0
+            ray_pwr_wt[c - 1] = 1.0 / len(rvec0)
     return rvec0, rindex_vec0, ray_pwr_wt
 
 
@@ -414,8 +424,8 @@ def ray_init_axisym_toroid_R_Z_nphi_ntheta(p: RaysParams, nml: Dict[str, Dict[st
         rindex = r_ph[..., None] * phi_unit + r_th[..., None] * theta_unit
         n3 = (bunit[0] * rindex[..., 0] + bunit[1] * rindex[..., 1]) + bunit[2] * rindex[..., 2]
         n2 = (trans_unit[0] * rindex[..., 0] + trans_unit[1] * rindex[..., 1]) + trans_unit[2] * rindex[..., 2]
-        npsi = solve_n1_vs_n2_n3(alpha, gamma, str(rf.get("wave_mode", "")), int(rf.get("k0_sign", 1)), n2, n3)
-        keep = ~np.isnan(npsi)
+        npsi, keep = _solve_n1_keep(alpha, gamma, str(rf.get("wave_mode", "")), int(rf.get("k0_sign", 1)), n2, n3,
+                                    nan_is_kept=True)
         rv.append(np.broadcast_to(rvec, (int(keep.sum()), 3)))
         nv.append(rindex[keep] - npsi[keep][:, None] * psi_unit)
     if not rv or sum(len(a) for a in rv) == 0:

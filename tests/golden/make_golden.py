@@ -8,7 +8,8 @@ Only runs where /root/reference was available to build the binary; the committed
 what the tests read.  tests/golden/deposition_binner_cases.npz comes from oracle/_ref/ref_binner (the reference's
 binner_real alone) on the synthetic rays of tests/deposition_cases.py, tests/golden/rhs_state_cases.npz from
 oracle/_ref/ref_states (the reference's right-hand side and one ode_solver step) at the synthetic states of
-tests/rhs_state_cases.py.
+tests/rhs_state_cases.py, tests/golden/launch_cases.npz from oracle/_ref/ref_launch (the reference's initialize: its ray
+launchers) on the namelists of tests/launch_cases.py.
 
     python tests/golden/make_golden.py [fixture names ...]    (re)generate
     python tests/golden/make_golden.py --check                 regenerate everything into a scratch directory and
@@ -236,6 +237,18 @@ def rhs_states_fixture(out_root):
     print(f"rhs_state_cases: {total} states of {len(rc.CASES)} cases -> {os.path.getsize(path) / 1e3:.0f} kB")
 
 
+LAUNCH_FIXTURE = os.path.join("tests", "golden", "launch_cases.npz")
+REF_LAUNCH = os.path.join(ROOT, "oracle", "_ref", "ref_launch")
+
+
+def launch_fixture(out_root):
+    """tests/golden/launch_cases.npz: the fans the reference's own ray launchers make of the namelists of
+    tests/launch_cases.py (oracle/_ref/ref_launch = oracle/ref_launch_driver.f90 on the reference's objects), one child
+    process per case; where every launch is dropped, the reference's exit status and stop text."""
+    from tests import launch_cases as lc
+    lc.generate(out_root, REF_LAUNCH)
+
+
 def same_bits(a, b):
     """Two arrays of a fixture: same dtype, shape and bytes (floats compared through their bit patterns)."""
     a, b = np.asarray(a), np.asarray(b)
@@ -267,6 +280,8 @@ def generate(out_root, only=()):
         binner_fixture(out_root)
     if not only or "rhs_state_cases" in only:
         rhs_states_fixture(out_root)
+    if not only or "launch_cases" in only:
+        launch_fixture(out_root)
     host_tabs = {}
     for name, cfg, subset, stride, nprobe in CASES:
         if only and name not in only:
@@ -369,7 +384,8 @@ def check():
     diffs = []
     with tempfile.TemporaryDirectory() as d:
         generate(d)
-        for name in [c[0] + ".npz" for c in CASES] + [os.path.basename(BINNER_FIXTURE), os.path.basename(RHS_STATES_FIXTURE)]:
+        for name in [c[0] + ".npz" for c in CASES] + [os.path.basename(BINNER_FIXTURE), os.path.basename(RHS_STATES_FIXTURE),
+                                                      os.path.basename(LAUNCH_FIXTURE)]:
             a, b = np.load(os.path.join(d, "tests", "golden", name)), np.load(os.path.join(ROOT, "tests", "golden", name))
             if set(a.files) != set(b.files):
                 diffs.append(f"{name}: keys differ: only regenerated {sorted(set(a.files) - set(b.files))}, "
@@ -395,6 +411,8 @@ def main():
         sys.exit("oracle/_ref/ref_binner missing: run `bash oracle/build_ref.sh` first")
     if not os.path.exists(REF_STATES):
         sys.exit("oracle/_ref/ref_states missing: run `bash oracle/build_ref.sh` first")
+    if not os.path.exists(REF_LAUNCH):
+        sys.exit("oracle/_ref/ref_launch missing: run `bash oracle/build_ref.sh` first")
     if "--check" in args:
         diffs = check()
         for x in diffs:

@@ -56,3 +56,19 @@ def test_cfg5_equilibrium_file_is_what_the_references_own_tool_writes(tmp_path):
     shutil.copy(os.path.join(ROOT, "configs", "solovev_2_eqdsk_129.in"), tmp_path / "rays.in")
     subprocess.run([tool], cwd=tmp_path, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
     assert (tmp_path / "solovev_129x129.geqdsk").read_bytes() == open(os.path.join(ROOT, "configs", "solovev_129x129.geqdsk"), "rb").read()
+
+
+REF_LAUNCH = os.path.join(ROOT, "oracle", "_ref", "ref_launch")
+
+
+@pytest.mark.skipif(not os.path.exists(REF_LAUNCH), reason="oracle/_ref/ref_launch not built (no /root/reference here)")
+def test_launch_fixture_is_what_the_references_launchers_produce(tmp_path):
+    """tests/golden/launch_cases.npz regenerated from oracle/_ref/ref_launch (the reference's initialize on the namelists
+    of tests/launch_cases.py): the same entries, each the same dtype, shape and bytes."""
+    import numpy as np
+    from tests import launch_cases as lc
+    lc.generate(str(tmp_path), REF_LAUNCH)
+    a, b = np.load(tmp_path / lc.FIXTURE), np.load(os.path.join(ROOT, lc.FIXTURE))
+    assert sorted(a.files) == sorted(b.files)
+    for k in a.files:
+        assert a[k].dtype == b[k].dtype and a[k].shape == b[k].shape and a[k].tobytes() == b[k].tobytes(), k

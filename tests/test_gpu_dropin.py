@@ -21,9 +21,14 @@ REF = os.path.join(ROOT, "oracle", "_ref", "rays_ref_dump")
 HIPBIN = os.path.join(ROOT, "oracle", "_ref", "rays_hip_dropin")
 
 
-def _run(binary, cfg, d, extra_env=None):
+def _run(binary, cfg, d, extra_env=None, text=None):
+    """`text`: the namelist itself, where it is no file under configs/"""
     os.makedirs(d, exist_ok=True)
-    shutil.copy(os.path.join(ROOT, "configs", cfg), os.path.join(d, "rays.in"))
+    if text is None:
+        shutil.copy(os.path.join(ROOT, "configs", cfg), os.path.join(d, "rays.in"))
+    else:
+        with open(os.path.join(d, "rays.in"), "w") as f:
+            f.write(text)
     for f in os.listdir(os.path.join(ROOT, "configs")):
         if f.endswith(".geqdsk") or f.startswith("ray_init_"):   # (file_input_ray_init reads ray_init_<run_label>.in)
             shutil.copy(os.path.join(ROOT, "configs", f), d)
@@ -90,3 +95,21 @@ def test_fortran_deposition_dropin_equals_reference_post_processor(cfg):
         for a, b in zip(outs["hip"][k], outs["ref"][k]):
             np.testing.assert_array_equal(a, b, err_msg=k)
     assert outs["hip"]["q_sum"] == outs["ref"]["q_sum"]
+
+
+@pytest.mark.skipif(not os.path.exists(HIPBIN), reason="reference binaries not built (oracle/build_ref.sh needs /root/reference)")
+@pytest.mark.parametrize("name", ["A.slab.fast_neg", "B.slab.x12.255", "A.solovev.slow_neg", "B.solovev.big.minus",
+                                  "A.axisym_eqdsk.minus_neg", "A.axisym_solmag.fast_neg", "A.axisym_eqlin.slow_pos"])
+def test_fortran_launcher_shims_equal_the_reference_records(name):
+    """fortran/{simple_slab,solovev,axisym_toroid}_ray_init_hip.f90 under the reference's initialize, on launches of
+    tests/launch_cases.py (one of class A and the large mixed fan per launcher; the axisym launcher does not step its
+    launch position: one per magnetics model): the fan equals the record the reference's own launcher left in
+    tests/golden/launch_cases.npz.  The trace after it is cut to two steps: this test is about the launch."""
+    from tests import launch_cases as lc
+    case = lc.BY_NAME[name]
+    short = lc.Case(case.name, case.cls, case.base, dict(case.overrides, ode_list=dict(nstep_max=2)))
+    rec = lc.load_fixture(name)
+    with tempfile.TemporaryDirectory() as d:
+        out = _run(HIPBIN, None, d, text=lc.namelist_text(short))
+    assert out["nray"] == int(rec["nray"])
+    lc.compare_fan(name, rec, out["rvec0"], out["rindex_vec0"], None, "the launcher shims under the reference host")
