@@ -74,6 +74,15 @@
         type(c_ptr) :: v, s, nstep, stop_code, resid, sg_err, flags
     end type rays_ray_state_t
 
+    ! One record of rays_hip_trace_profiles[_device] (include/rays_hip.h: rays_dep_profile_t).  which: RAYS_DEP_PTOTAL_PSI
+    ! = 0 | _RHO = 1 | _X = 2.  Host form: work = c_loc(work(n_bins, nray)) or c_null_ptr, profile_in = c_null_ptr,
+    ! profile = c_loc(profile(n_bins)); device form: device pointers, work(nray, n_bins) in Fortran order (bin-major).
+    integer(c_int), parameter :: RAYS_DEP_MAX_PROFILES = 2
+    type, bind(C) :: rays_dep_profile_t
+        integer(c_int) :: which, n_bins
+        type(c_ptr) :: work, profile_in, profile
+    end type rays_dep_profile_t
+
     type, bind(C) :: rays_params_t
         integer(c_int32_t) :: abi_version
         integer(c_int32_t) :: nv, nspec, nstep_max
@@ -381,6 +390,48 @@
           real(c_double), intent(inout) :: profile(*)
           real(c_double), intent(out) :: elapsed_s
        end function rays_hip_trace_deposition
+
+       ! Fused deposition into every profile of the equilibrium in ONE trace pass (include/rays_hip.h): what `call
+       ! trace_rays` followed by calculate_deposition_profiles gives for axisym_toroid -- Ptotal_psi and Ptotal_rho --
+       ! without the trajectories and without tracing twice.  profiles(n_profiles): one or two records.
+       integer(c_int) function rays_hip_trace_profiles_device(p, nray, d_rvec0, d_rindex_vec0, d_initial_ray_power, &
+                    & n_profiles, profiles, d_npoints, d_stop_code, d_start_ray_vec, d_end_ray_vec, d_end_residuals, &
+                    & d_max_residuals, hip_stream) bind(C, name='rays_hip_trace_profiles_device')
+          import :: c_int, c_ptr, rays_params_t, rays_dep_profile_t
+          type(rays_params_t), intent(in) :: p
+          integer(c_int), value :: nray, n_profiles
+          type(rays_dep_profile_t), intent(in) :: profiles(*)
+          type(c_ptr), value :: d_rvec0, d_rindex_vec0, d_initial_ray_power, d_npoints, d_stop_code, d_start_ray_vec
+          type(c_ptr), value :: d_end_ray_vec, d_end_residuals, d_max_residuals, hip_stream
+       end function rays_hip_trace_profiles_device
+
+       integer(c_int) function rays_hip_trace_profiles(p, nray, rvec0, rindex_vec0, initial_ray_power, n_profiles, &
+                    & profiles, npoints, stop_code, start_ray_vec, end_ray_vec, end_residuals, max_residuals, elapsed_s) &
+                    & bind(C, name='rays_hip_trace_profiles')
+          import :: c_int, c_int32_t, c_double, rays_params_t, rays_dep_profile_t
+          type(rays_params_t), intent(in) :: p
+          integer(c_int), value :: nray, n_profiles
+          real(c_double), intent(in) :: rvec0(3,*), rindex_vec0(3,*), initial_ray_power(*)
+          type(rays_dep_profile_t), intent(in) :: profiles(*)
+          integer(c_int32_t), intent(inout) :: npoints(*), stop_code(*)
+          real(c_double), intent(inout) :: start_ray_vec(*), end_ray_vec(*), end_residuals(*), max_residuals(*)
+          real(c_double), intent(out) :: elapsed_s
+       end function rays_hip_trace_profiles
+
+       ! the profiles of p's equilibrium in the reference's order, into which(RAYS_DEP_MAX_PROFILES); returns their number
+       integer(c_int) function rays_hip_deposition_profile_set(p, which) bind(C, name='rays_hip_deposition_profile_set')
+          import :: c_int, rays_params_t
+          type(rays_params_t), intent(in) :: p
+          integer(c_int), intent(out) :: which(*)
+       end function rays_hip_deposition_profile_set
+
+       ! (c_ptr to a NUL-terminated name, as the other *_kernel_name_for)
+       type(c_ptr) function rays_hip_profiles_kernel_name_for(p, nray, n_profiles) &
+                    & bind(C, name='rays_hip_profiles_kernel_name_for')
+          import :: c_int, c_ptr, rays_params_t
+          type(rays_params_t), intent(in) :: p
+          integer(c_int), value :: nray, n_profiles
+       end function rays_hip_profiles_kernel_name_for
 
        ! ASYNCHRONOUS on hip_stream (blocking before round 3): synchronise the stream before d_v1 / d_resid /
        ! d_stop_code are read on the host or from another stream; one caller thread per (device, stream).

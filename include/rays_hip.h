@@ -370,8 +370,8 @@ const char* rays_hip_summary_kernel_name_for(const rays_params_t* p, int nray);
  * row; equilib_model = solovev; Ptotal_psi / Ptotal_rho on a slab, Ptotal_x on axisym_toroid; Ptotal_rho without
  * rays_hip_set_rho_table or for the two magnetics models without rho; n_bins outside 1..RAYS_DEP_MAX_BINS; a null
  * required pointer; nray < 0; a shape that is not built (the message of rays_hip_check_params).
- * OUT OF SCOPE here: several profiles in one pass, the fused ds scan, a tolerance variant, more than
- * RAYS_DEP_MAX_BINS (320) bins. */
+ * OUT OF SCOPE here: the fused ds scan, a tolerance variant, more than RAYS_DEP_MAX_BINS (320) bins.  (Several profiles
+ * in one pass: rays_hip_trace_profiles* below.) */
 int rays_hip_trace_deposition_device(const rays_params_t* p, int nray, const double* d_rvec0,
                                      const double* d_rindex_vec0, const double* d_initial_ray_power, int which,
                                      int n_bins, int32_t* d_npoints, int32_t* d_stop_code,
@@ -391,6 +391,53 @@ int rays_hip_trace_deposition(const rays_params_t* p, int nray, const double* rv
                               double* profile, double* elapsed_s /* may be NULL */);
 /* Name of the kernel the fused entries launch for a fan of nray rays ("" when p is refused or has no such kernel). */
 const char* rays_hip_deposition_kernel_name_for(const rays_params_t* p, int nray);
+
+/* ---- fused deposition into every profile of the equilibrium, in one trace pass -----------------------------------
+ * The reference post-processor never bins one profile: calculate_deposition_profiles loops over all profiles of the
+ * equilibrium (deposition_profiles_m.f90:228-260) -- Ptotal_psi and Ptotal_rho for axisym_toroid on the eqdsk splines,
+ * Ptotal_x alone for the slab.  These entries take the list.
+ *   n_profiles == 1   rays_hip_trace_deposition[_device] itself: the same kernel (EQ + 96), the same bytes
+ *   n_profiles == 2   ONE launch of the two-profile kernel (EQ + 352 in its name: + the bit 256): the grid value is
+ *                     evaluated once per accepted point -- psiN, then rho(psiN) from it -- and the segment is binned
+ *                     into both rows, with the post-processor's statements.  Each work / profile is bit for bit what
+ *                     the single-profile entry gives for that record; the two bin counts are independent.
+ * Device form: asynchronous on hip_stream; `profiles` is a HOST array of records that hold DEVICE pointers.  Each work
+ * (required, [n_bins][nray] bin-major) is zeroed by the call; each profile is the ray-ordered sum over its work
+ * continued from its own profile_in (NULL = from zero; profile_in == profile is allowed).  One caller thread per
+ * (device, stream); a 96-byte argument block per stream is kept and released by rays_hip_finalize.  Always the EXACT
+ * kernels.
+ * Host form: blocking, sharded and chained in ray order like rays_hip_trace_deposition; work is the reference's layout
+ * [nray][n_bins] and may be NULL; profile_in must be NULL.  A kept device image is dropped.
+ * Refused by name, before anything is allocated or launched: everything rays_hip_trace_deposition_device refuses, for
+ * each record; n_profiles outside 1..RAYS_DEP_MAX_PROFILES; the same `which` twice; two profiles on a configuration
+ * that has one (the single-profile refusal's message); a null work or profile in the device form; a non-null
+ * profile_in in the host form.
+ * OUT OF SCOPE: more than two profiles, the same profile at two bin counts, a tolerance variant, windows. */
+#define RAYS_DEP_MAX_PROFILES 2
+typedef struct rays_dep_profile {
+  int which, n_bins;          /* RAYS_DEP_PTOTAL_*; 1..RAYS_DEP_MAX_BINS */
+  double* work;               /* device form: [n_bins][nray], required.  host form: [nray][n_bins], may be NULL */
+  const double* profile_in;   /* device form: running sums to continue, may be NULL; host form: must be NULL */
+  double* profile;            /* [n_bins] */
+} rays_dep_profile_t;
+int rays_hip_trace_profiles_device(const rays_params_t* p, int nray, const double* d_rvec0,
+                                   const double* d_rindex_vec0, const double* d_initial_ray_power, int n_profiles,
+                                   const rays_dep_profile_t* profiles /* host array of device pointers */,
+                                   int32_t* d_npoints, int32_t* d_stop_code, double* d_start_ray_vec /* may be NULL */,
+                                   double* d_end_ray_vec, double* d_end_residuals, double* d_max_residuals,
+                                   void* hip_stream);
+int rays_hip_trace_profiles(const rays_params_t* p, int nray, const double* rvec0, const double* rindex_vec0,
+                            const double* initial_ray_power, int n_profiles, const rays_dep_profile_t* profiles,
+                            int32_t* npoints, int32_t* stop_code, double* start_ray_vec /* may be NULL */,
+                            double* end_ray_vec, double* end_residuals, double* max_residuals,
+                            double* elapsed_s /* may be NULL */);
+/* Name of the kernel rays_hip_trace_profiles* launch for n_profiles records ("" when p is refused or has no such
+ * kernel: two profiles on a slab or Solovev configuration). */
+const char* rays_hip_profiles_kernel_name_for(const rays_params_t* p, int nray, int n_profiles);
+/* The profiles of the configuration's equilibrium in the reference's order, as RAYS_DEP_PTOTAL_* in
+ * which[RAYS_DEP_MAX_PROFILES]; returns their number.  Slab: x.  axisym_toroid on the eqdsk splines with a rho table
+ * set: psi, rho; the other two magnetics models, or no rho table: psi.  Solovev (or p refused): 0. */
+int rays_hip_deposition_profile_set(const rays_params_t* p, int* which);
 
 /* ---- windowed tracing: pause rays after n steps, continue from a saved state ---------------------------------------
  * Every entry above runs a ray from its launch point to its end in one launch, so whoever wants trajectories holds

@@ -47,6 +47,7 @@ hipError_t launch_deposition(const DevParams& P, const DepArgs& D, const double*
                              hipStream_t s);
 // (rays_deposition.hip; weak: a library linked without them refuses the fused entries by name)
 __attribute__((weak)) hipError_t launch_dep_trace_args(const DepTraceArgs& T, DepTraceArgs* d_out, hipStream_t s);
+__attribute__((weak)) hipError_t launch_dep2_trace_args(const Dep2TraceArgs& T, Dep2TraceArgs* d_out, hipStream_t s);
 __attribute__((weak)) hipError_t launch_profile_sum(int n_bins, int nray, const double* work, const double* carry,
                                                     double* profile, hipStream_t s);
 struct FanArgs;
@@ -137,12 +138,14 @@ std::atomic<int> g_numerics{initial_numerics()};
 //   Window, WindowSummary
 //              the continuation variant (windowed tracing) of the exact kernel, recording or summary-only: always the
 //              one-ray-per-lane entry, whatever the fan size -- the only one built, and bit-identical to the others
-enum class KernelVariant { Recording, ExactTwin, Summary, Deposit, Window, WindowSummary };
+//   Deposit2   the two-profile variant of the fused deposition kernel (axisym_toroid groups)
+enum class KernelVariant { Recording, ExactTwin, Summary, Deposit, Window, WindowSummary, Deposit2 };
 // The build of rays_inst.hip that holds a variant's kernels under the exact numerics (from Summary on the two
 // enumerations name the same builds in the same order).
 rays::KernelBuild build_of(KernelVariant v) {
   static_assert((int)KernelVariant::Summary == (int)rays::KernelBuild::Summary &&
-                (int)KernelVariant::WindowSummary == (int)rays::KernelBuild::WindowSummary, "KernelVariant | KernelBuild");
+                (int)KernelVariant::WindowSummary == (int)rays::KernelBuild::WindowSummary &&
+                (int)KernelVariant::Deposit2 == (int)rays::KernelBuild::Deposit2, "KernelVariant | KernelBuild");
   return v < KernelVariant::Summary ? rays::KernelBuild::Recording : (rays::KernelBuild)(int)v;
 }
 
@@ -363,6 +366,7 @@ StreamWorkspace g_step_ws;
 // rays_hip_finalize, and a new stream that gets the same handle value takes the block over -- harmless, the block is
 // rewritten on the stream before every launch that reads it.
 StreamWorkspace g_dep_ws;
+StreamWorkspace g_dep2_ws;   // the same for the Dep2TraceArgs block of a two-profile launch (rays_hip_trace_profiles*)
 // Neighbourhood size of that order: every second row of 64 rays is traced first (cfg 5b: 4.05 | 3.26 | 3.34 | 3.42 ms for
 // index order | 2 | 4 | 8; the model of tools/refill_model.py agrees: the more pilots, the better the later half is
 // ordered).  RAYS_HIP_RAY_ORDER=index hands the rays out in index order instead (for A/B measurements; the results
@@ -539,7 +543,7 @@ int rays_hip_finalize(void) {
         if (e) (void)hipEventDestroy(e);
       g_ws[d] = DeviceWorkspace();
     }
-  for (StreamWorkspace* w : {&g_sg_ws, &g_sched_ws, &g_step_ws, &g_dep_ws}) w->release_all();
+  for (StreamWorkspace* w : {&g_sg_ws, &g_sched_ws, &g_step_ws, &g_dep_ws, &g_dep2_ws}) w->release_all();
   for (DeviceTable* t : std::initializer_list<DeviceTable*>{&g_zfun, &g_axi, &g_rho}) t->release_all();
   release_staging();
   release_cached_device_blocks();
@@ -672,6 +676,8 @@ struct TraceExtras {
   int rays_per_run = 0;
   // KernelVariant::Deposit: the device block the kernel reads its binning arguments from
   const rays::DepTraceArgs* dep = nullptr;
+  // KernelVariant::Deposit2: the same for the two-profile kernel
+  const rays::Dep2TraceArgs* dep2 = nullptr;
   // KernelVariant::Window | WindowSummary: the saved ray state and the window's length (rays_trace.hpp:
   // TraceArgs::state); state_init: launch the shape's state_init kernel instead of the trace kernel
   const rays::TraceArgs::State* state = nullptr;
@@ -718,10 +724,13 @@ int launch_trace(const rays_params_t* p, KernelVariant variant, int nray, const 
   A.sched_stride = 0;
   A.set_start_ray_vec(recording ? nullptr : out.sv);
   if (variant == KernelVariant::Deposit) A.set_dep(extra.dep);
+  if (variant == KernelVariant::Deposit2) A.set_dep2(extra.dep2);
   if (window) A.set_state(*extra.state, extra.n_steps);
   const rays::KernelEntry* kernel = find_kernel(*p, nray, variant);
   if (!kernel || (extra.state_init && !kernel->resume))
     return fail(window ? "rays_hip: the continuation kernel of this configuration is not in this build"
+                : variant == KernelVariant::Deposit2
+                    ? "rays_hip: the two-profile deposition kernel of this configuration is not in this build"
                 : variant == KernelVariant::Deposit
                     ? "rays_hip: the fused deposition kernel of this configuration is not in this build"
                     : "rays_hip: the summary-only kernel of this configuration is not in this build");
@@ -1850,6 +1859,193 @@ int rays_hip_trace_deposition(const rays_params_t* p, int nray, const double* rv
     return 0;
   });
   if (rc) return rc;
+  if (elapsed_s)
+    *elapsed_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  return 0;
+}
+
+// ---- fused deposition into every profile of the equilibrium in one pass (include/rays_hip.h) --------------------------
+int rays_hip_deposition_profile_set(const rays_params_t* p, int* which) {
+  if (!p || !which || rays_hip_check_params(p)) return 0;
+  if (p->equilib_model == RAYS_EQ_SLAB) {  // deposition_profiles_m.f90:129-160
+    which[0] = RAYS_DEP_PTOTAL_X;
+    return 1;
+  }
+  if (p->equilib_model != RAYS_EQ_AXISYM) return 0;
+  which[0] = RAYS_DEP_PTOTAL_PSI;  // :162-222: Ptotal_psi, then Ptotal_rho where the equilibrium has rho
+  if (p->axisym.magnetics_model != RAYS_AXI_MAG_EQDSK_SPLINE) return 1;
+  {
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (g_rho.n < 2) return 1;
+  }
+  which[1] = RAYS_DEP_PTOTAL_RHO;
+  return 2;
+}
+
+// What the two entries refuse before anything is allocated or launched: the single-profile entry's checks for each
+// record, then the list's own.
+static int refuse_trace_profiles(const char* who, const rays_params_t* p, int nray, int n_profiles,
+                                 const rays_dep_profile_t* profiles) {
+  const std::string w(who);
+  if (!p) return fail(w + ": null parameter block");
+  if (n_profiles < 1 || n_profiles > RAYS_DEP_MAX_PROFILES)
+    return fail(w + ": n_profiles = " + std::to_string(n_profiles) + " is outside 1.." +
+                std::to_string(RAYS_DEP_MAX_PROFILES) + " (RAYS_DEP_MAX_PROFILES)");
+  if (!profiles) return fail(w + ": null profile list");
+  for (int i = 0; i < n_profiles; i++) {
+    const int rc = refuse_trace_deposition(who, p, nray, profiles[i].which, profiles[i].n_bins);
+    if (rc) return rc;
+  }
+  if (n_profiles == 2) {
+    if (profiles[0].which == profiles[1].which) return fail(w + ": the same profile twice");
+    if (!find_kernel(*p, nray, KernelVariant::Deposit2) || !rays::launch_dep2_trace_args)
+      return fail(w + ": the two-profile deposition kernel of this configuration is not in this build");
+  }
+  return 0;
+}
+
+// zero both work arrays, the Dep2TraceArgs block, the two-profile trace.  Arguments already checked.
+static int trace_profiles_launch(const rays_params_t* p, int nray, const RayInputs& in, const rays_dep_profile_t* pr,
+                                 double* const d_work[2], const SummaryArrays& out, hipStream_t stream) {
+  rays::Dep2TraceArgs T;
+  T.power = in.power;
+  T.rho_grid = nullptr; T.rho_fspl = nullptr; T.n_rho = 0; T.pad_ = 0;
+  for (int i = 0; i < 2; i++) {
+    rays::DepTraceArgs G;  // (the grid limits and the rho table of this record, as the single-profile launch takes them)
+    const int rc = fill_deposition_grid(p, pr[i].which, &G);
+    if (rc) return rc;
+    T.prof[i].which = pr[i].which;
+    T.prof[i].n_bins = pr[i].n_bins;
+    T.prof[i].grid_min = G.grid_min;
+    T.prof[i].grid_max = G.grid_max;
+    T.prof[i].work = d_work[i];
+    if (pr[i].which == RAYS_DEP_PTOTAL_RHO) { T.rho_grid = G.rho_grid; T.rho_fspl = G.rho_fspl; T.n_rho = G.n_rho; }
+  }
+  rays::Dep2TraceArgs* d_T = nullptr;
+  HIP_TRY_AS("hipMalloc (deposition arguments)", g_dep2_ws.get(stream, sizeof(rays::Dep2TraceArgs), (void**)&d_T));
+  for (int i = 0; i < 2; i++)
+    HIP_TRY(hipMemsetAsync(d_work[i], 0, sizeof(double) * (size_t)pr[i].n_bins * (size_t)nray, stream));
+  const hipError_t e = rays::launch_dep2_trace_args(T, d_T, stream);
+  if (e != hipSuccess) return hip_fail(e, "deposition arguments kernel");
+  TraceExtras x;
+  x.dep2 = d_T;
+  return launch_trace(p, KernelVariant::Deposit2, nray, in, {}, out, stream, RAYS_TRACE_NO_ZERO_FILL, x);
+}
+
+int rays_hip_trace_profiles_device(const rays_params_t* p, int nray, const double* d_rvec0, const double* d_rindex_vec0,
+                                   const double* d_initial_ray_power, int n_profiles, const rays_dep_profile_t* profiles,
+                                   int32_t* d_npoints, int32_t* d_stop_code, double* d_start_ray_vec, double* d_end_ray_vec,
+                                   double* d_end_residuals, double* d_max_residuals, void* hip_stream) {
+  const char* who = "rays_hip_trace_profiles_device";
+  int rc = refuse_trace_profiles(who, p, nray, n_profiles, profiles);
+  if (rc) return rc;
+  for (int i = 0; i < n_profiles; i++)
+    if (!profiles[i].work || !profiles[i].profile) return fail(std::string(who) + ": null work or profile");
+  if (n_profiles == 1)
+    return rays_hip_trace_deposition_device(p, nray, d_rvec0, d_rindex_vec0, d_initial_ray_power, profiles[0].which,
+                                            profiles[0].n_bins, d_npoints, d_stop_code, d_start_ray_vec, d_end_ray_vec,
+                                            d_end_residuals, d_max_residuals, profiles[0].work, profiles[0].profile_in,
+                                            profiles[0].profile, hip_stream);
+  const hipStream_t stream = (hipStream_t)hip_stream;
+  if (nray == 0) {  // the sums over no rays: the carried profiles, or zeros
+    for (int i = 0; i < 2; i++) {
+      const size_t bytes = sizeof(double) * (size_t)profiles[i].n_bins;
+      if (!profiles[i].profile_in) HIP_TRY(hipMemsetAsync(profiles[i].profile, 0, bytes, stream));
+      else if (profiles[i].profile_in != profiles[i].profile)
+        HIP_TRY(hipMemcpyAsync(profiles[i].profile, profiles[i].profile_in, bytes, hipMemcpyDeviceToDevice, stream));
+    }
+    return 0;
+  }
+  if (!d_rvec0 || !d_rindex_vec0 || !d_initial_ray_power || !d_npoints || !d_stop_code || !d_end_ray_vec ||
+      !d_end_residuals || !d_max_residuals)
+    return fail(std::string(who) + ": null device pointer");
+  double* const d_work[2] = {profiles[0].work, profiles[1].work};
+  rc = trace_profiles_launch(p, nray, {d_rvec0, d_rindex_vec0, d_initial_ray_power}, profiles, d_work,
+                             {d_npoints, d_stop_code, d_start_ray_vec, d_end_ray_vec, d_end_residuals, d_max_residuals},
+                             stream);
+  if (rc) return rc;
+  for (int i = 0; i < 2; i++) {  // + the ray-ordered sums, each continued from its own carry
+    const hipError_t e = rays::launch_profile_sum(profiles[i].n_bins, nray, profiles[i].work, profiles[i].profile_in,
+                                                  profiles[i].profile, stream);
+    if (e != hipSuccess) return hip_fail(e, "profile sum kernel");
+  }
+  return 0;
+}
+
+const char* rays_hip_profiles_kernel_name_for(const rays_params_t* p, int nray, int n_profiles) {
+  if (!p || n_profiles < 1 || n_profiles > RAYS_DEP_MAX_PROFILES || rays_hip_check_params(p)) return "";
+  const rays::KernelEntry* k = find_kernel(*p, nray, n_profiles == 2 ? KernelVariant::Deposit2 : KernelVariant::Deposit);
+  return k ? k->name : "";
+}
+
+namespace {
+// A block of rays_hip_trace_profiles: both work arrays stay on the device (owned by the block's bufs) until both
+// profiles have been chained in ray order.
+struct ProfilesBlock : RayBlock {
+  using RayBlock::RayBlock;
+  double *d_work[2] = {nullptr, nullptr}, *d_in[2] = {nullptr, nullptr}, *d_out[2] = {nullptr, nullptr};
+};
+}  // namespace
+
+int rays_hip_trace_profiles(const rays_params_t* p, int nray, const double* rvec0, const double* rindex_vec0,
+                            const double* initial_ray_power, int n_profiles, const rays_dep_profile_t* profiles,
+                            int32_t* npoints, int32_t* stop_code, double* start_ray_vec, double* end_ray_vec,
+                            double* end_residuals, double* max_residuals, double* elapsed_s) {
+  const char* who = "rays_hip_trace_profiles";
+  int rc = refuse_trace_profiles(who, p, nray, n_profiles, profiles);
+  if (rc) return rc;
+  for (int i = 0; i < n_profiles; i++) {
+    if (profiles[i].profile_in) return fail(std::string(who) + ": profile_in is for the device form (the host form chains its own blocks)");
+    if (!profiles[i].profile) return fail(std::string(who) + ": null array argument");
+  }
+  if (n_profiles == 1)
+    return rays_hip_trace_deposition(p, nray, rvec0, rindex_vec0, initial_ray_power, profiles[0].which, profiles[0].n_bins,
+                                     npoints, stop_code, start_ray_vec, end_ray_vec, end_residuals, max_residuals,
+                                     profiles[0].work, profiles[0].profile, elapsed_s);
+  if (nray > 0 && (!rvec0 || !rindex_vec0 || !initial_ray_power || !npoints || !stop_code || !end_ray_vec ||
+                   !end_residuals || !max_residuals))
+    return fail(std::string(who) + ": null array argument");
+  std::vector<int> devs;
+  if (call_devices(&devs)) return 3;
+  drop_kept_result();  // the image of an earlier rays_hip_trace (if any) is not this call's result: it goes back
+  const auto t0 = std::chrono::steady_clock::now();
+  const SummaryArrays out = {npoints, stop_code, start_ray_vec, end_ray_vec, end_residuals, max_residuals};
+  std::deque<ProfilesBlock> blk;
+  // every block traced and binned into its two work arrays; the summaries go to the caller's arrays
+  rc = run_blocks(devs, nray, &blk, [&](ProfilesBlock& B) {
+    if (B.n() <= 0) return 0;
+    HIP_TRY_AS("hipSetDevice / hipStreamCreate", B.open());
+    HIP_TRY_AS("hipMalloc (result arrays)", B.d.alloc(B.bufs, (size_t)B.n(), (size_t)p->nv, start_ray_vec != nullptr));
+    for (int i = 0; i < 2; i++) {
+      const size_t nb = (size_t)profiles[i].n_bins;
+      HIP_TRY_AS("hipMalloc(&d_work)", B.bufs.alloc(&B.d_work[i], nb * (size_t)B.n()));
+      HIP_TRY_AS("hipMalloc(&d_in)", B.bufs.alloc(&B.d_in[i], nb));
+      HIP_TRY_AS("hipMalloc(&d_out)", B.bufs.alloc(&B.d_out[i], nb));
+    }
+    HIP_TRY_AS("hipMalloc / hipMemcpyAsync (block inputs)", B.upload({rvec0, rindex_vec0, initial_ray_power}));
+    const int rc_b = trace_profiles_launch(p, B.n(), B.in, profiles, B.d_work, B.d, B.st());
+    if (rc_b) return rc_b;
+    HIP_TRY_AS("hipMemcpyAsync (summaries)", B.download(out, (size_t)p->nv));
+    HIP_TRY(hipStreamSynchronize(B.st()));
+    return 0;
+  });
+  if (rc) return rc;
+  for (int i = 0; i < 2; i++) {  // each profile chained over the blocks in ray order, on this thread
+    const int n_bins = profiles[i].n_bins;
+    const size_t nb = (size_t)n_bins;
+    rc = chain_profiles(blk, n_bins, profiles[i].work, profiles[i].profile,
+                        [&](ProfilesBlock& B, DeviceBuffers&, const double* carry_in, double* carry_out,
+                            const double** d_work_out) {
+      if (carry_in) HIP_TRY(hipMemcpyAsync(B.d_in[i], carry_in, sizeof(double) * nb, hipMemcpyHostToDevice, B.st()));
+      const hipError_t e = rays::launch_profile_sum(n_bins, B.n(), B.d_work[i], carry_in ? B.d_in[i] : nullptr, B.d_out[i], B.st());
+      if (e != hipSuccess) return hip_fail(e, "profile sum kernel");
+      HIP_TRY(hipMemcpyAsync(carry_out, B.d_out[i], sizeof(double) * nb, hipMemcpyDeviceToHost, B.st()));
+      HIP_TRY(hipStreamSynchronize(B.st()));
+      *d_work_out = B.d_work[i];
+      return 0;
+    });
+    if (rc) return rc;
+  }
   if (elapsed_s)
     *elapsed_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   return 0;

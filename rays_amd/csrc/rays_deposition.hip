@@ -57,7 +57,16 @@ profile_sum_kernel(int n_bins, int nray, const double* __restrict__ work, const 
 __global__ void __launch_bounds__(kDepWave) dep_trace_args_kernel(const DepTraceArgs T, DepTraceArgs* out) {
   if (threadIdx.x == 0 && blockIdx.x == 0) *out = T;
 }
+// ... and the Dep2TraceArgs block of a two-profile launch
+__global__ void __launch_bounds__(kDepWave) dep2_trace_args_kernel(const Dep2TraceArgs T, Dep2TraceArgs* out) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) *out = T;
+}
 }  // namespace
+
+hipError_t launch_dep2_trace_args(const Dep2TraceArgs& T, Dep2TraceArgs* d_out, hipStream_t s) {
+  hipLaunchKernelGGL(dep2_trace_args_kernel, dim3(1), dim3(kDepWave), 0, s, T, d_out);
+  return hipGetLastError();
+}
 
 hipError_t launch_dep_trace_args(const DepTraceArgs& T, DepTraceArgs* d_out, hipStream_t s) {
   hipLaunchKernelGGL(dep_trace_args_kernel, dim3(1), dim3(kDepWave), 0, s, T, d_out);

@@ -176,4 +176,71 @@ RAYS_DEV void dep_trace_segment(const DevParams& P, const DepTraceArgs& T, int r
   q_prev = q;
 }
 
+// ---- two profiles in one pass (kEqDeposit2) -----------------------------------------------------------
+// The axisym_toroid post-processor bins every ray twice, on psiN and on rho(psiN) (deposition_profiles_m.f90:228-260).
+// The two-profile variant of a fused trace kernel does both from ONE grid evaluation per accepted point: one q, two
+// x_prev, one q_prev per lane.  Its argument block, written and found like DepTraceArgs:
+struct Dep2Profile {
+  int which, n_bins;       // RAYS_DEP_PTOTAL_PSI | RAYS_DEP_PTOTAL_RHO; 1..RAYS_DEP_MAX_BINS
+  double grid_min, grid_max;
+  double* work;            // [n_bins][nray], zeroed before the launch; ray i owns work[b * nray + i]
+};
+struct Dep2TraceArgs {
+  Dep2Profile prof[2];     // in the caller's order; the two bin counts are independent
+  const double* power;     // initial_ray_power[nray]
+  const double* rho_grid;  // rho(psiN) spline
+  const double* rho_fspl;
+  int n_rho, pad_;
+};
+static_assert(sizeof(Dep2Profile) == 32 && sizeof(Dep2TraceArgs) == 96, "Dep2TraceArgs: two records + the shared part");
+
+// psiN and rho(psiN) of a ray point from one evaluation: dep_grid_value's statements, so each has dep_grid_value's bits
+RAYS_DEV void dep2_grid_values(const DevParams& P, const Dep2TraceArgs& T, const double* v, double& psiN, double& rho) {
+  const double x = v[0], y = v[1], z = v[2];
+  const double r = sqrt(x * x + y * y);
+  double f6[6];
+  if (P.a_mag_model == RAYS_AXI_MAG_SOLOVEV) {
+    const double psi = P.half_bp0 * (sq(r * z / P.rk) + sq(r * r - P.rmaj2) / P.rmaj2 / 4.);
+    psiN = psi / P.psiB;
+  } else if (P.a_mag_model == RAYS_AXI_MAG_EQDSK_LIN) {
+    psiN = eqlin_getpsi(P, r, z) / P.a_psiB;
+  } else {
+    spl2_fpp(P, r, z, f6);
+    psiN = f6[0] / P.a_psiB;
+  }
+  double drho;
+  spl1_fp(T.rho_grid, T.rho_fspl, T.n_rho, psiN, rho, drho);
+}
+// the two grid values, in the records' order, and the absorbed power of the ODE vector v of ray `ray`
+RAYS_DEV void dep2_trace_point(const DevParams& P, const Dep2TraceArgs& T, int ray, const double* v, double& xa,
+                               double& xb, double& q) {
+  double psiN, rho;
+  dep2_grid_values(P, T, v, psiN, rho);
+  xa = T.prof[0].which == 0 ? psiN : rho;
+  xb = T.prof[1].which == 0 ? psiN : rho;
+  q = v[7] * T.power[ray];  // ray_vec(8)*initial_ray_power
+}
+// point 1 of ray `ray`: where its first segment starts on either grid
+RAYS_DEV void dep2_trace_first(const DevParams& P, const Dep2TraceArgs& T, int ray, const double* v, double& xa_prev,
+                               double& xb_prev, double& q_prev) {
+  double xa, xb, q;
+  dep2_trace_point(P, T, ray, v, xa, xb, q);
+  xa_prev = xa;
+  xb_prev = xb;  // (its own grid value: the two grids differ from the first point on)
+  q_prev = q;
+}
+// an accepted point of ray `ray` (of nray): the segment from the ray's previous point into the ray's row of each work
+RAYS_DEV void dep2_trace_segment(const DevParams& P, const Dep2TraceArgs& T, int ray, int nray, const double* v,
+                                 double& xa_prev, double& xb_prev, double& q_prev) {
+  double xa, xb, q;
+  dep2_trace_point(P, T, ray, v, xa, xb, q);
+  deposit_segment(T.prof[0].work + ray, (long long)nray, T.prof[0].n_bins, T.prof[0].grid_min, T.prof[0].grid_max, xa_prev,
+                  q_prev, xa, q);
+  deposit_segment(T.prof[1].work + ray, (long long)nray, T.prof[1].n_bins, T.prof[1].grid_min, T.prof[1].grid_max, xb_prev,
+                  q_prev, xb, q);
+  xa_prev = xa;
+  xb_prev = xb;
+  q_prev = q;
+}
+
 }  // namespace rays

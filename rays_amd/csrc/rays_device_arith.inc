@@ -33,6 +33,12 @@ constexpr int kEqNoTraj = 32;
 // (rays_deposition.hpp: deposit_segment), so the absorbed-power profile exists without the trajectories.  Kernels with
 // the absorbed-power row only; own translation units (Makefile: dep_*.o), exact arithmetic only.
 constexpr int kEqDeposit = 64;
+// Two-profile variant of a fused deposition kernel (only together with kEqNoTraj | kEqDeposit, on axisym_toroid;
+// DESIGN.md 4.9.1): every accepted point is binned into two rows, Ptotal_psi and Ptotal_rho, from one grid evaluation
+// (rays_deposition.hpp: Dep2TraceArgs).  Own translation units (Makefile: dep2_*.o): EQ + 352 in the kernel names.
+constexpr int kEqDeposit2 = 256;
+template <int EQ>
+inline constexpr bool kIsDeposit2 = (EQ & kEqDeposit2) != 0;
 // Continuation variant of a one-ray-per-lane trace kernel (windowed tracing; DESIGN.md 4.10): a ray starts from a saved
 // state instead of its launch point, is paused into that state after the launch's n_steps recorded steps, and its
 // points go to a window slab of n_steps points per ray (rays_trace.hpp: TraceArgs::state).  With kEqNoTraj: the same

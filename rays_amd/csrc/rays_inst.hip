@@ -9,6 +9,8 @@
 //   summary-only kernel that also bins every accepted point) of a slab or axisym_toroid group.  The same shape lists,
 //   cut down to the entries with the absorbed-power row (nv = 8 | 13; 8 + NS | 13 + NS in the MS groups) and to the
 //   one-ray-per-lane kernels: a damped configuration is traced fused exactly when it is traced at all.
+//   ... -DRAYS_INST_DEPOSIT2=1 on top of those two: the two-profile variant (rays_device_arith.inc: kEqDeposit2; both
+//   axisym_toroid profiles from one grid evaluation per point) of an axisym_toroid group, with the fused variant's lists.
 //   -DRAYS_INST_CONTINUE=1 [-DRAYS_INST_NOTRAJ=1]: the continuation variant (rays_device_arith.inc: kEqContinue;
 //   windowed tracing) of an exact group, recording or summary-only.  The same shape lists, cut down to the
 //   one-ray-per-lane kernels: a configuration is continued exactly when it is traced at all.  The recording objects
@@ -56,6 +58,12 @@
 #if RAYS_INST_DEPOSIT && !(RAYS_INST_NOTRAJ && (RAYS_INST_EQ == 0 || RAYS_INST_EQ == 2))
 #error "the fused deposition variant is a summary-only kernel of the slab or axisym_toroid groups"
 #endif
+#ifndef RAYS_INST_DEPOSIT2
+#define RAYS_INST_DEPOSIT2 0
+#endif
+#if RAYS_INST_DEPOSIT2 && !(RAYS_INST_DEPOSIT && RAYS_INST_EQ == 2)
+#error "the two-profile variant is a fused deposition kernel of the axisym_toroid groups"
+#endif
 #if RAYS_INST_TOL && !(defined(RAYS_TOL_FLAVOUR) && RAYS_INST_SOLVER == 0 && RAYS_INST_DERIV == 0 && RAYS_INST_MS == 0)
 #error "the tolerance flavour exists for the cold RK4 kernels only, compiled with -DRAYS_TOL_FLAVOUR"
 #endif
@@ -75,7 +83,8 @@ namespace {
 constexpr int EQ = RAYS_INST_EQT;
 static_assert(EQ == (RAYS_INST_EQ | (RAYS_INST_UE ? kEqUnitExp : 0) | (RAYS_INST_MS ? kEqMultiSpec : 0) |
                      (RAYS_INST_TOL ? kEqTol : 0) | (RAYS_INST_NOTRAJ ? kEqNoTraj : 0) |
-                     (RAYS_INST_DEPOSIT ? kEqDeposit : 0) | (RAYS_INST_CONTINUE ? kEqContinue : 0)), "EQ encoding");
+                     (RAYS_INST_DEPOSIT ? kEqDeposit : 0) | (RAYS_INST_CONTINUE ? kEqContinue : 0) |
+                     (RAYS_INST_DEPOSIT2 ? kEqDeposit2 : 0)), "EQ encoding");
 constexpr int DERIV = RAYS_INST_DERIV;
 
 template <int NS, int NV, int OCC = 1>
@@ -255,6 +264,7 @@ extern "C" int RAYS_CAT(rays_debug_sg_profile, RAYS_INST_SOLVER, RAYS_INST_EQ, R
 
 namespace {
 constexpr KernelBuild kBuild = RAYS_INST_TOL        ? KernelBuild::Tolerance
+                               : RAYS_INST_DEPOSIT2 ? KernelBuild::Deposit2
                                : RAYS_INST_DEPOSIT  ? KernelBuild::Deposit
                                : RAYS_INST_CONTINUE ? (RAYS_INST_NOTRAJ ? KernelBuild::WindowSummary : KernelBuild::Window)
                                : RAYS_INST_NOTRAJ   ? KernelBuild::Summary

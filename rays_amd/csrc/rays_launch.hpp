@@ -39,8 +39,9 @@ struct KernelEntry {
 //   Deposit        fused deposition: the summary-only kernel that also bins every accepted point
 //   Window, WindowSummary
 //                  the continuation kernels of windowed tracing, recording and summary-only
-enum class KernelBuild { Recording, Tolerance, Summary, Deposit, Window, WindowSummary };
-constexpr int kKernelBuilds = 6;
+//   Deposit2       fused deposition into two profiles (axisym_toroid: Ptotal_psi and Ptotal_rho in one pass)
+enum class KernelBuild { Recording, Tolerance, Summary, Deposit, Window, WindowSummary, Deposit2 };
+constexpr int kKernelBuilds = 7;
 
 // The entry list of one object of rays_inst.hip.  Every object holds one and hands it to register_kernel_group from a
 // static initialiser; rays_capi.hip looks kernels up in the list of what registered, so a group that is not linked in is

@@ -101,6 +101,9 @@
   static_assert(!kDeposit || (kNoTraj && RayVec<(EQ & kEqMultiSpec) != 0, NS, NV>::DAMP),
                 "the fused deposition variant: a summary-only kernel with the absorbed-power row");
   [[maybe_unused]] double dep_x_prev = 0., dep_q_prev = 0.;
+  // two-profile variant (kEqDeposit2): the second profile's grid value of that point; q is shared
+  static_assert(!kIsDeposit2<EQ> || (kDeposit && (EQ & 3) == 2), "the two-profile variant: a fused axisym_toroid kernel");
+  [[maybe_unused]] double dep_x2_prev = 0.;
   extern __shared__ double lds[];
   Window win;
   if constexpr (kWindow) win.attach(lds, threadIdx.x);
@@ -325,7 +328,8 @@
             if (start)
 #pragma unroll
               for (int i = 0; i < NV; i++) start[(long long)ray * NV + i] = v[i];
-            if constexpr (kDeposit) dep_trace_point(P, *A.dep(), ray, v, dep_x_prev, dep_q_prev);
+            if constexpr (kIsDeposit2<EQ>) dep2_trace_first(P, *A.dep2(), ray, v, dep_x_prev, dep_x2_prev, dep_q_prev);
+            else if constexpr (kDeposit) dep_trace_point(P, *A.dep(), ray, v, dep_x_prev, dep_q_prev);
           } else if constexpr (kWindow) {
             int pv, pr;
             Window::phases(A_hot, ray, npt, pv, pr);
@@ -361,7 +365,10 @@
             nstep = nstep + 1;
             if constexpr (kNoTraj) {
               // the point is counted, not stored -- and binned by the fused deposition variant
-              if constexpr (kDeposit) {
+              if constexpr (kIsDeposit2<EQ>) {
+                const TraceArgs& A = cold_args(A_hot);
+                dep2_trace_segment(P, *A.dep2(), ray, A.nray, v, dep_x_prev, dep_x2_prev, dep_q_prev);
+              } else if constexpr (kDeposit) {
                 const TraceArgs& A = cold_args(A_hot);
                 dep_trace_segment(P, *A.dep(), ray, A.nray, v, dep_x_prev, dep_q_prev);
               }

@@ -484,6 +484,9 @@ sg_trace_kernel(const DevParams P_kernarg, const TraceArgs A_hot) {
   static_assert(!kDeposit || ((EQ & kEqNoTraj) != 0 && RayVec<(EQ & kEqMultiSpec) != 0, NS, NV>::DAMP),
                 "the fused deposition variant: a summary-only kernel with the absorbed-power row");
   [[maybe_unused]] double dep_x_prev = 0., dep_q_prev = 0.;
+  // two-profile variant (kEqDeposit2): the second profile's grid value of that point; q is shared
+  static_assert(!kIsDeposit2<EQ> || (kDeposit && (EQ & 3) == 2), "the two-profile variant: a fused axisym_toroid kernel");
+  [[maybe_unused]] double dep_x2_prev = 0.;
   // continuation variant (kEqContinue): rays start from the saved state and are paused into it after the
   // launch's n_steps recorded steps; points go into the window slab [nray][n_steps]
   constexpr bool kContinue = (EQ & kEqContinue) != 0;
@@ -648,7 +651,8 @@ sg_trace_kernel(const DevParams P_kernarg, const TraceArgs A_hot) {
             if (start)
 #pragma unroll
               for (int i = 0; i < NV; i++) start[(long long)ray * NV + i] = yy[i];
-            if constexpr (kDeposit) dep_trace_point(P, *A.dep(), ray, yy, dep_x_prev, dep_q_prev);
+            if constexpr (kIsDeposit2<EQ>) dep2_trace_first(P, *A.dep2(), ray, yy, dep_x_prev, dep_x2_prev, dep_q_prev);
+            else if constexpr (kDeposit) dep_trace_point(P, *A.dep(), ray, yy, dep_x_prev, dep_q_prev);
           } else {
             record_point<NV>(cold_args(A_hot), (long long)ray * npt, yy, 0.);
           }
@@ -679,7 +683,10 @@ sg_trace_kernel(const DevParams P_kernarg, const TraceArgs A_hot) {
                 record_point<NV>(A, (long long)ray * A.win_steps() + (nstep - win0 - 1), yy, resid);
               }
             } else if constexpr ((EQ & kEqNoTraj) == 0) record_point<NV>(cold_args(A_hot), (long long)ray * npt + nstep, yy, resid);
-            if constexpr (kDeposit) {  // the point is binned where the recording kernels store it
+            if constexpr (kIsDeposit2<EQ>) {  // the point is binned where the recording kernels store it
+              const TraceArgs& A = cold_args(A_hot);
+              dep2_trace_segment(P, *A.dep2(), ray, A.nray, yy, dep_x_prev, dep_x2_prev, dep_q_prev);
+            } else if constexpr (kDeposit) {
               const TraceArgs& A = cold_args(A_hot);
               dep_trace_segment(P, *A.dep(), ray, A.nray, yy, dep_x_prev, dep_q_prev);
             }

@@ -79,6 +79,11 @@ struct TraceArgs {
   __host__ __device__ void set_dep(const DepTraceArgs* d) {
     ray_vec = reinterpret_cast<double*>(const_cast<DepTraceArgs*>(d));
   }
+  // ... or, for the two-profile kernels (kEqDeposit2), of the launch's Dep2TraceArgs block
+  __host__ __device__ const Dep2TraceArgs* dep2() const { return reinterpret_cast<const Dep2TraceArgs*>(ray_vec); }
+  __host__ __device__ void set_dep2(const Dep2TraceArgs* d) {
+    ray_vec = reinterpret_cast<double*>(const_cast<Dep2TraceArgs*>(d));
+  }
   // Continuation kernels (kEqContinue) and the state_init kernel: the saved ray state (include/rays_hip.h:
   // rays_ray_state_t) travels in slots these kernels have no other use for -- they write no per-ray summary (the state
   // holds it), take no caller's v0 / s0 and run no fused scan -- so TraceArgs is not lengthened for it either:

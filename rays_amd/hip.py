@@ -37,6 +37,8 @@ EXPORTED_SYMBOLS = (
     "rays_hip_trace_summary_device", "rays_hip_scan_summary_device", "rays_hip_trace_summary",
     "rays_hip_summary_kernel_name_for",
     "rays_hip_trace_deposition_device", "rays_hip_trace_deposition", "rays_hip_deposition_kernel_name_for",
+    "rays_hip_trace_profiles_device", "rays_hip_trace_profiles", "rays_hip_profiles_kernel_name_for",
+    "rays_hip_deposition_profile_set",
     "rays_hip_rk4_loop_for",
     "rays_hip_state_init_device", "rays_hip_trace_window_device", "rays_hip_state_summary_device",
     "rays_hip_window_kernel_name_for", "rays_hip_trace_windowed",
@@ -56,6 +58,15 @@ class RayStateStruct(C.Structure):
 
 
 STATE_REFUSED = 1   # RAYS_STATE_REFUSED
+
+
+class DepProfileStruct(C.Structure):
+    """rays_dep_profile_t (include/rays_hip.h): one record of rays_hip_trace_profiles[_device]"""
+    _fields_ = [("which", C.c_int), ("n_bins", C.c_int), ("work", C.c_void_p), ("profile_in", C.c_void_p),
+                ("profile", C.c_void_p)]
+
+
+DEP_MAX_PROFILES = 2   # RAYS_DEP_MAX_PROFILES
 
 
 def load():
@@ -136,6 +147,17 @@ def load():
                                                   dp]
         lib.rays_hip_deposition_kernel_name_for.restype = C.c_char_p
         lib.rays_hip_deposition_kernel_name_for.argtypes = [pp, C.c_int]
+    # (likewise the several-profiles entries -- tools/fused_profiles_bench.py)
+    if hasattr(lib, "rays_hip_trace_profiles_device"):
+        rp = C.POINTER(DepProfileStruct)
+        lib.rays_hip_trace_profiles_device.restype = C.c_int
+        lib.rays_hip_trace_profiles_device.argtypes = [pp, C.c_int, vp, vp, vp, C.c_int, rp, vp, vp, vp, vp, vp, vp, vp]
+        lib.rays_hip_trace_profiles.restype = C.c_int
+        lib.rays_hip_trace_profiles.argtypes = [pp, C.c_int, dp, dp, dp, C.c_int, rp, ip, ip, dp, dp, dp, dp, dp]
+        lib.rays_hip_profiles_kernel_name_for.restype = C.c_char_p
+        lib.rays_hip_profiles_kernel_name_for.argtypes = [pp, C.c_int, C.c_int]
+        lib.rays_hip_deposition_profile_set.restype = C.c_int
+        lib.rays_hip_deposition_profile_set.argtypes = [pp, C.POINTER(C.c_int)]
     # (likewise the step-loop query -- an A/B run times the parent commit's library next to this one)
     if hasattr(lib, "rays_hip_rk4_loop_for"):
         lib.rays_hip_rk4_loop_for.restype = C.c_int
@@ -702,6 +724,80 @@ def trace_deposition_host(p: RaysParams, rvec0, rindex_vec0, initial_ray_power, 
                                        _dp(out["end_ray_vec"]), _dp(out["end_residuals"]), _dp(out["max_residuals"]),
                                        _dp(out["work"]) if want_work else None, _dp(out["profile"]), C.byref(el))
     _check(rc, "rays_hip_trace_deposition")
+    out["elapsed_s"] = el.value
+    return out
+
+
+def deposition_profile_set(p: RaysParams) -> tuple:
+    """rays_hip_deposition_profile_set: the names of the profiles of p's equilibrium, in the reference's order
+    (calculate_deposition_profiles loops over all of them)."""
+    ensure_tables(p)
+    which = (C.c_int * DEP_MAX_PROFILES)()
+    n = load().rays_hip_deposition_profile_set(C.byref(p), which)
+    names = {v: k for k, v in DEP_PROFILES.items()}
+    return tuple(names[which[i]] for i in range(n))
+
+
+def profiles_kernel_name(p: RaysParams, nray: int, n_profiles: int) -> str:
+    """Kernel rays_hip_trace_profiles* would launch for n_profiles records; "" where there is none (two profiles on a
+    slab or Solovev configuration)."""
+    return load().rays_hip_profiles_kernel_name_for(C.byref(p), int(nray), int(n_profiles)).decode()
+
+
+def _profile_records(records):
+    """[(which, n_bins, work, profile_in, profile), ...] (addresses as ints or None) -> the C array"""
+    arr = (DepProfileStruct * max(len(records), 1))()
+    for r, (which, n_bins, work, profile_in, profile) in zip(arr, records):
+        r.which, r.n_bins = _dep_which(which), int(n_bins)
+        r.work, r.profile_in, r.profile = work or None, profile_in or None, profile or None
+    return arr
+
+
+def trace_profiles_device(p: RaysParams, nray: int, d_rvec0: int, d_rindex_vec0: int, d_power: int, records,
+                          d_npoints: int, d_stop_code: int, d_start_ray_vec: int, d_end_ray_vec: int,
+                          d_end_residuals: int, d_max_residuals: int, stream: int = 0):
+    """rays_hip_trace_profiles_device: raw device pointers (ints); records = [(which, n_bins, d_work, d_profile_in,
+    d_profile), ...], one or two.  Asynchronous on `stream`; every work is zeroed by the call."""
+    arr = _profile_records(records)
+    ensure_tables(p)
+    rc = load().rays_hip_trace_profiles_device(
+        C.byref(p), int(nray), d_rvec0 or None, d_rindex_vec0 or None, d_power or None, len(records), arr,
+        d_npoints or None, d_stop_code or None, d_start_ray_vec or None, d_end_ray_vec or None, d_end_residuals or None,
+        d_max_residuals or None, stream or None)
+    _check(rc, "rays_hip_trace_profiles_device")
+
+
+def trace_profiles_host(p: RaysParams, rvec0, rindex_vec0, initial_ray_power, profiles, ngpu: int = 0,
+                        want_work: bool = True) -> dict:
+    """rays_hip_trace_profiles: host numpy arrays in; profiles = [(which, n_bins), ...].  Out: the per-ray summaries,
+    and `works` / `profiles` as lists in the order asked (work[nray][n_bins]; None without want_work)."""
+    lib = load()
+    rvec0 = np.ascontiguousarray(rvec0, dtype=np.float64)
+    rindex_vec0 = np.ascontiguousarray(rindex_vec0, dtype=np.float64)
+    power = np.ascontiguousarray(initial_ray_power, dtype=np.float64)
+    nray, nv = len(rvec0), p.nv
+    if power.shape != (nray,):
+        raise ValueError("trace_profiles_host: initial_ray_power must hold one weight per ray")
+    if ngpu is not None and lib.rays_hip_init(int(ngpu)) < 0:
+        raise RaysHipError("rays_hip_init: " + last_error())
+    ensure_tables(p)
+    out = dict(npoints=np.zeros(nray, dtype=np.int32), stop_code=np.zeros(nray, dtype=np.int32),
+               start_ray_vec=np.zeros((nray, nv)), end_ray_vec=np.zeros((nray, nv)), end_residuals=np.zeros(nray),
+               max_residuals=np.zeros(nray), works=[], profiles=[])
+    records = []
+    for which, n_bins in profiles:
+        nb = max(int(n_bins), 0)
+        out["works"].append(np.zeros((nray, nb)) if want_work else None)
+        out["profiles"].append(np.zeros(nb))
+        records.append((which, n_bins, out["works"][-1].ctypes.data if want_work else None, None,
+                        out["profiles"][-1].ctypes.data))
+    arr = _profile_records(records)
+    el = C.c_double(0.0)
+    rc = lib.rays_hip_trace_profiles(C.byref(p), nray, _dp(rvec0), _dp(rindex_vec0), _dp(power), len(records), arr,
+                                     _ip(out["npoints"]), _ip(out["stop_code"]), _dp(out["start_ray_vec"]),
+                                     _dp(out["end_ray_vec"]), _dp(out["end_residuals"]), _dp(out["max_residuals"]),
+                                     C.byref(el))
+    _check(rc, "rays_hip_trace_profiles")
     out["elapsed_s"] = el.value
     return out
 

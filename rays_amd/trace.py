@@ -219,6 +219,48 @@ def _deposition_spec(deposition, with_power: bool):
     return deposition
 
 
+def _is_profile_list(deposition) -> bool:
+    """deposition=[(which, n_bins), ...] or "all": the several-profiles spelling (one trace pass, rays_hip_trace_profiles*)."""
+    if isinstance(deposition, str):
+        return True
+    return isinstance(deposition, list) and (not deposition or isinstance(deposition[0], (tuple, list)))
+
+
+def _profile_list(params: RaysParams, deposition, n_bins, who: str):
+    """[(which, n_bins), ...] of the several-profiles spelling, checked: one or two different profiles of the
+    configuration's equilibrium.  "all" with n_bins=n: the equilibrium's whole set in the reference's order
+    (hip.deposition_profile_set), n bins each."""
+    if isinstance(deposition, str):
+        if deposition != "all":
+            raise ValueError(f'{who}: deposition={deposition!r}: a string can only be "all" (with n_bins=n)')
+        if n_bins is None:
+            raise ValueError(f'{who}: deposition="all" needs n_bins=n')
+        names = hip.deposition_profile_set(params)
+        if not names:
+            raise ValueError(f'{who}: deposition="all": this equilibrium has no deposition profile')
+        return [(w, int(n_bins)) for w in names]
+    if n_bins is not None:
+        raise ValueError(f'{who}: n_bins=... goes with deposition="all" only; a list carries its own bin counts')
+    specs = []
+    for d in deposition:
+        if not isinstance(d, (tuple, list)) or len(d) != 2:
+            raise ValueError(f"{who}: deposition=[(which, n_bins), ...] takes pairs; the powers go in "
+                             "ray_power= (DeviceTrace) or come from ray_pwr_wt (RaysRun) -- the tuple and the list "
+                             "spelling do not mix")
+        which, nb = _deposition_spec(d, False)
+        specs.append((which, int(nb)))
+    if not 1 <= len(specs) <= hip.DEP_MAX_PROFILES:
+        raise ValueError(f"{who}: deposition=[...] takes 1..{hip.DEP_MAX_PROFILES} profiles, not {len(specs)}")
+    if len({w for w, _ in specs}) != len(specs):
+        raise ValueError(f"{who}: deposition=[...] names the profile {specs[0][0]!r} twice")
+    slab = int(params.equilib_model) == 0
+    for w, _ in specs:
+        if (w == "Ptotal_x") != slab:
+            raise ValueError(f"{who}: deposition profile {w!r} does not exist for this equilib_model (slab: Ptotal_x; "
+                             "axisym_toroid: Ptotal_psi, Ptotal_rho)")
+    return specs
+
+
 def load_axisym_tables(namelist_path: str, nml: Dict[str, Dict[str, Any]]) -> Optional[Dict[str, Any]]:
     """Host-built spline tables of an eqdsk equilibrium: `<eqdsk_file_name>.tables.npz` next to the
     namelist (None for the analytic equilibria)."""
@@ -281,14 +323,20 @@ class RaysRun:
         return len(self.rvec0)
 
     def trace_rays(self, ngpu: int = 1, trajectories: bool = True, deposition=None, want_work: bool = False,
-                   window: Optional[int] = None):
+                   window: Optional[int] = None, n_bins: Optional[int] = None):
         """window=n_steps: the same RayResults, traced in windows of n_steps on one device (hip.trace_windowed_host):
         the device holds the ray state and two window slabs, and each window's points reach the host arrays through
         pinned memory while the next window runs -- the way to trace a fan whose trajectories exceed the card.
         trajectories=False: the summary-only trace (RaySummaries; no trajectory array on the device or the host).
         trajectories=False, deposition=(which, n_bins): the fused trace + deposition (RayDeposition: the summaries and
         the profile `which` of the launcher's power weights ray_pwr_wt -- initial_ray_power of the run's results -- with
-        work[nray][n_bins] if want_work)."""
+        work[nray][n_bins] if want_work).
+        trajectories=False, deposition=[(which, n_bins), ...]: one or two profiles from ONE trace pass
+        (rays_hip_trace_profiles): a list of RayDeposition that share one RaySummaries.  deposition="all", n_bins=n: the
+        whole set of the equilibrium in the reference's order (calculate_deposition_profiles bins every one), whose
+        profile_records go straight into results.write_deposition_profiles_LD / _NC."""
+        if n_bins is not None and not isinstance(deposition, str):
+            raise ValueError('RaysRun.trace_rays: n_bins=... goes with deposition="all" only')
         if window is not None:
             if deposition is not None or not trajectories:
                 raise ValueError("RaysRun.trace_rays: window=... assembles the full trajectories; it goes with neither "
@@ -298,11 +346,20 @@ class RaysRun:
             if trajectories:
                 raise ValueError("RaysRun.trace_rays: deposition=... is the fused trace without trajectories -- pass "
                                  "trajectories=False (or bin a full trace with hip.deposition_host)")
-            which, n_bins = _deposition_spec(deposition, False)
+            specs = _profile_list(self.params, deposition, n_bins, "RaysRun.trace_rays") if _is_profile_list(deposition) else None
+            if specs is None:
+                which, n_bins = _deposition_spec(deposition, False)
             if self.ray_pwr_wt is None:
                 raise ValueError("RaysRun.trace_rays: deposition=... needs the launcher's power weights (ray_pwr_wt); this "
                                  "run has none")
             power = np.asarray(self.ray_pwr_wt, dtype=np.float64)
+            if specs is not None:
+                out = hip.trace_profiles_host(self.params, self.rvec0, self.rindex_vec0, power, specs, ngpu=ngpu,
+                                              want_work=want_work)
+                works, profs = out.pop("works"), out.pop("profiles")
+                summ = RaySummaries(**out)
+                return [RayDeposition(summ, w, nb, *deposition_grid_limits(self.params, w), prof, work)
+                        for (w, nb), prof, work in zip(specs, profs, works)]
             out = hip.trace_deposition_host(self.params, self.rvec0, self.rindex_vec0, power, which, int(n_bins),
                                             ngpu=ngpu, want_work=want_work)
             work, prof = out.pop("work"), out.pop("profile")
@@ -345,10 +402,15 @@ class DeviceTrace:
     it each ray recorded in the last window.  launch() puts every ray at its launch point (start_ray_vec = point 1,
     residual 0); advance() runs one window and returns (ray_vec_win, residual_win, npoints_win) -- the object's own
     tensors, overwritten by the next advance(); results() gives the state's RaySummaries, rays under way included as
-    they stand.  state= continues a RayState saved earlier instead of allocating one."""
+    they stand.  state= continues a RayState saved earlier instead of allocating one.
+    trajectories=False, deposition=[(which, n_bins), ...], ray_power=power: one or two profiles from ONE trace pass
+    (rays_hip_trace_profiles_device) -- .works, .profiles and .deposition are lists in the order asked, profile_in a
+    list of tensors / None of the same length, and results() returns a list of RayDeposition that share one
+    RaySummaries.  deposition="all", n_bins=n: the equilibrium's whole set (hip.deposition_profile_set)."""
 
     def __init__(self, params: RaysParams, rvec0, rindex_vec0, device=None, trajectories: bool = True, deposition=None,
-                 profile_in=None, window: Optional[int] = None, state: Optional[RayState] = None):
+                 profile_in=None, window: Optional[int] = None, state: Optional[RayState] = None, ray_power=None,
+                 n_bins: Optional[int] = None):
         import torch
 
         self.torch = torch
@@ -360,7 +422,24 @@ class DeviceTrace:
         self.deposition = None
         self.work = self.profile = self.power = None
         self.profile_in = profile_in
-        if deposition is not None:
+        self.works = self.profiles = None
+        self.profile_list = deposition is not None and _is_profile_list(deposition)
+        if self.profile_list:
+            if self.trajectories:
+                raise ValueError("DeviceTrace: deposition=... is the fused trace without trajectories -- pass "
+                                 "trajectories=False (or bin a full trace with hip.deposition_device)")
+            self.deposition = _profile_list(params, deposition, n_bins, "DeviceTrace")
+            if ray_power is None:
+                raise ValueError("DeviceTrace: deposition=[...] needs ray_power= (one weight per ray)")
+            if len(ray_power) != self.nray:
+                raise ValueError("DeviceTrace: ray_power must hold one weight per ray")
+            if profile_in is not None and (not isinstance(profile_in, (list, tuple)) or len(profile_in) != len(self.deposition)):
+                raise ValueError("DeviceTrace: profile_in of deposition=[...] is a list with one entry (a tensor or None) "
+                                 "per profile")
+        elif ray_power is not None or n_bins is not None:
+            raise ValueError("DeviceTrace: ray_power= / n_bins= go with the list spelling deposition=[(which, n_bins), ...] "
+                             'or "all"; the tuple spelling carries its power: deposition=(which, n_bins, power)')
+        elif deposition is not None:
             if self.trajectories:
                 raise ValueError("DeviceTrace: deposition=... is the fused trace without trajectories -- pass "
                                  "trajectories=False (or bin a full trace with hip.deposition_device)")
@@ -405,7 +484,14 @@ class DeviceTrace:
             self.end_ray_vec = torch.zeros((self.nray, nv), dtype=f64, device=self.device)
             self.end_residuals = torch.zeros(self.nray, dtype=f64, device=self.device)
             self.max_residuals = torch.zeros(self.nray, dtype=f64, device=self.device)
-            if self.deposition is not None:
+            if self.profile_list:
+                pw = ray_power
+                self.power = (pw.to(device=self.device, dtype=f64).contiguous() if torch.is_tensor(pw)
+                              else torch.as_tensor(np.ascontiguousarray(pw, dtype=np.float64)).to(self.device))
+                self.works = [torch.zeros((max(nb, 0), self.nray), dtype=f64, device=self.device)
+                              for _, nb in self.deposition]
+                self.profiles = [torch.zeros(max(nb, 0), dtype=f64, device=self.device) for _, nb in self.deposition]
+            elif self.deposition is not None:
                 nb = max(self.deposition[1], 0)
                 pw = deposition[2]
                 self.power = (pw.to(device=self.device, dtype=f64).contiguous() if torch.is_tensor(pw)
@@ -419,6 +505,15 @@ class DeviceTrace:
         if self.window is not None:
             hip.state_init_device(self.params, self.nray, self.rvec0.data_ptr(), self.rindex_vec0.data_ptr(), self.state,
                                   self.start_ray_vec.data_ptr(), stream=stream)
+            return
+        if self.profile_list:
+            pin = self.profile_in or [None] * len(self.deposition)
+            records = [(w, nb, work.data_ptr(), None if c is None else c.data_ptr(), prof.data_ptr())
+                       for (w, nb), work, c, prof in zip(self.deposition, self.works, pin, self.profiles)]
+            hip.trace_profiles_device(self.params, self.nray, self.rvec0.data_ptr(), self.rindex_vec0.data_ptr(),
+                                      self.power.data_ptr(), records, self.npoints.data_ptr(), self.stop_code.data_ptr(),
+                                      self.start_ray_vec.data_ptr(), self.end_ray_vec.data_ptr(),
+                                      self.end_residuals.data_ptr(), self.max_residuals.data_ptr(), stream=stream)
             return
         if self.deposition is not None:
             hip.trace_deposition_device(self.params, self.nray, self.rvec0.data_ptr(), self.rindex_vec0.data_ptr(),
@@ -519,6 +614,12 @@ class DeviceTrace:
         if self.window is not None:
             return RaySummaries(c(self.npoints), c(self.stop_code), c(self.start_ray_vec), c(self.end_ray_vec),
                                 c(self.end_residuals), c(self.max_residuals))
+        if self.profile_list:
+            summ = RaySummaries(c(self.npoints), c(self.stop_code), c(self.start_ray_vec), c(self.end_ray_vec),
+                                c(self.end_residuals), c(self.max_residuals))
+            return [RayDeposition(summ, w, nb, *deposition_grid_limits(self.params, w), c(prof),
+                                  np.ascontiguousarray(c(work).T))
+                    for (w, nb), work, prof in zip(self.deposition, self.works, self.profiles)]
         if not self.trajectories:
             return RaySummaries(c(self.npoints), c(self.stop_code), c(self.start_ray_vec), c(self.end_ray_vec),
                                 c(self.end_residuals), c(self.max_residuals))
