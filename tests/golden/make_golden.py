@@ -8,7 +8,7 @@ Only runs where /root/reference was available to build the binary; the committed
 what the tests read.  tests/golden/deposition_binner_cases.npz comes from oracle/_ref/ref_binner (the reference's
 binner_real alone) on the synthetic rays of tests/deposition_cases.py, tests/golden/rhs_state_cases.npz from
 oracle/_ref/ref_states (the reference's right-hand side and one ode_solver step) at the synthetic states of
-tests/rhs_state_cases.py, tests/golden/launch_cases.npz from oracle/_ref/ref_launch (the reference's initialize: its ray
+tests/rhs_state_cases.py (tests/golden/eq_knot_states.npz: the same at its class K), tests/golden/launch_cases.npz from oracle/_ref/ref_launch (the reference's initialize: its ray
 launchers) on the namelists of tests/launch_cases.py.
 
     python tests/golden/make_golden.py [fixture names ...]    (re)generate
@@ -17,9 +17,10 @@ launchers) on the namelists of tests/launch_cases.py.
 
 The host-side spline tables next to an eqdsk file (configs/<file>.geqdsk.tables.npz, read by the Python host) are the
 UNION of what the cases on that file dump (each case's namelist selects its own profile splines: ne_* in one,
-te_* / ti_* in another); overlapping entries must agree bit for bit.  Two files: solovev_65x65.geqdsk (written by
-tools/make_solovev_eqdsk.py) and solovev_129x129.geqdsk (BASELINE config 5's, written by the REFERENCE's own
-solovev_2_eqdsk: oracle/make_cfg5_eqdsk.sh).
+te_* / ti_* in another); overlapping entries must agree bit for bit.  Three files: solovev_65x65.geqdsk (written by
+tools/make_solovev_eqdsk.py), solovev_129x129.geqdsk (BASELINE config 5's) and solovev_49x65.geqdsk (a box whose grid
+spacings are no powers of two; its tables lie in tests/golden/: tables_path), both written by the REFERENCE's own
+solovev_2_eqdsk: oracle/make_cfg5_eqdsk.sh.
 """
 import os
 import shutil
@@ -95,6 +96,10 @@ CASES = [
     # solovev_2_eqdsk (oracle/make_cfg5_eqdsk.sh), splined n, Te and Ti, ECH damping; RK4 and Shampine-Gordon
     ("gold_axisym64_eqdsk129_tspline_damp_rk4", "gold_axisym64_eqdsk129_tspline_damp_rk4.in", list(range(0, 64, 5)), 10, 60),
     ("gold_axisym64_eqdsk129_tspline_damp_sg", "gold_axisym64_eqdsk129_tspline_damp_sg.in", list(range(0, 64, 5)), 0, 0),
+    # the same equilibrium on a box whose grid spacings are no powers of two (0.48..1.56 x -0.74..0.74, 49 x 65 points,
+    # written by the reference's solovev_2_eqdsk: oracle/make_cfg5_eqdsk.sh), n on 14 knots, Te and Ti on 12: the cell
+    # estimate of the spline lookups rounds across grid lines in R too (tests/rhs_state_cases.py: class K); 4 x 4 rays
+    ("gold_axisym16_eqdsk49x65_tspline_damp_rk4", "gold_axisym16_eqdsk49x65_tspline_damp_rk4.in", None, 10, 60),
     ("gold_axisym64_eqlin_damp_rk4", "gold_axisym64_eqlin_damp_rk4.in", list(range(0, 64, 5)), 10, 0),
     ("gold_axisym64_eqlin_tspline_sg_num", "gold_axisym64_eqlin_tspline_sg_num.in", list(range(0, 64, 7)), 0, 0),
     # launchers that take single rays by position and direction (host-side in every build: acos / cos of libm)
@@ -116,11 +121,16 @@ def check_deterministic(cfg):
                  "(the reference races otherwise and the fixture would not be reproducible)")
 
 
-EQDSK_FILES = ("solovev_65x65.geqdsk", "solovev_129x129.geqdsk")
+EQDSK_FILES = ("solovev_65x65.geqdsk", "solovev_129x129.geqdsk", "solovev_49x65.geqdsk")
+
+
+# an eqdsk file that only tests read keeps its host tables with the fixtures: a run on it is handed them
+# (RaysRun.from_namelist(path, axisym_tables=...)) instead of finding them next to the namelist
+TEST_ONLY_EQDSK = ("solovev_49x65.geqdsk",)
 
 
 def tables_path(eqdsk):
-    return os.path.join("configs", eqdsk + ".tables.npz")
+    return os.path.join(os.path.join("tests", "golden") if eqdsk in TEST_ONLY_EQDSK else "configs", eqdsk + ".tables.npz")
 
 
 def eqdsk_of(cfg):
@@ -210,9 +220,25 @@ def rhs_states_fixture(out_root):
     equilibrium returns with an error its eq_point is undefined: such a record keeps its flags and is blanked otherwise
     (tests/refdump.py: blank_undefined)."""
     from tests import rhs_state_cases as rc
+    states_fixture(out_root, RHS_STATES_FIXTURE, rc.all_states(), rc.CASES)
+
+
+KNOT_STATES_FIXTURE = os.path.join("tests", "golden", "eq_knot_states.npz")
+
+
+def knot_states_fixture(out_root):
+    """tests/golden/eq_knot_states.npz: class K of tests/rhs_state_cases.py (points on and beside the grid lines of the
+    equilibrium's spline and bilinear tables, where the cell search of the lookups takes its rare branches) and the same
+    records of the same driver; the same layout as rhs_state_cases.npz."""
+    from tests import rhs_state_cases as rc
+    states_fixture(out_root, KNOT_STATES_FIXTURE, rc.all_knot_states(), rc.K_CASES)
+
+
+def states_fixture(out_root, fixture, states, cases):
+    from tests import rhs_state_cases as rc
     from tests.refdump import blank_undefined, read_states, write_states
     out, total = {}, 0
-    for case, (v, s, label, side) in rc.all_states().items():
+    for case, (v, s, label, side) in states.items():
         cfg = case + ".in"
         check_deterministic(cfg)
         with tempfile.TemporaryDirectory() as d:
@@ -231,10 +257,10 @@ def rhs_states_fixture(out_root):
         out[case + ":s"], out[case + ":label"], out[case + ":side"], out[case + ":geom"] = s, label, side, geom
         out[case + ":probe"], out[case + ":step"] = probe, step
         total += len(v)
-    out["cases"] = np.array(list(rc.CASES))
-    path = os.path.join(out_root, RHS_STATES_FIXTURE)
+    out["cases"] = np.array(list(cases))
+    path = os.path.join(out_root, fixture)
     np.savez_compressed(path, **out)
-    print(f"rhs_state_cases: {total} states of {len(rc.CASES)} cases -> {os.path.getsize(path) / 1e3:.0f} kB")
+    print(f"{os.path.basename(fixture)[:-4]}: {total} states of {len(cases)} cases -> {os.path.getsize(path) / 1e3:.0f} kB")
 
 
 LAUNCH_FIXTURE = os.path.join("tests", "golden", "launch_cases.npz")
@@ -280,6 +306,8 @@ def generate(out_root, only=()):
         binner_fixture(out_root)
     if not only or "rhs_state_cases" in only:
         rhs_states_fixture(out_root)
+    if not only or "eq_knot_states" in only:
+        knot_states_fixture(out_root)
     if not only or "launch_cases" in only:
         launch_fixture(out_root)
     host_tabs = {}
@@ -384,7 +412,7 @@ def check():
     diffs = []
     with tempfile.TemporaryDirectory() as d:
         generate(d)
-        for name in [c[0] + ".npz" for c in CASES] + [os.path.basename(BINNER_FIXTURE), os.path.basename(RHS_STATES_FIXTURE),
+        for name in [c[0] + ".npz" for c in CASES] + [os.path.basename(BINNER_FIXTURE), os.path.basename(RHS_STATES_FIXTURE), os.path.basename(KNOT_STATES_FIXTURE),
                                                       os.path.basename(LAUNCH_FIXTURE)]:
             a, b = np.load(os.path.join(d, "tests", "golden", name)), np.load(os.path.join(ROOT, "tests", "golden", name))
             if set(a.files) != set(b.files):

@@ -10,6 +10,8 @@ tests/golden/rhs_state_cases.npz by tests/golden/make_golden.py: rhs_states_fixt
 
 label = "<class>.<threshold>", class in A..H ("Thresholds of the right-hand side" has the table):
     A interior   B box   C plasma edge   D axis and symmetry   E dispersion edges   F damping argument   G check_save   H steps
+    K table knots: points on and beside the grid lines of the equilibrium's spline and bilinear tables (knot_states; a
+      fixture of its own, tests/golden/eq_knot_states.npz)
 side  = -1 | +1: the side of the label's threshold the state was aimed at (0: the label has no threshold)."""
 from __future__ import annotations
 
@@ -34,6 +36,49 @@ TINY = 1e-13                    # the margin of axisym_toroid_eq's box test
 KNOTS_SLAB = sorted({int(round(k)) for k in np.linspace(1, 499, 32)} | {499})
 KNOTS_FEW = KNOTS_SLAB[1::2]
 BOX_FLAGS = (10, 11, 12, 20, 21, 22, 23, 25, 26)
+# class K: the axisym_toroid cases that read tables (gold_axisym64_solmag_damp_rk4 has none: analytic magnetics, parabolic
+# profiles) and the case on the box whose grid spacings are no powers of two; a cap of its own
+K_CASES = ["gold_axisym64_eqdsk129_tspline_damp_rk4", "gold_axisym64_eqdsk_tspline_rk4_num", "gold_axisym64_eqlin_damp_rk4",
+           "gold_axisym16_eqdsk49x65_tspline_damp_rk4"]
+MAX_KNOT_STATES = 1500
+K_OFFSETS = (0, -1, 1, -2, 2)   # a node, its neighbouring doubles, two doubles away
+K_EVEN = 4                      # nodes added evenly spaced beyond those the estimate singles out
+
+
+def cell_estimate(grid, x):
+    """The cell search of the reference's cspevx on an evenly spaced grid (splines_lib/cspeval.f90:150-159), restated:
+    -> (the cell estimated from 1 + nxm * (x - x(1)) / (x(nx) - x(1)), the cell settled on), both 1-based"""
+    nxm = len(grid) - 1
+    x1, xn = float(grid[0]), float(grid[-1])
+    z = min(max(float(x), x1), xn)
+    i = min(nxm, max(1, int(1 + nxm * (z - x1) / (xn - x1))))
+    est = i
+    if z < float(grid[i - 1]):
+        i -= 1
+    elif z > float(grid[i]):
+        i += 1
+    return est, min(nxm, max(1, i))
+
+
+def lin_cell(grid, x):
+    """The truncating cell index of GetPsi (eqdsk_utilities_m.f90:154): 1 + int((x - x(1)) / (x(2) - x(1)))"""
+    return 1 + int((float(x) - float(grid[0])) / (float(grid[1]) - float(grid[0])))
+
+
+def knot_kind(grid, x, cell=cell_estimate):
+    """What the cell search makes of x: 'exact' | 'down' | 'up' (the estimate was right | one cell too high | too low; for
+    the truncating index, which has no second look: the index is the cell x lies in | the one below | the one above),
+    and whether x is an interior node that ends in the cell BELOW it (dx = h instead of dx = 0 in the cell above)"""
+    grid = np.asarray(grid)
+    if cell is lin_cell:
+        i = lin_cell(grid, x)
+        k = int(np.argmin(np.abs(grid - x)))
+        # (the truncation has no second look: 'down' / 'up' = the index is not the cell the point lies in)
+        true = int(np.searchsorted(grid, x, side="right"))
+        return ("exact" if i == true else "up" if i > true else "down"), bool(grid[k] == x and i == k)
+    est, i = cell_estimate(grid, x)
+    k = int(np.argmin(np.abs(grid - x)))
+    return ("exact" if est == i else "down" if i < est else "up"), bool(0 < k < len(grid) - 1 and grid[k] == x and i == k)
 
 
 def ulps(x, n):
@@ -391,6 +436,172 @@ class _Case:
             self.label.append("H.step")
             self.side.append(side)
 
+    # ---- K ----
+    def inside(self, v):
+        return self.ev(v)["codes"][0] == 0
+
+    def on_shell(self, v):
+        """v with k rescaled so that check_save's residual is under half its limit (the base state's k belongs to the base
+        state's place: elsewhere check_save ends the ray before its first step, and no trace kernel would take a step from
+        the state); r untouched.  v itself where no factor between 1/2 and 2 does it.  Either way as a LAUNCH state: the
+        rows behind k zero and k = k0 * (k / k0) bit for bit, so that a trace launched at r with the refractive index k / k0
+        starts from this very state (initialize_ode_vector)."""
+        lim = 0.5 * float(self.p.dispersion_resid_limit)
+        k0 = float(self.p.k0)
+
+        def launched(w):
+            w = np.array(w, dtype=np.float64)
+            w[6:] = 0.0
+            for _ in range(4):
+                w[3:6] = k0 * (w[3:6] / k0)
+            assert np.array_equal(k0 * (w[3:6] / k0), w[3:6])
+            return w
+
+        def scaled(mu):
+            w = np.array(v, dtype=np.float64)
+            w[3:6] = w[3:6] * mu
+            return w
+
+        def resid(mu):
+            r = self.ev(scaled(mu))["resid"]
+            return r if r == r else math.inf
+
+        if resid(1.0) <= lim:
+            return launched(v)
+        mus = [2.0 ** (j / 20.0) for j in range(-20, 21)]
+        j = int(np.argmin([resid(m) for m in mus]))
+        lo, hi = mus[max(j - 1, 0)], mus[min(j + 1, len(mus) - 1)]
+        g = (math.sqrt(5.0) - 1.0) / 2.0
+        for _ in range(48):
+            a, b = hi - g * (hi - lo), lo + g * (hi - lo)
+            if resid(a) <= resid(b):
+                hi = b
+            else:
+                lo = a
+        mu = lo + (hi - lo) / 2.0
+        return launched(scaled(mu) if resid(mu) <= lim else v)
+
+    def psiN(self, v):
+        return float(diag_expect.psi_expected(self.p, self.tab, v))
+
+    def node_states(self, label, c, grid, cell=cell_estimate, skip=()):
+        """Interior nodes of `grid` on the base chord in coordinate c that lie inside the plasma: the node, its neighbouring
+        doubles and the doubles two away.  Every node that ends in the lower cell, every node with such a neighbour whose
+        estimate is off, and K_EVEN evenly spaced others.  skip: nodes another label already holds."""
+        grid = np.asarray(grid, dtype=np.float64)
+        nodes = [k for k in range(1, len(grid) - 1) if self.inside(self.at(**{c: float(grid[k])}))]
+        picked = []
+        for k in nodes:
+            kinds = [knot_kind(grid, ulps(float(grid[k]), n), cell) for n in K_OFFSETS]
+            if kinds[0][1] or any(kind != "exact" for kind, _ in kinds):
+                picked.append(k)
+        rest = [k for k in nodes if k not in picked]
+        if rest:
+            picked += [rest[i] for i in sorted(set(np.linspace(0, len(rest) - 1, K_EVEN).astype(int)))]
+        for k in sorted(set(picked) - set(skip)):
+            for n in K_OFFSETS:
+                self.add(label, self.on_shell(self.at(**{c: ulps(float(grid[k]), n)})), (n > 0) - (n < 0))
+        return sorted(picked)
+
+    def corner_states(self):
+        """R and Z both on or beside nodes, the combinations chosen for what the estimate does in each direction: R off
+        alone, Z off alone, both off, and both on nodes that end in the lower cell -- two of each where the grids of the
+        case produce them (a grid with dyadic spacing has no off estimate: there the exact neighbour stands in)."""
+        rg, zg = np.asarray(self.tab["r_grid"]), np.asarray(self.tab["z_grid"])
+
+        def candidates(grid, c, want):
+            out = []
+            for k in range(1, len(grid) - 1):
+                for n in K_OFFSETS:
+                    x = ulps(float(grid[k]), n)
+                    kind, lower = knot_kind(grid, x)
+                    if (kind != "exact", lower) == want and self.inside(self.at(**{c: x})):
+                        out.append(x)
+            return out
+
+        off_r, off_z = candidates(rg, "R", (True, False)), candidates(zg, "z", (True, False))
+        on_r, on_z = candidates(rg, "R", (False, False)), candidates(zg, "z", (False, False))
+        low_r, low_z = candidates(rg, "R", (False, True)), candidates(zg, "z", (False, True))
+
+        def two_inside(rs, zs):
+            """two points (R, z) inside the plasma, no R and no z used twice; the candidates nearest the axis first"""
+            out = []
+            for R in sorted(rs, key=lambda t: abs(t - self.rmaj)):
+                for z in sorted(zs, key=abs):
+                    if not any(R == a or z == b for a, b in out) and self.inside(self.at(R=R, z=z)):
+                        out.append((R, z))
+                        break
+                if len(out) == 2:
+                    break
+            return out
+
+        for rs, zs in ((off_r or on_r, on_z), (on_r, off_z or on_z), (off_r or on_r, off_z or on_z), (low_r or on_r, low_z or on_z),
+                       (off_r or on_r, low_z or on_z), (low_r or on_r, off_z or on_z)):
+            for R, z in two_inside(rs, zs):
+                self.add("K.corner", self.on_shell(self.at(R=R, z=z)))
+
+    def psi_knot_states(self):
+        """Per splined profile of the case: the chord at the base height (the midplane, where the base chord does not reach
+        the knot) on which psiN crosses each interior knot of the profile's grid -- neighbouring doubles of R, one further
+        double either way; psiN EQUAL to the knot, and to each of its neighbouring doubles, where the height scan of
+        C.psi_exactly_1 finds such a chord; and the last doubles inside the plasma (the last cell below psiN = 1).
+        -> by profile, the (knot, offset in doubles) the scan has hit"""
+        exact = {}
+        edge_R = self.box["R"][1]
+        for prof in ("ne", "te", "ti"):
+            grid = self.tab.get(prof + "_grid", ())
+            if np.size(grid) < 2:
+                continue
+            if prof == "ti" and np.array_equal(grid, self.tab.get("te_grid", ())):
+                continue      # (the reference tabulates Te and Ti on ONE grid: the te states are the ti states)
+            label = f"K.psi_knot.{prof}"
+            exact[prof] = []
+            for k in range(1, len(grid) - 1):
+                knot = float(grid[k])
+                for z in (float(self.base[2]), 0.0):
+                    make = lambda t, z=z: self.at(R=t, z=z)
+                    pair = adjacent(lambda t: self.psiN(make(t)) >= knot, self.rmaj, edge_R)
+                    if pair:
+                        self.add_pair(label, lambda t: self.on_shell(make(t)), pair, reach=(1,))
+                        break
+                # (neighbouring doubles of R are several doubles of psiN apart: the knot itself and ITS neighbouring doubles,
+                #  where the quotient of the estimate rounds across the knot, are met on other chords)
+                for n in (0, -1, 1):
+                    target = ulps(knot, n)
+                    for j in range(400):
+                        z = float(self.base[2]) + j * 2.0 ** -10
+                        make = lambda t, z=z: self.at(R=t, z=z)
+                        pair = adjacent(lambda t: self.psiN(make(t)) >= target, self.rmaj, edge_R)
+                        if pair and self.psiN(make(pair[1])) == target:
+                            self.add(label, self.on_shell(make(pair[1])), n)
+                            exact[prof].append((k, n))
+                            break
+            make = lambda t: self.at(R=t)
+            pair = adjacent(lambda t: not self.inside(make(t)), self.rmaj, edge_R)
+            if pair:
+                for n in (0, -1):
+                    self.add(label, self.on_shell(make(ulps(pair[0], n))), -1)
+        return exact
+
+    def knots(self):
+        """-> (v, s, label, side) of class K, and what the generator found: the nodes picked per label and the profile
+        knots with an exact hit"""
+        found = {}
+        self.base_s = 0.0           # (launch states)
+        rg, zg = self.tab["r_grid"], self.tab["z_grid"]
+        found["K.z_node"] = self.node_states("K.z_node", "z", zg)
+        found["K.r_node"] = self.node_states("K.r_node", "R", rg)
+        if "rb_grid" in self.tab and not np.array_equal(self.tab["rb_grid"], rg):
+            found["K.rb_node"] = self.node_states("K.rb_node", "R", self.tab["rb_grid"])
+        self.corner_states()
+        found["exact"] = self.psi_knot_states()
+        if self.p.axisym.magnetics_model == 2:
+            # (nodes away from the outermost cells, where the central differences leave the array: reference_undefined)
+            # the same nodes serve the truncating index; K.lin_cell adds those it singles out that K.z_node / K.r_node lack
+            found["K.lin_cell.z"] = self.node_states("K.lin_cell", "z", zg, lin_cell, skip=found["K.z_node"])
+            found["K.lin_cell.R"] = self.node_states("K.lin_cell", "R", rg, lin_cell, skip=found["K.r_node"])
+        return (np.stack(self.v), np.array(self.s), np.array(self.label), np.array(self.side, dtype=np.int8)), found
+
     def build(self):
         self.interior()
         self.box_states()
@@ -416,6 +627,23 @@ def all_states():
     out = {c: states(c) for c in CASES}
     total = sum(len(v[0]) for v in out.values())
     assert total <= MAX_STATES, total
+    return out
+
+
+_knot_cache = {}
+
+
+def knot_states(case, with_findings=False):
+    """Class K of a case of K_CASES: (v, s, label, side)"""
+    if case not in _knot_cache:
+        _knot_cache[case] = _Case(case).knots()
+    return _knot_cache[case] if with_findings else _knot_cache[case][0]
+
+
+def all_knot_states():
+    out = {c: knot_states(c) for c in K_CASES}
+    total = sum(len(v[0]) for v in out.values())
+    assert total <= MAX_KNOT_STATES, total
     return out
 
 
@@ -447,7 +675,8 @@ def reference_undefined(case, v):
 
 
 # ---- the committed fixture (tests/golden/rhs_state_cases.npz) ----
-_fixture = None
+_fixture = {}
+FIXTURE_FILES = {"A-H": "rhs_state_cases.npz", "K": "eq_knot_states.npz"}
 
 
 def flag_codes(flags, axisym):
@@ -459,18 +688,17 @@ def flag_codes(flags, axisym):
     return np.array([table[f.decode()] for f in flags], dtype=np.int32)
 
 
-def load_fixture(case):
-    """The states of a case and the reference's records: v, s, label, side, cls (the label's class letter), probe, step
+def load_fixture(case, classes="A-H"):
+    """The states of a case (classes "A-H": tests/golden/rhs_state_cases.npz; "K": tests/golden/eq_knot_states.npz, the same
+    record layout) and the reference's records: v, s, label, side, cls (the label's class letter), probe, step
     (tests/refdump.py: read_states, blanked where the reference is undefined), `ok` (tests/refdump.py: defined_masks --
     which parts of each record are reference facts), and the reference's flags as stop codes: eq_code, rhs_code,
     cs_code, step_code, cs1_code."""
-    global _fixture
     import os
     from tests.common import ROOT
-    from tests.refdump import defined_masks
-    if _fixture is None:
-        _fixture = np.load(os.path.join(ROOT, "tests", "golden", "rhs_state_cases.npz"), allow_pickle=False)
-    z = _fixture
+    if classes not in _fixture:
+        _fixture[classes] = np.load(os.path.join(ROOT, "tests", "golden", FIXTURE_FILES[classes]), allow_pickle=False)
+    z = _fixture[classes]
     probe, step, geom = z[case + ":probe"], z[case + ":step"], z[case + ":geom"]
     out = dict(v=np.ascontiguousarray(probe["v"]), s=z[case + ":s"], label=z[case + ":label"], side=z[case + ":side"],
                probe=probe, step=step, geom=geom)
@@ -584,3 +812,19 @@ def expected_ode_step(f):
     # (where equilibrium refuses v0 itself the reference's check_save computes with an eq_point it never set: no fact)
     started = ~never_starts & ok["values"]
     return code, never_starts | (rows & started), ok["step"] & started, never_starts
+
+
+def compare_one_step_trace(f, npoints, stop_code, v_end, resid_end, what):
+    """A trace of nstep_max = 1 LAUNCHED at the states (class K holds launch states: r and the refractive index k / k0 give
+    the state back bit for bit) against the reference's records: where the step is taken and kept the ray has two
+    points, ends on ' nstep > nstep_max' (2) and its last point is the reference's v1 with its residual; elsewhere it has
+    its launch point alone and the stop code the records give."""
+    want, rows, v1_rows, zero_rows = expected_ode_step(f)
+    kept = rows & v1_rows & (want == 0)
+    assert 3 * kept.sum() >= 2 * len(kept), f"{what}: {int(kept.sum())} of {len(kept)} states take a step that is kept"
+    _check(f, what, "npoints", np.asarray(npoints), np.where(kept, 2, 1).astype(np.int32), rows)
+    _check(f, what, "the stop code", np.asarray(stop_code), np.where(kept, 2, want).astype(np.int32), rows)
+    _check(f, what, "the last point", np.asarray(v_end), f["step"]["v1"], kept)
+    if resid_end is not None:      # (a summary-only trace keeps no residual of a point)
+        _check(f, what, "the last point's residual", np.asarray(resid_end), f["step"]["resid1"], kept & f["ok"]["step_cs"])
+    return kept

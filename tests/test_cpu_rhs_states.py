@@ -11,6 +11,7 @@ from tests import diag_expect as dx, emul_build as eb, oracle_lib, probe_emul_li
 from tests.common import load_golden
 
 DAMPED = [c for c in rc.CASES if load_golden(c)[2].damping_model]
+NEW_BOX = "gold_axisym16_eqdsk49x65_tspline_damp_rk4"      # (the box whose grid spacings are no powers of two)
 
 
 # the floors of the axisym_toroid profiles: (column of the eq record, the floored value); the splined temperatures of the
@@ -20,9 +21,9 @@ FLOORS = {"C.dens_floor": lambda p: (28, p.n0s[0] * p.axisym.d_scrape_off),
           "C.Ti_floor": lambda p: (44, p.t0s[1] * p.axisym.T_scrape_off)}
 
 
-def _case(case):
+def _case(case, classes="A-H"):
     g, nml, p = load_golden(case)
-    return g, p, eb.axisym_tables_of(g), rc.load_fixture(case)
+    return g, p, eb.axisym_tables_of(g), rc.load_fixture(case, classes)
 
 
 # ---- the fixture itself ----
@@ -131,8 +132,8 @@ def test_oracle_equals_the_reference_at_every_state(case):
 
 
 # ---- the device headers on the host ----
-def _compare_emulated(case, lib_=None, only=None):
-    g, p, tab, f = _case(case)
+def _compare_emulated(case, lib_=None, only=None, classes="A-H"):
+    g, p, tab, f = _case(case, classes)
     f = dict(f, only=None if only is None else np.isin(f["cls"], list(only)))
     got = pe.probe(p, f["v"], tab, lib_)
     rc.compare_probe(f, got, f"{case}: emulated probe", eq_columns=pe.eq_columns(p))
@@ -190,6 +191,11 @@ def test_emulated_diagnostics_at_the_states(case):
 #     the whole row are NaN with and without the guard);
 #   * `k3 > 0.` -> `k3 >= 0.`: the two differ at k3 = 0 alone, which the guard above has already answered.
 # The branch itself is held by `k3 > 0.` -> `k3 < 0.`.
+# A third, of the bilinear model's cell index (class K): `1 + (int)q` -> `(int)ceil(q)`.  The two differ where the quotient q
+# is a whole number -- on a grid line, or a double below one where q rounds up to it -- and there they name neighbouring
+# cells with the fraction 0 in one and 1 (or a negative fraction of 1e-16) in the other: the bilinear form is continuous
+# across the line, three of its four products are then exact zeros, and the value has the same bits either way.  What K
+# holds is the index itself (`1 +` -> `2 +`), which every class of that configuration sees as well.
 MUTATIONS = {
     "slab box < -> <=": ("gold_slab16_damp_rk4", "if (x < P.xmin || x > P.xmax) err", "if (x <= P.xmin || x > P.xmax) err", "B"),
     "axisym Tiny margin dropped": ("gold_axisym64_eqdsk129_tspline_damp_rk4", "r > P.a_box_rmax + Tiny", "r > P.a_box_rmax", "B"),
@@ -201,6 +207,13 @@ MUTATIONS = {
     "fabs(xi) > 5. -> >= 5.": ("gold_slab16_damp_rk4", "if (fabs(xi) > 5.) return 0.;", "if (fabs(xi) >= 5.) return 0.;", "F"),
     "(float) of delta_im removed": ("gold_slab16_damp_rk4", "const float delta_im = (float)divdc3(num, den).im;", "const double delta_im = divdc3(num, den).im;", "F"),
     "v[7] > limit -> >=": ("gold_solovev64_damp_rk4", "] > P.total_damping_limit) {", "] >= P.total_damping_limit) {", "F"),
+    # the cell search of the table lookups (class K: tests/golden/eq_knot_states.npz)
+    "spl_settle: arms exchanged": (NEW_BOX, "i = z < lo ? i - 1 : i + 1;", "i = z < lo ? i + 1 : i - 1;", "K"),
+    "spl_settle: z > hi -> >=": (NEW_BOX, "if (RAYS_RARE(z < lo || z > hi)) {", "if (RAYS_RARE(z < lo || z >= hi)) {", "K"),
+    "spl2_fpp: offx || offy -> &&": (NEW_BOX, "if (RAYS_RARE(offx || offy)) {", "if (RAYS_RARE(offx && offy)) {", "K"),
+    "spl1_ax: lo not fetched again": ("gold_axisym64_eqdsk_tspline_rk4_num", "  if (spl_settle(n, z, lo, hi, i)) {\n    lo = grid[i - 1];\n    c = fspl", "  if (spl_settle(n, z, lo, hi, i)) {\n    c = fspl", "K"),
+    "eqlin: cell index one higher": ("gold_axisym64_eqlin_damp_rk4", "const int j = 1 + (int)div(Z - z1, Rhz);", "const int j = 2 + (int)div(Z - z1, Rhz);", "K"),
+    "spl_guess: product with the stored reciprocal": (NEW_BOX, "div(nxm * (z - x1), const_recip(xn - x1, ax[2]))", "((nxm * (z - x1)) * ax[2])", "K"),
 }
 
 
@@ -209,7 +222,7 @@ def test_one_changed_token_fails_in_the_class_that_owns_the_threshold(name, tmp_
     case, old, new, classes = MUTATIONS[name]
     lib_ = pe.mutated_lib(tmp_path, old, new)
     with pytest.raises(AssertionError, match=rf"\(class [{classes}],") as e:
-        _compare_emulated(case, lib_, only=classes)      # the states of the owning class ALONE have to show it
+        _compare_emulated(case, lib_, only=classes, classes="K" if classes == "K" else "A-H")      # the states of the owning class ALONE have to show it
     print(f"{name}: {e.value}")
 
 
