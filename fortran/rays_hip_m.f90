@@ -433,6 +433,31 @@
           integer(c_int), value :: nray, n_profiles
        end function rays_hip_profiles_kernel_name_for
 
+       ! One deposition window: the state advances as in a summary-policy rays_hip_trace_window_device call, and every point
+       ! the window accepts is binned into the records' work(nray, n_bins) (device pointers, bin-major) -- ACCUMULATORS the
+       ! call never zeroes: zero them once, when rays_hip_state_init_device is called.  A record's profile may be
+       ! c_null_ptr (no sum in this window); otherwise it is the ray-ordered sum over the work so far, continued from
+       ! profile_in.  d_initial_ray_power(nray) is required; d_npoints_win(nray): the points this call accepted.
+       ! Asynchronous on hip_stream; one caller thread per (device, stream).
+       integer(c_int) function rays_hip_trace_window_profiles_device(p, nray, state, n_steps, d_initial_ray_power, &
+                    & n_profiles, profiles, d_npoints_win, hip_stream) &
+                    & bind(C, name='rays_hip_trace_window_profiles_device')
+          import :: c_int, c_ptr, rays_params_t, rays_ray_state_t, rays_dep_profile_t
+          type(rays_params_t), intent(in) :: p
+          integer(c_int), value :: nray, n_steps, n_profiles
+          type(rays_ray_state_t), intent(in) :: state
+          type(rays_dep_profile_t), intent(in) :: profiles(*)
+          type(c_ptr), value :: d_initial_ray_power, d_npoints_win, hip_stream
+       end function rays_hip_trace_window_profiles_device
+
+       ! (c_ptr to a NUL-terminated name, as the other *_kernel_name_for)
+       type(c_ptr) function rays_hip_window_profiles_kernel_name_for(p, nray, n_profiles) &
+                    & bind(C, name='rays_hip_window_profiles_kernel_name_for')
+          import :: c_int, c_ptr, rays_params_t
+          type(rays_params_t), intent(in) :: p
+          integer(c_int), value :: nray, n_profiles
+       end function rays_hip_window_profiles_kernel_name_for
+
        ! ASYNCHRONOUS on hip_stream (blocking before round 3): synchronise the stream before d_v1 / d_resid /
        ! d_stop_code are read on the host or from another stream; one caller thread per (device, stream).
        integer(c_int) function rays_hip_ode_step_device(p, n, d_v0, d_s0, d_v1, d_resid, d_stop_code, hip_stream) &

@@ -412,7 +412,8 @@ const char* rays_hip_deposition_kernel_name_for(const rays_params_t* p, int nray
  * each record; n_profiles outside 1..RAYS_DEP_MAX_PROFILES; the same `which` twice; two profiles on a configuration
  * that has one (the single-profile refusal's message); a null work or profile in the device form; a non-null
  * profile_in in the host form.
- * OUT OF SCOPE: more than two profiles, the same profile at two bin counts, a tolerance variant, windows. */
+ * OUT OF SCOPE: more than two profiles, the same profile at two bin counts, a tolerance variant.  (In windows:
+ * rays_hip_trace_window_profiles_device below.) */
 #define RAYS_DEP_MAX_PROFILES 2
 typedef struct rays_dep_profile {
   int which, n_bins;          /* RAYS_DEP_PTOTAL_*; 1..RAYS_DEP_MAX_BINS */
@@ -480,8 +481,9 @@ int rays_hip_deposition_profile_set(const rays_params_t* p, int* which);
  * library traces.
  * Asynchronous on hip_stream.  Refused by name, before anything is launched: n_steps < 1, nray < 0, a null required
  * pointer, sg_err == NULL with SG_ODE, only one of the two window arrays, a shape that is not built.
- * OUT OF SCOPE: continuing the fused deposition variant or the fused ds scan; a tolerance flavour; re-opening a ray
- * that ended with ' nstep > nstep_max' under a larger nstep_max (its s has been advanced). */
+ * OUT OF SCOPE: continuing the fused ds scan; a tolerance flavour; re-opening a ray that ended with
+ * ' nstep > nstep_max' under a larger nstep_max (its s has been advanced).  (Continuing the fused deposition variant:
+ * rays_hip_trace_window_profiles_device below.) */
 #define RAYS_STATE_REFUSED 1
 typedef struct rays_ray_state {
   double* v;          /* [nray][nv] */
@@ -504,6 +506,40 @@ int rays_hip_state_summary_device(const rays_params_t* p, int nray, const rays_r
 /* Name of the kernel rays_hip_trace_window_device launches (recording != 0: with window arrays; 0: summary policy);
  * "" when p is refused or has no such kernel. */
 const char* rays_hip_window_kernel_name_for(const rays_params_t* p, int nray, int recording);
+/* ---- deposition windows: the fused deposition kernels continued from the saved state --------------------------------
+ * rays_hip_trace_window_profiles_device advances the state exactly as a summary-policy rays_hip_trace_window_device
+ * call does (no trajectory exists) and bins every point the window accepts into the rows of `profiles`, a HOST array of
+ * 1..RAYS_DEP_MAX_PROFILES records holding DEVICE pointers:
+ *   n_profiles == 1   the continuation variant of the fused deposition kernel (EQ + 224 in its name)
+ *   n_profiles == 2   that of the two-profile kernel (EQ + 480), axisym_toroid with a rho table only
+ *   work              [n_bins][nray] bin-major, required.  An ACCUMULATOR: the call never zeroes it.  The caller zeroes
+ *                     it once, when it calls rays_hip_state_init_device, and hands the same array to every window.
+ *   profile           may be NULL: then no sum is run (an intermediate window need not pay for it).  Otherwise the
+ *                     ray-ordered sum over the work SO FAR, continued from profile_in (NULL = from zero).
+ * d_initial_ray_power[nray] is required.  d_npoints_win[nray]: the points this call accepted, 0 for a ray that had ended.
+ * A paused ray's saved v is its last recorded point and the last point binned: the launch that continues it evaluates
+ * the grid value(s) and v(8) * power there again, which are the values the one-shot kernel carries in registers.
+ * CONTRACT: start from rays_hip_state_init_device with zeroed works and run any sequence of deposition windows with
+ * n_steps >= 1 until every ray has ended.  Then each work and profile equals rays_hip_trace_profiles_device's on the
+ * same rays bit for bit, and rays_hip_state_summary_device gives the one-shot summaries.  After any prefix of the
+ * sequence each work equals rays_hip_deposition_device on the one-shot trajectories with npoints clipped to
+ * state.nstep + 1.  Once every ray has ended, further calls change no byte of the state or the works and return
+ * npoints_win = 0.
+ * THE CALLER'S CHOICE, not detectable: steps taken by a plain rays_hip_trace_window_device call in between are not
+ * binned (the next deposition window starts its segments from the point that call left).
+ * Asynchronous on hip_stream; one caller thread per (device, stream); the argument block is the one the one-shot
+ * entries keep per stream, released by rays_hip_finalize.  Always the EXACT kernels.
+ * Refused by name, before anything is launched: everything rays_hip_trace_profiles_device refuses, for each record
+ * (but a null profile is allowed); everything rays_hip_trace_window_device refuses; a null d_initial_ray_power.
+ * OUT OF SCOPE: a host form; recording windows that also bin; the fused ds scan; a tolerance variant. */
+int rays_hip_trace_window_profiles_device(const rays_params_t* p, int nray, const rays_ray_state_t* state, int n_steps,
+                                          const double* d_initial_ray_power, int n_profiles,
+                                          const rays_dep_profile_t* profiles /* host array of device pointers */,
+                                          int32_t* d_npoints_win, void* hip_stream);
+/* Name of the kernel rays_hip_trace_window_profiles_device launches for n_profiles records ("" when p is refused or
+ * has no such kernel). */
+const char* rays_hip_window_profiles_kernel_name_for(const rays_params_t* p, int nray, int n_profiles);
+
 /* Host pointers, blocking: the arguments and the results of rays_hip_trace, bit for bit (entries past npoints are left
  * as the caller passed them), traced in windows of n_steps.  Device memory is the ray state, two window slabs
  * [nray][n_steps][nv + 1] and the inputs, whatever nstep_max is; window k is copied out (whole slabs, through pinned

@@ -15,9 +15,12 @@ $(call inst_variant,win,128,-DRAYS_INST_CONTINUE=1)
 $(call inst_variant,wsum,160,-DRAYS_INST_CONTINUE=1 -DRAYS_INST_NOTRAJ=1)
 $(call inst_variant,tol,16,-DRAYS_INST_TOL=1)
 $(call inst_variant,dep2,352,-DRAYS_INST_NOTRAJ=1 -DRAYS_INST_DEPOSIT=1 -DRAYS_INST_DEPOSIT2=1)
+$(call inst_variant,wdep,224,-DRAYS_INST_CONTINUE=1 -DRAYS_INST_NOTRAJ=1 -DRAYS_INST_DEPOSIT=1)
+$(call inst_variant,wdep2,480,-DRAYS_INST_CONTINUE=1 -DRAYS_INST_NOTRAJ=1 -DRAYS_INST_DEPOSIT=1 -DRAYS_INST_DEPOSIT2=1)
 # (inst: the kernels record the trajectories; sum: summary-only; dep: fused deposition; win, wsum: the continuation
 # kernels of windowed tracing, recording and summary-only; tol: the tolerance flavour of the cold RK4 groups; dep2: fused
-# deposition into two profiles, kEqDeposit2 256, of the axisym_toroid groups.  Which
+# deposition into two profiles, kEqDeposit2 256, of the axisym_toroid groups; wdep, wdep2: the continuation kernels of
+# dep and dep2, windowed tracing that bins what it accepts.  Which
 # kernels of the shape lists a variant keeps: rays_inst.hip.)
 #
 # The including Makefile supplies

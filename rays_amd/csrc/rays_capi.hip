@@ -139,13 +139,16 @@ std::atomic<int> g_numerics{initial_numerics()};
 //              the continuation variant (windowed tracing) of the exact kernel, recording or summary-only: always the
 //              one-ray-per-lane entry, whatever the fan size -- the only one built, and bit-identical to the others
 //   Deposit2   the two-profile variant of the fused deposition kernel (axisym_toroid groups)
-enum class KernelVariant { Recording, ExactTwin, Summary, Deposit, Window, WindowSummary, Deposit2 };
+//   WindowDeposit, WindowDeposit2
+//              the continuation variant of the fused deposition kernels
+enum class KernelVariant { Recording, ExactTwin, Summary, Deposit, Window, WindowSummary, Deposit2, WindowDeposit, WindowDeposit2 };
 // The build of rays_inst.hip that holds a variant's kernels under the exact numerics (from Summary on the two
 // enumerations name the same builds in the same order).
 rays::KernelBuild build_of(KernelVariant v) {
   static_assert((int)KernelVariant::Summary == (int)rays::KernelBuild::Summary &&
                 (int)KernelVariant::WindowSummary == (int)rays::KernelBuild::WindowSummary &&
-                (int)KernelVariant::Deposit2 == (int)rays::KernelBuild::Deposit2, "KernelVariant | KernelBuild");
+                (int)KernelVariant::Deposit2 == (int)rays::KernelBuild::Deposit2 &&
+                (int)KernelVariant::WindowDeposit2 == (int)rays::KernelBuild::WindowDeposit2, "KernelVariant | KernelBuild");
   return v < KernelVariant::Summary ? rays::KernelBuild::Recording : (rays::KernelBuild)(int)v;
 }
 
@@ -685,8 +688,9 @@ struct TraceExtras {
   bool state_init = false;
 };
 // variant: Recording (into `traj`), Summary or Deposit (no trajectory arrays; out.sv is optional).  out.ev, out.er and
-// out.mr are optional for a recording launch.  Window (into the slabs `traj`) | WindowSummary: out.np is npoints_win and
-// the other summaries live in extra.state.
+// out.mr are optional for a recording launch.  Window (into the slabs `traj`) | WindowSummary | WindowDeposit |
+// WindowDeposit2: out.np is npoints_win and the other summaries live in extra.state; the last two also take extra.dep |
+// extra.dep2 (the ray_vec slot, which the summary-policy continuation kernels leave null).
 int launch_trace(const rays_params_t* p, KernelVariant variant, int nray, const RayInputs& in,
                  const TrajectoryArrays& traj, const SummaryArrays& out, hipStream_t stream, int flags,
                  const TraceExtras& extra = TraceExtras()) {
@@ -705,7 +709,8 @@ int launch_trace(const rays_params_t* p, KernelVariant variant, int nray, const 
   A.nray = nray;
   A.rvec0 = in.rvec0;
   A.rindex_vec0 = in.rindex_vec0;
-  const bool window = variant == KernelVariant::Window || variant == KernelVariant::WindowSummary;
+  const bool window_dep = variant == KernelVariant::WindowDeposit || variant == KernelVariant::WindowDeposit2;
+  const bool window = variant == KernelVariant::Window || variant == KernelVariant::WindowSummary || window_dep;
   A.ray_vec = recording || variant == KernelVariant::Window ? traj.rv : nullptr;
   A.residual = recording || variant == KernelVariant::Window ? traj.res : nullptr;
   A.npoints = out.np;
@@ -723,12 +728,13 @@ int launch_trace(const rays_params_t* p, KernelVariant variant, int nray, const 
   A.sched = nullptr;
   A.sched_stride = 0;
   A.set_start_ray_vec(recording ? nullptr : out.sv);
-  if (variant == KernelVariant::Deposit) A.set_dep(extra.dep);
-  if (variant == KernelVariant::Deposit2) A.set_dep2(extra.dep2);
+  if (variant == KernelVariant::Deposit || variant == KernelVariant::WindowDeposit) A.set_dep(extra.dep);
+  if (variant == KernelVariant::Deposit2 || variant == KernelVariant::WindowDeposit2) A.set_dep2(extra.dep2);
   if (window) A.set_state(*extra.state, extra.n_steps);
   const rays::KernelEntry* kernel = find_kernel(*p, nray, variant);
   if (!kernel || (extra.state_init && !kernel->resume))
-    return fail(window ? "rays_hip: the continuation kernel of this configuration is not in this build"
+    return fail(window_dep ? "rays_hip: the deposition window kernel of this configuration is not in this build"
+                : window ? "rays_hip: the continuation kernel of this configuration is not in this build"
                 : variant == KernelVariant::Deposit2
                     ? "rays_hip: the two-profile deposition kernel of this configuration is not in this build"
                 : variant == KernelVariant::Deposit
@@ -1975,6 +1981,88 @@ int rays_hip_trace_profiles_device(const rays_params_t* p, int nray, const doubl
 const char* rays_hip_profiles_kernel_name_for(const rays_params_t* p, int nray, int n_profiles) {
   if (!p || n_profiles < 1 || n_profiles > RAYS_DEP_MAX_PROFILES || rays_hip_check_params(p)) return "";
   const rays::KernelEntry* k = find_kernel(*p, nray, n_profiles == 2 ? KernelVariant::Deposit2 : KernelVariant::Deposit);
+  return k ? k->name : "";
+}
+
+// ---- deposition windows: the fused kernels continued from a saved ray state (include/rays_hip.h) ----
+// The rows of work are accumulators: nothing here zeroes them, so a sequence of windows performs the additions of one
+// fused pass in the same order.  The argument block is written per call into the owner the one-shot entries use (one
+// caller thread per (device, stream)).
+int rays_hip_trace_window_profiles_device(const rays_params_t* p, int nray, const rays_ray_state_t* state, int n_steps,
+                                          const double* d_initial_ray_power, int n_profiles,
+                                          const rays_dep_profile_t* profiles, int32_t* d_npoints_win, void* hip_stream) {
+  const char* who = "rays_hip_trace_window_profiles_device";
+  int rc = refuse_trace_profiles(who, p, nray, n_profiles, profiles);
+  if (rc) return rc;
+  rc = refuse_state(who, p, nray, state);
+  if (rc) return rc;
+  if (n_steps < 1) return fail(std::string(who) + ": n_steps < 1");
+  if (!d_npoints_win) return fail(std::string(who) + ": null device pointer");
+  if ((long long)nray * n_steps > 0x7fffffffll) return fail(std::string(who) + ": nray * n_steps exceeds 2^31 - 1");
+  if (!d_initial_ray_power) return fail(std::string(who) + ": null initial_ray_power");
+  for (int i = 0; i < n_profiles; i++)
+    if (!profiles[i].work) return fail(std::string(who) + ": null work");
+  const KernelVariant variant = n_profiles == 2 ? KernelVariant::WindowDeposit2 : KernelVariant::WindowDeposit;
+  if (!find_kernel(*p, nray, variant))
+    return fail(std::string(who) + ": the deposition window kernel of this configuration is not in this build");
+  if (nray == 0) return 0;
+  const hipStream_t stream = (hipStream_t)hip_stream;
+  const rays::TraceArgs::State st = state_of(state);
+  TraceExtras x;
+  x.state = &st;
+  x.n_steps = n_steps;
+  if (n_profiles == 1) {
+    rays::DepTraceArgs T;
+    T.which = profiles[0].which;
+    T.n_bins = profiles[0].n_bins;
+    T.power = d_initial_ray_power;
+    T.work = profiles[0].work;
+    T.pad_ = 0;
+    rc = fill_deposition_grid(p, profiles[0].which, &T);
+    if (rc) return rc;
+    rays::DepTraceArgs* d_T = nullptr;
+    HIP_TRY_AS("hipMalloc (deposition arguments)", g_dep_ws.get(stream, sizeof(rays::DepTraceArgs), (void**)&d_T));
+    const hipError_t e = rays::launch_dep_trace_args(T, d_T, stream);
+    if (e != hipSuccess) return hip_fail(e, "deposition arguments kernel");
+    x.dep = d_T;
+  } else {
+    rays::Dep2TraceArgs T;
+    T.power = d_initial_ray_power;
+    T.rho_grid = nullptr; T.rho_fspl = nullptr; T.n_rho = 0; T.pad_ = 0;
+    for (int i = 0; i < 2; i++) {
+      rays::DepTraceArgs G;  // (the grid limits and the rho table of this record, as the single-profile launch takes them)
+      rc = fill_deposition_grid(p, profiles[i].which, &G);
+      if (rc) return rc;
+      T.prof[i].which = profiles[i].which;
+      T.prof[i].n_bins = profiles[i].n_bins;
+      T.prof[i].grid_min = G.grid_min;
+      T.prof[i].grid_max = G.grid_max;
+      T.prof[i].work = profiles[i].work;
+      if (profiles[i].which == RAYS_DEP_PTOTAL_RHO) { T.rho_grid = G.rho_grid; T.rho_fspl = G.rho_fspl; T.n_rho = G.n_rho; }
+    }
+    rays::Dep2TraceArgs* d_T = nullptr;
+    HIP_TRY_AS("hipMalloc (deposition arguments)", g_dep2_ws.get(stream, sizeof(rays::Dep2TraceArgs), (void**)&d_T));
+    const hipError_t e = rays::launch_dep2_trace_args(T, d_T, stream);
+    if (e != hipSuccess) return hip_fail(e, "deposition arguments kernel");
+    x.dep2 = d_T;
+  }
+  SummaryArrays out = {};
+  out.np = d_npoints_win;
+  rc = launch_trace(p, variant, nray, {nullptr, nullptr}, {}, out, stream, RAYS_TRACE_NO_ZERO_FILL, x);
+  if (rc) return rc;
+  for (int i = 0; i < n_profiles; i++) {  // + the ray-ordered sums over the work so far, where the caller wants them
+    if (!profiles[i].profile) continue;
+    const hipError_t e = rays::launch_profile_sum(profiles[i].n_bins, nray, profiles[i].work, profiles[i].profile_in,
+                                                  profiles[i].profile, stream);
+    if (e != hipSuccess) return hip_fail(e, "profile sum kernel");
+  }
+  return 0;
+}
+
+const char* rays_hip_window_profiles_kernel_name_for(const rays_params_t* p, int nray, int n_profiles) {
+  if (!p || n_profiles < 1 || n_profiles > RAYS_DEP_MAX_PROFILES || rays_hip_check_params(p)) return "";
+  const rays::KernelEntry* k =
+      find_kernel(*p, nray, n_profiles == 2 ? KernelVariant::WindowDeposit2 : KernelVariant::WindowDeposit);
   return k ? k->name : "";
 }
 

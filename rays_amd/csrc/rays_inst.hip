@@ -15,6 +15,8 @@
 //   windowed tracing) of an exact group, recording or summary-only.  The same shape lists, cut down to the
 //   one-ray-per-lane kernels: a configuration is continued exactly when it is traced at all.  The recording objects
 //   also hold the state_init kernel of each shape (rays_trace.hpp), in the entries' `resume` slot.
+//   -DRAYS_INST_CONTINUE=1 -DRAYS_INST_NOTRAJ=1 -DRAYS_INST_DEPOSIT=1 [-DRAYS_INST_DEPOSIT2=1]: the continuation variant of
+//   a fused deposition kernel (a window that bins what it accepts), with the fused variant's lists.
 //   -DRAYS_INST_TOL=1 -DRAYS_TOL_FLAVOUR -ffp-contract=fast: the tolerance flavour of a cold RK4 group
 //   (rays_device.hpp: kEqTol; 1e-10 relative per step instead of bit-identity)
 // `make FULL=1` (-DRAYS_INST_FULL): each group instantiates the species counts NS = 1..6 (nspec = 0..5,
@@ -49,8 +51,8 @@
 #ifndef RAYS_INST_CONTINUE
 #define RAYS_INST_CONTINUE 0
 #endif
-#if RAYS_INST_CONTINUE && (RAYS_INST_TOL || RAYS_INST_DEPOSIT)
-#error "the continuation variant exists for the exact recording and summary-only kernels only"
+#if RAYS_INST_CONTINUE && (RAYS_INST_TOL || (RAYS_INST_DEPOSIT && !RAYS_INST_NOTRAJ))
+#error "the continuation variant exists for the exact recording, summary-only and fused deposition kernels only"
 #endif
 #if RAYS_INST_NOTRAJ && RAYS_INST_TOL
 #error "the summary-only variant exists in the exact arithmetic only"
@@ -264,8 +266,8 @@ extern "C" int RAYS_CAT(rays_debug_sg_profile, RAYS_INST_SOLVER, RAYS_INST_EQ, R
 
 namespace {
 constexpr KernelBuild kBuild = RAYS_INST_TOL        ? KernelBuild::Tolerance
-                               : RAYS_INST_DEPOSIT2 ? KernelBuild::Deposit2
-                               : RAYS_INST_DEPOSIT  ? KernelBuild::Deposit
+                               : RAYS_INST_DEPOSIT2 ? (RAYS_INST_CONTINUE ? KernelBuild::WindowDeposit2 : KernelBuild::Deposit2)
+                               : RAYS_INST_DEPOSIT  ? (RAYS_INST_CONTINUE ? KernelBuild::WindowDeposit : KernelBuild::Deposit)
                                : RAYS_INST_CONTINUE ? (RAYS_INST_NOTRAJ ? KernelBuild::WindowSummary : KernelBuild::Window)
                                : RAYS_INST_NOTRAJ   ? KernelBuild::Summary
                                                     : KernelBuild::Recording;

@@ -40,8 +40,10 @@ struct KernelEntry {
 //   Window, WindowSummary
 //                  the continuation kernels of windowed tracing, recording and summary-only
 //   Deposit2       fused deposition into two profiles (axisym_toroid: Ptotal_psi and Ptotal_rho in one pass)
-enum class KernelBuild { Recording, Tolerance, Summary, Deposit, Window, WindowSummary, Deposit2 };
-constexpr int kKernelBuilds = 7;
+//   WindowDeposit, WindowDeposit2
+//                  the continuation kernels of Deposit and Deposit2: windows that bin what they accept
+enum class KernelBuild { Recording, Tolerance, Summary, Deposit, Window, WindowSummary, Deposit2, WindowDeposit, WindowDeposit2 };
+constexpr int kKernelBuilds = 9;
 
 // The entry list of one object of rays_inst.hip.  Every object holds one and hands it to register_kernel_group from a
 // static initialiser; rays_capi.hip looks kernels up in the list of what registered, so a group that is not linked in is

@@ -92,8 +92,8 @@
   // launch's n_steps recorded steps; points are stored directly into the window slab [nray][n_steps].  (kIsContinue<EQ>,
   // rays_trace.hpp: a constant of namespace scope -- one more local constant here moves instructions in the kernels
   // that do not have the bit, and those are to come out of the compiler exactly as they were.)
-  static_assert(!kIsContinue<EQ> || (RAYS_RK4_LONG_FIRST && !(EQ & (kEqDeposit | kEqTol))),
-                "the continuation variant: an exact one-wave-per-SIMD kernel, recording or summary-only");
+  static_assert(!kIsContinue<EQ> || (RAYS_RK4_LONG_FIRST && !(EQ & kEqTol) && (!(EQ & kEqDeposit) || (EQ & kEqNoTraj))),
+                "the continuation variant: an exact one-wave-per-SIMD kernel, recording, summary-only or fused deposition");
   constexpr bool kWindow = RAYS_RK4_USE_WINDOW && Window::kAny && !kNoTraj && !kIsContinue<EQ>;
   // fused deposition variant (kEqDeposit; rays_deposition.hpp): an accepted point is binned into the ray's row of work.
   // The grid value and the absorbed power of the ray's last recorded point belong to the ray: set at its point 1.
@@ -321,7 +321,16 @@
           // ray_tracing.f90:92-112: point 1 = initial state, residual(1) = 0
           if constexpr (kIsContinue<EQ>) {
             // a continued ray's first evaluation, at its saved point: the next step's first stage and nothing else -- the
-            // point was recorded (and passed check_save) by the launch that paused the ray there; cs_stop is not looked at
+            // point was recorded (and passed check_save) by the launch that paused the ray there; cs_stop is not looked at.
+            // It was also the last point binned (DESIGN.md 4.10.1): its grid value and absorbed power are what the one-shot
+            // kernel carries in registers here (dep_trace_segment ends by calling dep_trace_point on the same v).
+            if constexpr (kIsDeposit2<EQ>) {
+              const TraceArgs& A = cold_args(A_hot);
+              dep2_trace_first(P, *A.dep2(), ray, v, dep_x_prev, dep_x2_prev, dep_q_prev);
+            } else if constexpr (kDeposit) {
+              const TraceArgs& A = cold_args(A_hot);
+              dep_trace_point(P, *A.dep(), ray, v, dep_x_prev, dep_q_prev);
+            }
           } else if constexpr (kNoTraj) {  // ... of which the summaries keep the state: start_ray_vec (ray_tracing.f90:259)
             const TraceArgs& A = cold_args(A_hot);
             double* const start = A.start_ray_vec();

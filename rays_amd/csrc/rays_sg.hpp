@@ -490,7 +490,8 @@ sg_trace_kernel(const DevParams P_kernarg, const TraceArgs A_hot) {
   // continuation variant (kEqContinue): rays start from the saved state and are paused into it after the
   // launch's n_steps recorded steps; points go into the window slab [nray][n_steps]
   constexpr bool kContinue = (EQ & kEqContinue) != 0;
-  static_assert(!kContinue || !(EQ & (kEqDeposit | kEqTol)), "the continuation variant: recording or summary-only");
+  static_assert(!kContinue || (!(EQ & kEqTol) && (!(EQ & kEqDeposit) || (EQ & kEqNoTraj))),
+                "the continuation variant: recording, summary-only or fused deposition");
   [[maybe_unused]] int win0 = 0;  // steps the ray had recorded when this window began
 
   // ---- per-lane integrator state (de / step locals that live across RHS evaluations) ----------
@@ -642,7 +643,15 @@ sg_trace_kernel(const DevParams P_kernarg, const TraceArgs A_hot) {
         seg = SEG_DE_BEGIN;
         if (kContinue && RAYS_RARE(fl & FL_FIRST)) {
           // a continued ray's first evaluation, at its saved point: the start-of-interval f and nothing else -- the
-          // point was recorded (and passed check_save) by the launch that paused the ray there
+          // point was recorded (and passed check_save) by the launch that paused the ray there.  It was also the last
+          // point binned: its grid value and absorbed power are re-established from it.
+          if constexpr (kIsDeposit2<EQ>) {
+            const TraceArgs& A = cold_args(A_hot);
+            dep2_trace_first(P, *A.dep2(), ray, yy, dep_x_prev, dep_x2_prev, dep_q_prev);
+          } else if constexpr (kDeposit) {
+            const TraceArgs& A = cold_args(A_hot);
+            dep_trace_point(P, *A.dep(), ray, yy, dep_x_prev, dep_q_prev);
+          }
           fl &= ~FL_FIRST;
         } else if (RAYS_RARE(fl & FL_FIRST)) {  // ray_tracing.f90:92-112
           if constexpr ((EQ & kEqNoTraj) != 0) {  // summary-only: point 1 is kept as start_ray_vec (ray_tracing.f90:259)

@@ -42,6 +42,7 @@ EXPORTED_SYMBOLS = (
     "rays_hip_rk4_loop_for",
     "rays_hip_state_init_device", "rays_hip_trace_window_device", "rays_hip_state_summary_device",
     "rays_hip_window_kernel_name_for", "rays_hip_trace_windowed",
+    "rays_hip_trace_window_profiles_device", "rays_hip_window_profiles_kernel_name_for",
 )
 
 _lib = None
@@ -175,6 +176,13 @@ def load():
         lib.rays_hip_window_kernel_name_for.argtypes = [pp, C.c_int, C.c_int]
         lib.rays_hip_trace_windowed.restype = C.c_int
         lib.rays_hip_trace_windowed.argtypes = [pp, C.c_int, dp, dp, C.c_int, dp, dp, ip, ip, dp, dp, dp, dp]
+    # (likewise the deposition windows -- tools/window_deposition_bench.py)
+    if hasattr(lib, "rays_hip_trace_window_profiles_device"):
+        lib.rays_hip_trace_window_profiles_device.restype = C.c_int
+        lib.rays_hip_trace_window_profiles_device.argtypes = [pp, C.c_int, C.POINTER(RayStateStruct), C.c_int, vp, C.c_int,
+                                                              C.POINTER(DepProfileStruct), vp, vp]
+        lib.rays_hip_window_profiles_kernel_name_for.restype = C.c_char_p
+        lib.rays_hip_window_profiles_kernel_name_for.argtypes = [pp, C.c_int, C.c_int]
     lib.rays_hip_ode_step_device.restype = C.c_int
     lib.rays_hip_ode_step_device.argtypes = [pp, C.c_int, vp, vp, vp, vp, vp, vp]
     lib.rays_hip_pack_device.restype = C.c_int
@@ -847,6 +855,25 @@ def state_summary_device(p: RaysParams, nray: int, state, d_npoints: int, d_stop
     _check(load().rays_hip_state_summary_device(C.byref(p), int(nray), C.byref(st), d_npoints or None, d_stop_code or None,
                                                 d_end_ray_vec or None, d_end_residuals or None, d_max_residuals or None,
                                                 stream or None), "rays_hip_state_summary_device")
+
+
+def window_profiles_kernel_name(p: RaysParams, nray: int, n_profiles: int) -> str:
+    """Kernel rays_hip_trace_window_profiles_device would launch for n_profiles records (the fused deposition kernel's
+    name with EQ + 128); "" where there is none."""
+    return load().rays_hip_window_profiles_kernel_name_for(C.byref(p), int(nray), int(n_profiles)).decode()
+
+
+def trace_window_profiles_device(p: RaysParams, nray: int, state, n_steps: int, d_power: int, records,
+                                 d_npoints_win: int, stream: int = 0):
+    """rays_hip_trace_window_profiles_device: a summary-policy window that bins every point it accepts.  records =
+    [(which, n_bins, d_work, d_profile_in, d_profile), ...], one or two; each work is an accumulator the call never
+    zeroes; d_profile 0 = no sum in this window.  Asynchronous on `stream`."""
+    arr = _profile_records(records)
+    ensure_tables(p)
+    st = _state_struct(state)
+    _check(load().rays_hip_trace_window_profiles_device(C.byref(p), int(nray), C.byref(st), int(n_steps), d_power or None,
+                                                        len(records), arr, d_npoints_win or None, stream or None),
+           "rays_hip_trace_window_profiles_device")
 
 
 def trace_windowed_host(p: RaysParams, rvec0, rindex_vec0, n_steps: int, ngpu: int = 0, out: dict = None) -> dict:

@@ -261,6 +261,142 @@ def _profile_list(params: RaysParams, deposition, n_bins, who: str):
     return specs
 
 
+class WindowedDeposition:
+    """Deposition windows (rays_hip_trace_window_profiles_device): a damped fan advanced in windows of at most n_steps
+    recorded steps per ray, every accepted point binned into one or two profiles, no trajectory anywhere.  The saved
+    RayState and the work rows are all a run needs to go on -- in this process or, through save() / load(), in another.
+    deposition=[(which, n_bins), ...] or "all" with n_bins=n, as DeviceTrace takes them; ray_power: one weight per ray.
+    .works[k] is [n_bins][nray] (bin-major), an accumulator zeroed by launch() alone; .profiles[k] is the ray-ordered sum
+    over works[k] so far, continued from profile_in[k] (None = from zero), as of the last advance(profiles=True).
+    state= / works= continue tensors the caller holds instead of allocating them (then do not call launch()).
+    All launches are asynchronous on the current torch stream.  Once every ray has ended, advance() changes nothing."""
+
+    def __init__(self, params: RaysParams, rvec0, rindex_vec0, deposition=None, ray_power=None,
+                 n_bins: Optional[int] = None, state: Optional[RayState] = None, works=None, profile_in=None, device=None):
+        import torch
+
+        self.torch = torch
+        self.params = params
+        hip.check_params(params)
+        if deposition is None or not _is_profile_list(deposition):
+            raise ValueError('WindowedDeposition: deposition=[(which, n_bins), ...] or "all" (with n_bins=n)')
+        self.deposition = _profile_list(params, deposition, n_bins, "WindowedDeposition")
+        self.nray = len(rvec0)
+        if ray_power is None:
+            raise ValueError("WindowedDeposition: needs ray_power= (one weight per ray)")
+        if len(ray_power) != self.nray:
+            raise ValueError("WindowedDeposition: ray_power must hold one weight per ray")
+        k = len(self.deposition)
+        if profile_in is not None and (not isinstance(profile_in, (list, tuple)) or len(profile_in) != k):
+            raise ValueError("WindowedDeposition: profile_in is a list with one entry (a tensor or None) per profile")
+        if works is not None and (not isinstance(works, (list, tuple)) or len(works) != k or any(
+                tuple(w.shape) != (nb, self.nray) for w, (_, nb) in zip(works, self.deposition))):
+            raise ValueError("WindowedDeposition: works= is a list with one tensor [n_bins][nray] per profile")
+        nv = params.nv
+        if state is not None and (state.nray != self.nray or state.nv != nv):
+            raise ValueError("WindowedDeposition: state= does not match this fan")
+        self.profile_in = profile_in
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        f64, i32, dev = torch.float64, torch.int32, self.device
+        put = lambda a: (a.to(device=dev, dtype=f64).contiguous() if torch.is_tensor(a)
+                         else torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64)).to(dev))
+        self.rvec0, self.rindex_vec0, self.power = put(rvec0), put(rindex_vec0), put(ray_power)
+        self.state = state if state is not None else RayState(self.nray, nv, device=dev)
+        self.works = (list(works) if works is not None
+                      else [torch.zeros((nb, self.nray), dtype=f64, device=dev) for _, nb in self.deposition])
+        self.profiles = [torch.zeros(nb, dtype=f64, device=dev) for _, nb in self.deposition]
+        self.npoints_win = torch.zeros(self.nray, dtype=i32, device=dev)
+        self.start_ray_vec = torch.zeros((self.nray, nv), dtype=f64, device=dev)
+        self._start_known = False   # launch() fills start_ray_vec; a continued state gets it in results()
+        self.npoints = torch.zeros(self.nray, dtype=i32, device=dev)
+        self.stop_code = torch.zeros(self.nray, dtype=i32, device=dev)
+        self.end_ray_vec = torch.zeros((self.nray, nv), dtype=f64, device=dev)
+        self.end_residuals = torch.zeros(self.nray, dtype=f64, device=dev)
+        self.max_residuals = torch.zeros(self.nray, dtype=f64, device=dev)
+
+    def _stream(self, who: str) -> int:
+        if self.device.type != "cuda":
+            raise RuntimeError(f"WindowedDeposition.{who}: this object lives on {self.device}; the kernels need a GPU "
+                               "(there is no CPU fallback)")
+        return self.torch.cuda.current_stream(self.device).cuda_stream
+
+    def launch(self):
+        """Every ray at its launch point (rays_hip_state_init_device) and every work row zero."""
+        stream = self._stream("launch")
+        hip.state_init_device(self.params, self.nray, self.rvec0.data_ptr(), self.rindex_vec0.data_ptr(), self.state,
+                              self.start_ray_vec.data_ptr(), stream=stream)
+        self._start_known = True
+        for w in self.works:
+            w.zero_()
+
+    def advance(self, n_steps: int, profiles: bool = True):
+        """One deposition window of at most n_steps recorded steps per ray; profiles=False leaves the profile sums out
+        (an intermediate window need not pay for them).  Returns npoints_win[nray], overwritten by the next advance()."""
+        n = int(n_steps)
+        if n < 1:
+            raise ValueError("WindowedDeposition.advance: n_steps must be >= 1")
+        stream = self._stream("advance")
+        pin = self.profile_in or [None] * len(self.deposition)
+        records = [(w, nb, work.data_ptr(), None if c is None else c.data_ptr(), prof.data_ptr() if profiles else None)
+                   for (w, nb), work, c, prof in zip(self.deposition, self.works, pin, self.profiles)]
+        hip.trace_window_profiles_device(self.params, self.nray, self.state, n, self.power.data_ptr(), records,
+                                         self.npoints_win.data_ptr(), stream=stream)
+        return self.npoints_win
+
+    def results(self):
+        """A list of RayDeposition (one per profile) on the state's RaySummaries; rays under way are included as they
+        stand.  The profiles are those of the last advance(profiles=True).  Blocking."""
+        t = self.torch
+        stream = self._stream("results")
+        if not self._start_known:   # a continued state: point 1 of every ray, from a scratch state
+            scratch = RayState(self.nray, self.params.nv, device=self.device)
+            hip.state_init_device(self.params, self.nray, self.rvec0.data_ptr(), self.rindex_vec0.data_ptr(), scratch,
+                                  self.start_ray_vec.data_ptr(), stream=stream)
+            self._start_known = True
+        hip.state_summary_device(self.params, self.nray, self.state, self.npoints.data_ptr(), self.stop_code.data_ptr(),
+                                 self.end_ray_vec.data_ptr(), self.end_residuals.data_ptr(),
+                                 self.max_residuals.data_ptr(), stream=stream)
+        t.cuda.synchronize(self.device)
+        c = lambda x: x.cpu().numpy()
+        summ = RaySummaries(c(self.npoints), c(self.stop_code), c(self.start_ray_vec), c(self.end_ray_vec),
+                            c(self.end_residuals), c(self.max_residuals))
+        return [RayDeposition(summ, w, nb, *deposition_grid_limits(self.params, w), c(prof),
+                              np.ascontiguousarray(c(work).T))
+                for (w, nb), work, prof in zip(self.deposition, self.works, self.profiles)]
+
+    def save(self, path: str):
+        """One npz file: the seven state arrays, every work (work_0, work_1), ray_power and the (which, n_bins) list
+        (blocking: the tensors are copied to the host)."""
+        arrays = self.state.numpy()
+        for k, w in enumerate(self.works):
+            arrays[f"work_{k}"] = w.cpu().numpy()
+        arrays["ray_power"] = self.power.cpu().numpy()
+        arrays["which"] = np.array([w for w, _ in self.deposition])
+        arrays["n_bins"] = np.array([nb for _, nb in self.deposition], dtype=np.int32)
+        with open(path, "wb") as f:
+            np.savez(f, **arrays)
+
+    @classmethod
+    def load(cls, path: str, params: RaysParams, rvec0, rindex_vec0, device=None) -> "WindowedDeposition":
+        """A run saved by save(), in fresh tensors on `device`, ready for advance()."""
+        import torch
+
+        with np.load(path, allow_pickle=False) as z:
+            specs = [(str(w), int(nb)) for w, nb in zip(z["which"], z["n_bins"])]
+            wd = cls(params, rvec0, rindex_vec0, deposition=specs, ray_power=z["ray_power"], device=device)
+            for name, dt in RayState.FIELDS:
+                a = np.ascontiguousarray(z[name], dtype=dt)
+                if a.shape != tuple(getattr(wd.state, name).shape):
+                    raise ValueError(f"WindowedDeposition.load: {name} has shape {a.shape}")
+                getattr(wd.state, name).copy_(torch.as_tensor(a))
+            for k, w in enumerate(wd.works):
+                a = np.ascontiguousarray(z[f"work_{k}"], dtype=np.float64)
+                if a.shape != tuple(w.shape):
+                    raise ValueError(f"WindowedDeposition.load: work_{k} has shape {a.shape}")
+                w.copy_(torch.as_tensor(a))
+        return wd
+
+
 def load_axisym_tables(namelist_path: str, nml: Dict[str, Dict[str, Any]]) -> Optional[Dict[str, Any]]:
     """Host-built spline tables of an eqdsk equilibrium: `<eqdsk_file_name>.tables.npz` next to the
     namelist (None for the analytic equilibria)."""
@@ -456,7 +592,8 @@ class DeviceTrace:
         self.state = self.npoints_win = None
         if self.window is not None:
             if deposition is not None:
-                raise ValueError("DeviceTrace: window=... does not go with deposition=... (the fused variant is not continued)")
+                raise ValueError("DeviceTrace: window=... does not go with deposition=... (deposition windows are a class "
+                                 "of their own: WindowedDeposition)")
             if self.window < 1:
                 raise ValueError("DeviceTrace: window must be >= 1")
         elif state is not None:
