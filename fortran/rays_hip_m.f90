@@ -425,6 +425,43 @@
           integer(c_int), intent(out) :: which(*)
        end function rays_hip_deposition_profile_set
 
+       ! Segmented deposition (include/rays_hip.h): the ray-ordered profile sum per SEGMENT of rays -- segment s is the
+       ! rays off(s) .. off(s+1)-1 (zero-based, int32 on the device), or s*rays_per_seg .. with d_seg_offsets = c_null_ptr
+       ! -- on its own, behind the fused ds scan (ray_scan: every run binned while it is traced, one launch), and behind a
+       ! fused pass over many beams.  Device pointers; asynchronous on hip_stream.
+       integer(c_int) function rays_hip_profile_sum_segments_device(n_bins, nray, n_seg, d_seg_offsets, rays_per_seg, &
+                    & d_work, d_profile_in, d_profile_out, hip_stream) bind(C, name='rays_hip_profile_sum_segments_device')
+          import :: c_int, c_ptr
+          integer(c_int), value :: n_bins, nray, n_seg, rays_per_seg
+          type(c_ptr), value :: d_seg_offsets, d_work, d_profile_in, d_profile_out, hip_stream
+       end function rays_hip_profile_sum_segments_device
+
+       ! d_rvec0, d_rindex_vec0, d_initial_ray_power: per fan member (nray); each record's work is [n_bins][n_runs*nray],
+       ! its profile and profile_in [n_runs][n_bins]; the summaries are [n_runs*nray]
+       integer(c_int) function rays_hip_scan_profiles_device(p, n_runs, d_ds_values, nray, d_rvec0, d_rindex_vec0, &
+                    & d_initial_ray_power, n_profiles, profiles, d_npoints, d_stop_code, d_start_ray_vec, d_end_ray_vec, &
+                    & d_end_residuals, d_max_residuals, hip_stream) bind(C, name='rays_hip_scan_profiles_device')
+          import :: c_int, c_ptr, rays_params_t, rays_dep_profile_t
+          type(rays_params_t), intent(in) :: p
+          integer(c_int), value :: n_runs, nray, n_profiles
+          type(rays_dep_profile_t), intent(in) :: profiles(*)
+          type(c_ptr), value :: d_ds_values, d_rvec0, d_rindex_vec0, d_initial_ray_power, d_npoints, d_stop_code
+          type(c_ptr), value :: d_start_ray_vec, d_end_ray_vec, d_end_residuals, d_max_residuals, hip_stream
+       end function rays_hip_scan_profiles_device
+
+       ! rays_hip_trace_profiles_device with one profile per segment: profile and profile_in are [n_seg][n_bins]
+       integer(c_int) function rays_hip_trace_profiles_segments_device(p, nray, d_rvec0, d_rindex_vec0, &
+                    & d_initial_ray_power, n_profiles, profiles, n_seg, d_seg_offsets, rays_per_seg, d_npoints, &
+                    & d_stop_code, d_start_ray_vec, d_end_ray_vec, d_end_residuals, d_max_residuals, hip_stream) &
+                    & bind(C, name='rays_hip_trace_profiles_segments_device')
+          import :: c_int, c_ptr, rays_params_t, rays_dep_profile_t
+          type(rays_params_t), intent(in) :: p
+          integer(c_int), value :: nray, n_profiles, n_seg, rays_per_seg
+          type(rays_dep_profile_t), intent(in) :: profiles(*)
+          type(c_ptr), value :: d_rvec0, d_rindex_vec0, d_initial_ray_power, d_seg_offsets, d_npoints, d_stop_code
+          type(c_ptr), value :: d_start_ray_vec, d_end_ray_vec, d_end_residuals, d_max_residuals, hip_stream
+       end function rays_hip_trace_profiles_segments_device
+
        ! (c_ptr to a NUL-terminated name, as the other *_kernel_name_for)
        type(c_ptr) function rays_hip_profiles_kernel_name_for(p, nray, n_profiles) &
                     & bind(C, name='rays_hip_profiles_kernel_name_for')

@@ -370,8 +370,9 @@ const char* rays_hip_summary_kernel_name_for(const rays_params_t* p, int nray);
  * row; equilib_model = solovev; Ptotal_psi / Ptotal_rho on a slab, Ptotal_x on axisym_toroid; Ptotal_rho without
  * rays_hip_set_rho_table or for the two magnetics models without rho; n_bins outside 1..RAYS_DEP_MAX_BINS; a null
  * required pointer; nray < 0; a shape that is not built (the message of rays_hip_check_params).
- * OUT OF SCOPE here: the fused ds scan, a tolerance variant, more than RAYS_DEP_MAX_BINS (320) bins.  (Several profiles
- * in one pass: rays_hip_trace_profiles* below.) */
+ * OUT OF SCOPE here: a tolerance variant, more than RAYS_DEP_MAX_BINS (320) bins.  (Several profiles in one pass:
+ * rays_hip_trace_profiles* below; the fused ds scan and one profile per beam: rays_hip_scan_profiles_device and
+ * rays_hip_trace_profiles_segments_device further below.) */
 int rays_hip_trace_deposition_device(const rays_params_t* p, int nray, const double* d_rvec0,
                                      const double* d_rindex_vec0, const double* d_initial_ray_power, int which,
                                      int n_bins, int32_t* d_npoints, int32_t* d_stop_code,
@@ -439,6 +440,66 @@ const char* rays_hip_profiles_kernel_name_for(const rays_params_t* p, int nray, 
  * which[RAYS_DEP_MAX_PROFILES]; returns their number.  Slab: x.  axisym_toroid on the eqdsk splines with a rho table
  * set: psi, rho; the other two magnetics models, or no rho table: psi.  Solovev (or p refused): 0. */
 int rays_hip_deposition_profile_set(const rays_params_t* p, int* which);
+
+/* ---- segmented deposition: the fused ds scan and one profile per beam, in one pass --------------------------------
+ * The fused entries above sum every ray of a launch into ONE profile per record.  Two users want more than one from a
+ * launch: the ds scan (ray_scan: the same fan at n_runs step sizes, each run with a profile of its own, e.g. to see
+ * whether the deposition profile has converged in ds) and the aiming survey (many beams at one ds -- steering angles,
+ * launch positions, the ragged blocks rays_hip_ray_init_device returns -- each beam with its own profile).  The trace
+ * kernels need nothing new for either: every ray owns its column of work, and the step of a ray was already
+ * ds_values[ray / rays_per_run] in a scan launch.  What these entries add is the ray-ordered sum PER SEGMENT of rays.
+ *   A segment s is the rays off[s] .. off[s+1]-1, off an int32 DEVICE array of n_seg + 1 entries; or, with
+ *   d_seg_offsets == NULL, the rays s * rays_per_seg .. (s + 1) * rays_per_seg - 1.
+ *   profile[s][b] = carry[s][b] + work[b][off[s]] + work[b][off[s]+1] + ... + work[b][off[s+1]-1]
+ * with the adds in exactly that order and nothing else added.  An empty segment gives carry[s][b], or +0.0 without a
+ * carry (d_profile_in == NULL starts every sum from +0.0; d_profile_in == d_profile_out is allowed).  Every offset is
+ * clamped to [0, nray] on the device and end < start counts as empty, so no offset value makes the sum read outside
+ * work; rays before off[0] and from off[n_seg] on belong to no profile.
+ * RELATION TO THE SINGLE SUM: the kernel of the entries above pads its last chunk of rays with +0.0, which shows only
+ * when a caller's profile_in holds -0.0 (-0.0 + +0.0 = +0.0); the segmented sum adds nothing but the segment's rays.  For
+ * carries that are not -0.0, one segment [0, nray] equals those entries' profile bit for bit.
+ * All three entries are asynchronous on hip_stream, always run the EXACT kernels, and follow the fused entries' rule:
+ * one caller thread per (device, stream).
+ *
+ * rays_hip_profile_sum_segments_device: the sum on its own, e.g. behind rays_hip_deposition_device on the trajectories of
+ * a scan or of a many-beam fan, from the work it already wrote.  d_work is [n_bins][nray]; d_profile_in (may be NULL)
+ * and d_profile_out are [n_seg][n_bins].  n_seg == 0 does nothing.
+ *
+ * rays_hip_scan_profiles_device: the fused ds scan.  d_rvec0, d_rindex_vec0 and d_initial_ray_power are per fan member
+ * ([nray]), as in rays_hip_scan_summary_device; ray r * nray + i is member i at step d_ds_values[r].  Each record's
+ * work is [n_bins][n_runs * nray] (run r owns the columns r * nray ..), its profile and profile_in [n_runs][n_bins]; the
+ * summaries are [n_runs * nray].  The call zeroes each work, tiles the power to one weight per ray in a workspace kept
+ * per (device, stream) (grown on demand, released by rays_hip_finalize), launches the fused kernel of one or two
+ * profiles with the per-run steps, and sums per run.  Run r is bit for bit what rays_hip_trace_profiles_device gives
+ * with ds = d_ds_values[r]; profile_in chains the member blocks of a fan per run.  n_runs == 0 does nothing; nray == 0
+ * writes profile_in, or zeros.
+ *
+ * rays_hip_trace_profiles_segments_device: the arguments of rays_hip_trace_profiles_device and the segments: the same
+ * fused pass at the run's one ds, with profile and profile_in of each record [n_seg][n_bins].  work is that entry's.
+ *
+ * Refused by name, before anything is allocated or launched: everything rays_hip_trace_profiles_device refuses; n_runs
+ * < 0; n_runs * nray beyond 2^31 - 1; a null d_ds_values; n_seg < 0; neither offsets nor a positive rays_per_seg when
+ * n_seg > 0; (the sum alone) n_bins < 1, nray < 0, a null work or profile.
+ * OUT OF SCOPE: host-pointer (sharded) forms, windows over a scan, a tolerance variant, a scan parameter other than ds. */
+int rays_hip_profile_sum_segments_device(int n_bins, int nray, int n_seg, const int32_t* d_seg_offsets /* may be NULL */,
+                                         int rays_per_seg, const double* d_work /* [n_bins][nray] */,
+                                         const double* d_profile_in /* [n_seg][n_bins] or NULL */,
+                                         double* d_profile_out /* [n_seg][n_bins] */, void* hip_stream);
+int rays_hip_scan_profiles_device(const rays_params_t* p, int n_runs, const double* d_ds_values, int nray,
+                                  const double* d_rvec0, const double* d_rindex_vec0,
+                                  const double* d_initial_ray_power /* [nray], per fan member */, int n_profiles,
+                                  const rays_dep_profile_t* profiles /* host array of device pointers */,
+                                  int32_t* d_npoints, int32_t* d_stop_code, double* d_start_ray_vec /* may be NULL */,
+                                  double* d_end_ray_vec, double* d_end_residuals, double* d_max_residuals,
+                                  void* hip_stream);
+int rays_hip_trace_profiles_segments_device(const rays_params_t* p, int nray, const double* d_rvec0,
+                                            const double* d_rindex_vec0, const double* d_initial_ray_power,
+                                            int n_profiles,
+                                            const rays_dep_profile_t* profiles /* host array of device pointers */,
+                                            int n_seg, const int32_t* d_seg_offsets /* may be NULL */, int rays_per_seg,
+                                            int32_t* d_npoints, int32_t* d_stop_code,
+                                            double* d_start_ray_vec /* may be NULL */, double* d_end_ray_vec,
+                                            double* d_end_residuals, double* d_max_residuals, void* hip_stream);
 
 /* ---- windowed tracing: pause rays after n steps, continue from a saved state ---------------------------------------
  * Every entry above runs a ray from its launch point to its end in one launch, so whoever wants trajectories holds

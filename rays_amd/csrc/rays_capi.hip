@@ -50,6 +50,11 @@ __attribute__((weak)) hipError_t launch_dep_trace_args(const DepTraceArgs& T, De
 __attribute__((weak)) hipError_t launch_dep2_trace_args(const Dep2TraceArgs& T, Dep2TraceArgs* d_out, hipStream_t s);
 __attribute__((weak)) hipError_t launch_profile_sum(int n_bins, int nray, const double* work, const double* carry,
                                                     double* profile, hipStream_t s);
+__attribute__((weak)) hipError_t launch_profile_sum_segments(int n_bins, int nray, int n_seg, const int* d_off,
+                                                             int rays_per_seg, const double* work, const double* carry,
+                                                             double* profile, hipStream_t s);
+__attribute__((weak)) hipError_t launch_tile_power(int nray, long long total, const double* power, double* power_runs,
+                                                   hipStream_t s);
 struct FanArgs;
 hipError_t launch_ray_init(int eq_model, int ns, const DevParams& P, const FanArgs& F, int n_cand, double* cand,
                            int* keep, int* block_count, int* offs, int* first_of_launch, double* rvec0,
@@ -370,6 +375,13 @@ StreamWorkspace g_step_ws;
 // rewritten on the stream before every launch that reads it.
 StreamWorkspace g_dep_ws;
 StreamWorkspace g_dep2_ws;   // the same for the Dep2TraceArgs block of a two-profile launch (rays_hip_trace_profiles*)
+// A fused ds scan (rays_hip_scan_profiles_device) keeps its tiled power weights in the same block, kDepArgsRoom bytes
+// behind the argument block: one weight per ray of the launch.
+constexpr size_t kDepArgsRoom = 128;
+struct ScanPart {
+  const double* ds_run;  // [n_runs] on the device
+  int members;           // rays per run: `in` holds one start and one weight per fan member
+};
 // Neighbourhood size of that order: every second row of 64 rays is traced first (cfg 5b: 4.05 | 3.26 | 3.34 | 3.42 ms for
 // index order | 2 | 4 | 8; the model of tools/refill_model.py agrees: the more pilots, the better the later half is
 // ordered).  RAYS_HIP_RAY_ORDER=index hands the rays out in index order instead (for A/B measurements; the results
@@ -1750,8 +1762,11 @@ static int refuse_trace_deposition(const char* who, const rays_params_t* p, int 
 }
 
 // zero work, the DepTraceArgs block, the fused trace (in.power: the rays' initial power).  Arguments already checked.
+// scan: nray = n_runs * scan->members rays, ray r * members + i being member i at step scan->ds_run[r]; its weights are
+// tiled into the workspace behind the argument block.
 static int trace_deposition_launch(const rays_params_t* p, int nray, const RayInputs& in, int which, int n_bins,
-                                   const SummaryArrays& out, double* d_work, hipStream_t stream) {
+                                   const SummaryArrays& out, double* d_work, hipStream_t stream,
+                                   const ScanPart* scan = nullptr) {
   rays::DepTraceArgs T;
   T.which = which;
   T.n_bins = n_bins;
@@ -1760,12 +1775,23 @@ static int trace_deposition_launch(const rays_params_t* p, int nray, const RayIn
   T.pad_ = 0;
   int rc = fill_deposition_grid(p, which, &T);
   if (rc) return rc;
-  rays::DepTraceArgs* d_T = nullptr;
-  HIP_TRY_AS("hipMalloc (deposition arguments)", g_dep_ws.get(stream, sizeof(rays::DepTraceArgs), (void**)&d_T));
+  static_assert(sizeof(rays::DepTraceArgs) <= kDepArgsRoom, "the argument block fits its room");
+  char* ws = nullptr;
+  const size_t bytes = scan ? kDepArgsRoom + sizeof(double) * (size_t)nray : sizeof(rays::DepTraceArgs);
+  HIP_TRY_AS("hipMalloc (deposition arguments)", g_dep_ws.get(stream, bytes, (void**)&ws));
+  rays::DepTraceArgs* d_T = reinterpret_cast<rays::DepTraceArgs*>(ws);
   HIP_TRY(hipMemsetAsync(d_work, 0, sizeof(double) * (size_t)n_bins * (size_t)nray, stream));
+  TraceExtras x;
+  if (scan) {
+    double* power_runs = reinterpret_cast<double*>(ws + kDepArgsRoom);
+    const hipError_t et = rays::launch_tile_power(scan->members, nray, in.power, power_runs, stream);
+    if (et != hipSuccess) return hip_fail(et, "power tiling kernel");
+    T.power = power_runs;
+    x.ds_run = scan->ds_run;
+    x.rays_per_run = scan->members;
+  }
   hipError_t e = rays::launch_dep_trace_args(T, d_T, stream);
   if (e != hipSuccess) return hip_fail(e, "deposition arguments kernel");
-  TraceExtras x;
   x.dep = d_T;
   return launch_trace(p, KernelVariant::Deposit, nray, in, {}, out, stream, RAYS_TRACE_NO_ZERO_FILL, x);
 }
@@ -1912,7 +1938,8 @@ static int refuse_trace_profiles(const char* who, const rays_params_t* p, int nr
 
 // zero both work arrays, the Dep2TraceArgs block, the two-profile trace.  Arguments already checked.
 static int trace_profiles_launch(const rays_params_t* p, int nray, const RayInputs& in, const rays_dep_profile_t* pr,
-                                 double* const d_work[2], const SummaryArrays& out, hipStream_t stream) {
+                                 double* const d_work[2], const SummaryArrays& out, hipStream_t stream,
+                                 const ScanPart* scan = nullptr) {
   rays::Dep2TraceArgs T;
   T.power = in.power;
   T.rho_grid = nullptr; T.rho_fspl = nullptr; T.n_rho = 0; T.pad_ = 0;
@@ -1927,13 +1954,24 @@ static int trace_profiles_launch(const rays_params_t* p, int nray, const RayInpu
     T.prof[i].work = d_work[i];
     if (pr[i].which == RAYS_DEP_PTOTAL_RHO) { T.rho_grid = G.rho_grid; T.rho_fspl = G.rho_fspl; T.n_rho = G.n_rho; }
   }
-  rays::Dep2TraceArgs* d_T = nullptr;
-  HIP_TRY_AS("hipMalloc (deposition arguments)", g_dep2_ws.get(stream, sizeof(rays::Dep2TraceArgs), (void**)&d_T));
+  static_assert(sizeof(rays::Dep2TraceArgs) <= kDepArgsRoom, "the argument block fits its room");
+  char* ws = nullptr;
+  const size_t bytes = scan ? kDepArgsRoom + sizeof(double) * (size_t)nray : sizeof(rays::Dep2TraceArgs);
+  HIP_TRY_AS("hipMalloc (deposition arguments)", g_dep2_ws.get(stream, bytes, (void**)&ws));
+  rays::Dep2TraceArgs* d_T = reinterpret_cast<rays::Dep2TraceArgs*>(ws);
   for (int i = 0; i < 2; i++)
     HIP_TRY(hipMemsetAsync(d_work[i], 0, sizeof(double) * (size_t)pr[i].n_bins * (size_t)nray, stream));
+  TraceExtras x;
+  if (scan) {  // (as in trace_deposition_launch)
+    double* power_runs = reinterpret_cast<double*>(ws + kDepArgsRoom);
+    const hipError_t et = rays::launch_tile_power(scan->members, nray, in.power, power_runs, stream);
+    if (et != hipSuccess) return hip_fail(et, "power tiling kernel");
+    T.power = power_runs;
+    x.ds_run = scan->ds_run;
+    x.rays_per_run = scan->members;
+  }
   const hipError_t e = rays::launch_dep2_trace_args(T, d_T, stream);
   if (e != hipSuccess) return hip_fail(e, "deposition arguments kernel");
-  TraceExtras x;
   x.dep2 = d_T;
   return launch_trace(p, KernelVariant::Deposit2, nray, in, {}, out, stream, RAYS_TRACE_NO_ZERO_FILL, x);
 }
@@ -1982,6 +2020,105 @@ const char* rays_hip_profiles_kernel_name_for(const rays_params_t* p, int nray, 
   if (!p || n_profiles < 1 || n_profiles > RAYS_DEP_MAX_PROFILES || rays_hip_check_params(p)) return "";
   const rays::KernelEntry* k = find_kernel(*p, nray, n_profiles == 2 ? KernelVariant::Deposit2 : KernelVariant::Deposit);
   return k ? k->name : "";
+}
+
+// ---- segmented deposition: the fused ds scan and one profile per beam (include/rays_hip.h) -----------
+static int refuse_segments(const std::string& w, int n_seg, const int32_t* d_seg_offsets, int rays_per_seg) {
+  if (n_seg < 0) return fail(w + ": n_seg < 0");
+  if (n_seg > 0 && !d_seg_offsets && rays_per_seg < 1)
+    return fail(w + ": neither segment offsets nor a positive rays_per_seg");
+  if (!rays::launch_profile_sum_segments) return fail(w + ": the segmented profile sum is not in this build");
+  return 0;
+}
+
+int rays_hip_profile_sum_segments_device(int n_bins, int nray, int n_seg, const int32_t* d_seg_offsets, int rays_per_seg,
+                                         const double* d_work, const double* d_profile_in, double* d_profile_out,
+                                         void* hip_stream) {
+  const std::string w = "rays_hip_profile_sum_segments_device";
+  if (n_bins < 1) return fail(w + ": n_bins < 1");
+  if (nray < 0) return fail(w + ": nray < 0");
+  const int rc = refuse_segments(w, n_seg, d_seg_offsets, rays_per_seg);
+  if (rc) return rc;
+  if (n_seg == 0) return 0;
+  if ((nray > 0 && !d_work) || !d_profile_out) return fail(w + ": null work or profile");
+  const hipError_t e = rays::launch_profile_sum_segments(n_bins, nray, n_seg, d_seg_offsets, rays_per_seg, d_work,
+                                                         d_profile_in, d_profile_out, (hipStream_t)hip_stream);
+  if (e != hipSuccess) return hip_fail(e, "segmented profile sum kernel");
+  return 0;
+}
+
+// The fused pass of one or two profiles over `total` rays -- a scan's n_runs * members, or a fan as it is -- and the sums
+// per segment.  Arguments already checked.
+static int trace_profiles_segments(const char* who, const rays_params_t* p, int total, const RayInputs& in, int n_profiles,
+                                   const rays_dep_profile_t* profiles, const SummaryArrays& out, const ScanPart* scan,
+                                   int n_seg, const int32_t* d_seg_offsets, int rays_per_seg, hipStream_t stream) {
+  if (total > 0) {
+    if (!in.rvec0 || !in.rindex_vec0 || !in.power || !out.np || !out.sc || !out.ev || !out.er || !out.mr)
+      return fail(std::string(who) + ": null device pointer");
+    int rc = 0;
+    if (n_profiles == 1) {
+      rc = trace_deposition_launch(p, total, in, profiles[0].which, profiles[0].n_bins, out, profiles[0].work, stream, scan);
+    } else {
+      double* const d_work[2] = {profiles[0].work, profiles[1].work};
+      rc = trace_profiles_launch(p, total, in, profiles, d_work, out, stream, scan);
+    }
+    if (rc) return rc;
+  }
+  for (int i = 0; i < n_profiles; i++) {  // + the ray-ordered sums per segment, each continued from its own carry
+    const hipError_t e = rays::launch_profile_sum_segments(profiles[i].n_bins, total, n_seg, d_seg_offsets, rays_per_seg,
+                                                           profiles[i].work, profiles[i].profile_in, profiles[i].profile,
+                                                           stream);
+    if (e != hipSuccess) return hip_fail(e, "segmented profile sum kernel");
+  }
+  return 0;
+}
+
+int rays_hip_scan_profiles_device(const rays_params_t* p, int n_runs, const double* d_ds_values, int nray,
+                                  const double* d_rvec0, const double* d_rindex_vec0, const double* d_initial_ray_power,
+                                  int n_profiles, const rays_dep_profile_t* profiles, int32_t* d_npoints,
+                                  int32_t* d_stop_code, double* d_start_ray_vec, double* d_end_ray_vec,
+                                  double* d_end_residuals, double* d_max_residuals, void* hip_stream) {
+  const char* who = "rays_hip_scan_profiles_device";
+  const std::string w(who);
+  int rc = refuse_trace_profiles(who, p, nray, n_profiles, profiles);
+  if (rc) return rc;
+  if (n_runs < 0) return fail(w + ": n_runs < 0");
+  if ((long long)n_runs * nray > 0x7fffffffll) return fail(w + ": n_runs * nray exceeds 2^31 - 1");
+  if (n_runs > 0 && !d_ds_values) return fail(w + ": null d_ds_values");
+  rc = refuse_segments(w, n_runs, nullptr, nray > 0 ? nray : 1);
+  if (rc) return rc;
+  if (!rays::launch_tile_power) return fail(w + ": the power tiling kernel is not in this build");
+  for (int i = 0; i < n_profiles; i++)
+    if (!profiles[i].work || !profiles[i].profile) return fail(w + ": null work or profile");
+  if (n_runs == 0) return 0;
+  const int total = n_runs * nray;
+  // (the kernel is chosen for the launch's ray count, not for one run's)
+  if (total > 0 && !find_kernel(*p, total, n_profiles == 2 ? KernelVariant::Deposit2 : KernelVariant::Deposit))
+    return fail(w + ": the fused deposition kernel of this configuration is not in this build");
+  const ScanPart scan = {d_ds_values, nray};
+  // (nray == 0: every run is an empty segment of no rays -- profile_in, or zeros)
+  return trace_profiles_segments(who, p, total, {d_rvec0, d_rindex_vec0, d_initial_ray_power}, n_profiles, profiles,
+                                 {d_npoints, d_stop_code, d_start_ray_vec, d_end_ray_vec, d_end_residuals, d_max_residuals},
+                                 &scan, n_runs, nullptr, nray > 0 ? nray : 1, (hipStream_t)hip_stream);
+}
+
+int rays_hip_trace_profiles_segments_device(const rays_params_t* p, int nray, const double* d_rvec0,
+                                            const double* d_rindex_vec0, const double* d_initial_ray_power, int n_profiles,
+                                            const rays_dep_profile_t* profiles, int n_seg, const int32_t* d_seg_offsets,
+                                            int rays_per_seg, int32_t* d_npoints, int32_t* d_stop_code,
+                                            double* d_start_ray_vec, double* d_end_ray_vec, double* d_end_residuals,
+                                            double* d_max_residuals, void* hip_stream) {
+  const char* who = "rays_hip_trace_profiles_segments_device";
+  const std::string w(who);
+  int rc = refuse_trace_profiles(who, p, nray, n_profiles, profiles);
+  if (rc) return rc;
+  rc = refuse_segments(w, n_seg, d_seg_offsets, rays_per_seg);
+  if (rc) return rc;
+  for (int i = 0; i < n_profiles; i++)
+    if (!profiles[i].work || (n_seg > 0 && !profiles[i].profile)) return fail(w + ": null work or profile");
+  return trace_profiles_segments(who, p, nray, {d_rvec0, d_rindex_vec0, d_initial_ray_power}, n_profiles, profiles,
+                                 {d_npoints, d_stop_code, d_start_ray_vec, d_end_ray_vec, d_end_residuals, d_max_residuals},
+                                 nullptr, n_seg, d_seg_offsets, rays_per_seg, (hipStream_t)hip_stream);
 }
 
 // ---- deposition windows: the fused kernels continued from a saved ray state (include/rays_hip.h) ----

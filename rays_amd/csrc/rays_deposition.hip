@@ -52,6 +52,74 @@ profile_sum_kernel(int n_bins, int nray, const double* __restrict__ work, const 
   if (lane == 0) profile[b] = s;
 }
 
+// The same sum per SEGMENT of rays (the runs of a fused ds scan, the beams of an aiming survey):
+//   profile[s][b] = carry[s][b] + work[b][r0] + work[b][r0 + 1] + ... + work[b][r1 - 1],   r0 = off[s], r1 = off[s + 1]
+// (off == nullptr: r0 = s * rays_per_seg, r1 = r0 + rays_per_seg), the adds in exactly that order and nothing else added:
+// an empty segment gives carry[s][b], or +0.0 without a carry.  One wave per (segment, bin): blockIdx.x + seg0 is the
+// segment, blockIdx.y + bin0 the bin.  The loads start at the segment's first ray, wherever it lies, and the last chunk
+// walks only the lanes that hold rays of this segment, so it neither takes in the next segment's rays nor adds a padding
+// +0.0 (which profile_sum_kernel does: there it shows only when the carry holds -0.0; for every other carry one segment
+// [0, nray] gives that kernel's bits).  Every offset read is clamped to [0, nray] and r1 < r0 counts as empty, so no
+// offset value makes the kernel read outside work.  carry == profile is allowed: each wave reads its one element first.
+__global__ void __launch_bounds__(kDepWave)
+profile_sum_segments_kernel(int n_bins, int nray, int seg0, int bin0, const int* __restrict__ off, int rays_per_seg,
+                            const double* __restrict__ work, const double* carry, double* profile) {
+  constexpr int U = 8;
+  const int seg = seg0 + (int)blockIdx.x, b = bin0 + (int)blockIdx.y, lane = threadIdx.x;
+  long long r0, r1;
+  if (off) {
+    r0 = off[seg];
+    r1 = off[seg + 1];
+  } else {
+    r0 = (long long)seg * rays_per_seg;
+    r1 = r0 + rays_per_seg;
+  }
+  r0 = r0 < 0 ? 0 : r0 > nray ? nray : r0;
+  r1 = r1 < 0 ? 0 : r1 > nray ? nray : r1;
+  if (r1 < r0) r1 = r0;
+  const double* w = work + (long long)b * nray;
+  const long long at = (long long)seg * n_bins + b;
+  double s = carry ? carry[at] : 0.;
+  for (long long base = r0; base < r1; base += U * kDepWave) {
+    double v[U];
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      const long long r = base + u * kDepWave + lane;
+      v[u] = r < r1 ? w[r] : 0.;  // (a lane past the segment's end is never read below)
+    }
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      const long long left = r1 - (base + u * kDepWave);  // wave-uniform
+      if (left <= 0) break;
+      const unsigned lo = (unsigned)__double_as_longlong(v[u]);
+      const unsigned hi = (unsigned)(__double_as_longlong(v[u]) >> 32);
+      if (left >= kDepWave) {
+#pragma unroll
+        for (int l = 0; l < kDepWave; l++) {
+          const unsigned a = __builtin_amdgcn_readlane(lo, l), c = __builtin_amdgcn_readlane(hi, l);
+          s = s + __longlong_as_double((long long)(((unsigned long long)c << 32) | a));
+        }
+      } else {
+        const int n = __builtin_amdgcn_readfirstlane((int)left);
+        for (int l = 0; l < n; l++) {
+          const unsigned a = __builtin_amdgcn_readlane(lo, l), c = __builtin_amdgcn_readlane(hi, l);
+          s = s + __longlong_as_double((long long)(((unsigned long long)c << 32) | a));
+        }
+      }
+    }
+  }
+  if (lane == 0) profile[at] = s;
+}
+
+// power_runs[r][i] = power[i], r = 0..n_runs-1: the per-ray weights of a fused ds scan, whose ray r * nray + i is fan
+// member i (the fused kernels read the weight of a ray at the ray's own index)
+constexpr int kTileBlock = 256;
+__global__ void __launch_bounds__(kTileBlock)
+tile_power_kernel(int nray, long long total, const double* __restrict__ power, double* __restrict__ power_runs) {
+  for (long long i = (long long)blockIdx.x * kTileBlock + threadIdx.x; i < total; i += (long long)gridDim.x * kTileBlock)
+    power_runs[i] = power[i % nray];
+}
+
 // the DepTraceArgs block of a fused trace launch: a by-value kernel argument written to device memory in stream order
 // (no host memory has to outlive the asynchronous call)
 __global__ void __launch_bounds__(kDepWave) dep_trace_args_kernel(const DepTraceArgs T, DepTraceArgs* out) {
@@ -77,6 +145,33 @@ hipError_t launch_dep_trace_args(const DepTraceArgs& T, DepTraceArgs* d_out, hip
 hipError_t launch_profile_sum(int n_bins, int nray, const double* work, const double* carry, double* profile,
                               hipStream_t s) {
   hipLaunchKernelGGL(profile_sum_kernel, dim3(n_bins), dim3(kDepWave), 0, s, n_bins, nray, work, carry, profile);
+  return hipGetLastError();
+}
+
+// profile[s][b] = carry[s][b] + the sum over the rays of segment s of work(b, :) in ray order (see
+// profile_sum_segments_kernel).  d_off: n_seg + 1 offsets on the device, or nullptr with a uniform rays_per_seg.
+// The grid is cut so that neither dimension exceeds what a launch takes.
+hipError_t launch_profile_sum_segments(int n_bins, int nray, int n_seg, const int* d_off, int rays_per_seg,
+                                       const double* work, const double* carry, double* profile, hipStream_t s) {
+  constexpr int kSegChunk = 1 << 20, kBinChunk = 65535;
+  for (int seg0 = 0; seg0 < n_seg; seg0 += kSegChunk)
+    for (int bin0 = 0; bin0 < n_bins; bin0 += kBinChunk) {
+      const int ns = n_seg - seg0 < kSegChunk ? n_seg - seg0 : kSegChunk;
+      const int nb = n_bins - bin0 < kBinChunk ? n_bins - bin0 : kBinChunk;
+      hipLaunchKernelGGL(profile_sum_segments_kernel, dim3(ns, nb), dim3(kDepWave), 0, s, n_bins, nray, seg0, bin0, d_off,
+                         rays_per_seg, work, carry, profile);
+      const hipError_t e = hipGetLastError();
+      if (e != hipSuccess) return e;
+    }
+  return hipSuccess;
+}
+
+// power_runs[n_runs][nray] = power[nray] tiled, in stream order (see tile_power_kernel)
+hipError_t launch_tile_power(int nray, long long total, const double* power, double* power_runs, hipStream_t s) {
+  if (total <= 0 || nray <= 0) return hipSuccess;
+  const long long want = (total + kTileBlock - 1) / kTileBlock;
+  hipLaunchKernelGGL(tile_power_kernel, dim3((unsigned)(want < 4096 ? want : 4096)), dim3(kTileBlock), 0, s, nray, total,
+                     power, power_runs);
   return hipGetLastError();
 }
 

@@ -43,6 +43,7 @@ EXPORTED_SYMBOLS = (
     "rays_hip_state_init_device", "rays_hip_trace_window_device", "rays_hip_state_summary_device",
     "rays_hip_window_kernel_name_for", "rays_hip_trace_windowed",
     "rays_hip_trace_window_profiles_device", "rays_hip_window_profiles_kernel_name_for",
+    "rays_hip_profile_sum_segments_device", "rays_hip_scan_profiles_device", "rays_hip_trace_profiles_segments_device",
 )
 
 _lib = None
@@ -183,6 +184,17 @@ def load():
                                                               C.POINTER(DepProfileStruct), vp, vp]
         lib.rays_hip_window_profiles_kernel_name_for.restype = C.c_char_p
         lib.rays_hip_window_profiles_kernel_name_for.argtypes = [pp, C.c_int, C.c_int]
+    # (likewise the segmented deposition entries -- tools/scan_profiles_bench.py)
+    if hasattr(lib, "rays_hip_scan_profiles_device"):
+        rp = C.POINTER(DepProfileStruct)
+        lib.rays_hip_profile_sum_segments_device.restype = C.c_int
+        lib.rays_hip_profile_sum_segments_device.argtypes = [C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp]
+        lib.rays_hip_scan_profiles_device.restype = C.c_int
+        lib.rays_hip_scan_profiles_device.argtypes = [pp, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, rp, vp, vp, vp, vp, vp,
+                                                      vp, vp]
+        lib.rays_hip_trace_profiles_segments_device.restype = C.c_int
+        lib.rays_hip_trace_profiles_segments_device.argtypes = [pp, C.c_int, vp, vp, vp, C.c_int, rp, C.c_int, vp, C.c_int,
+                                                                vp, vp, vp, vp, vp, vp, vp]
     lib.rays_hip_ode_step_device.restype = C.c_int
     lib.rays_hip_ode_step_device.argtypes = [pp, C.c_int, vp, vp, vp, vp, vp, vp]
     lib.rays_hip_pack_device.restype = C.c_int
@@ -808,6 +820,68 @@ def trace_profiles_host(p: RaysParams, rvec0, rindex_vec0, initial_ray_power, pr
     _check(rc, "rays_hip_trace_profiles")
     out["elapsed_s"] = el.value
     return out
+
+
+def profile_sum_segments(work, segments, profile_in=None, profile_out=None, stream: int = 0):
+    """rays_hip_profile_sum_segments_device on torch CUDA tensors: work[n_bins][nray] (float64, contiguous); segments: an
+    int32 CUDA tensor of n_seg + 1 offsets, or (n_seg, rays_per_seg) for uniform segments; profile_in / profile_out
+    [n_seg][n_bins] (profile_out is allocated when None; the same tensor for both is allowed).  Returns profile_out.
+    Asynchronous on `stream`."""
+    import torch
+
+    if work.dim() != 2 or work.dtype != torch.float64 or not work.is_contiguous() or not work.is_cuda:
+        raise ValueError("profile_sum_segments: work is a contiguous float64 CUDA tensor [n_bins][nray]")
+    n_bins, nray = int(work.shape[0]), int(work.shape[1])
+    if torch.is_tensor(segments):
+        if segments.dtype != torch.int32 or segments.dim() != 1 or not segments.is_contiguous() or not segments.is_cuda or \
+                len(segments) < 1:
+            raise ValueError("profile_sum_segments: offsets are a contiguous int32 CUDA tensor of n_seg + 1 entries")
+        n_seg, d_off, per = len(segments) - 1, segments.data_ptr(), 0
+    else:
+        n_seg, per = (int(x) for x in segments)
+        d_off = None
+    for name, t in (("profile_in", profile_in), ("profile_out", profile_out)):
+        if t is not None and (tuple(t.shape) != (n_seg, n_bins) or t.dtype != torch.float64 or not t.is_contiguous()
+                              or not t.is_cuda):
+            raise ValueError(f"profile_sum_segments: {name} is a contiguous float64 CUDA tensor [n_seg][n_bins]")
+    if profile_out is None:
+        profile_out = torch.empty((max(n_seg, 0), n_bins), dtype=torch.float64, device=work.device)
+    rc = load().rays_hip_profile_sum_segments_device(
+        n_bins, nray, n_seg, d_off, per, work.data_ptr() or None, None if profile_in is None else profile_in.data_ptr(),
+        profile_out.data_ptr() or None, stream or None)
+    _check(rc, "rays_hip_profile_sum_segments_device")
+    return profile_out
+
+
+def scan_profiles_device(p: RaysParams, n_runs: int, d_ds_values: int, nray: int, d_rvec0: int, d_rindex_vec0: int,
+                         d_power: int, records, d_npoints: int, d_stop_code: int, d_start_ray_vec: int,
+                         d_end_ray_vec: int, d_end_residuals: int, d_max_residuals: int, stream: int = 0):
+    """rays_hip_scan_profiles_device: the fused ds scan, raw device pointers (ints).  The starts and d_power are per fan
+    member; records = [(which, n_bins, d_work[n_bins][n_runs * nray], d_profile_in, d_profile[n_runs][n_bins]), ...];
+    the summaries are [n_runs * nray].  Asynchronous on `stream`; every work is zeroed by the call."""
+    arr = _profile_records(records)
+    ensure_tables(p)
+    rc = load().rays_hip_scan_profiles_device(
+        C.byref(p), int(n_runs), d_ds_values or None, int(nray), d_rvec0 or None, d_rindex_vec0 or None, d_power or None,
+        len(records), arr, d_npoints or None, d_stop_code or None, d_start_ray_vec or None, d_end_ray_vec or None,
+        d_end_residuals or None, d_max_residuals or None, stream or None)
+    _check(rc, "rays_hip_scan_profiles_device")
+
+
+def trace_profiles_segments_device(p: RaysParams, nray: int, d_rvec0: int, d_rindex_vec0: int, d_power: int, records,
+                                   n_seg: int, d_seg_offsets, rays_per_seg: int, d_npoints: int, d_stop_code: int,
+                                   d_start_ray_vec: int, d_end_ray_vec: int, d_end_residuals: int, d_max_residuals: int,
+                                   stream: int = 0):
+    """rays_hip_trace_profiles_segments_device: trace_profiles_device with one profile per segment of rays -- d_profile_in
+    and d_profile of every record are [n_seg][n_bins]; d_seg_offsets: int32[n_seg + 1] on the device, or 0 / None with a
+    uniform rays_per_seg."""
+    arr = _profile_records(records)
+    ensure_tables(p)
+    rc = load().rays_hip_trace_profiles_segments_device(
+        C.byref(p), int(nray), d_rvec0 or None, d_rindex_vec0 or None, d_power or None, len(records), arr, int(n_seg),
+        d_seg_offsets or None, int(rays_per_seg), d_npoints or None, d_stop_code or None, d_start_ray_vec or None,
+        d_end_ray_vec or None, d_end_residuals or None, d_max_residuals or None, stream or None)
+    _check(rc, "rays_hip_trace_profiles_segments_device")
 
 
 def window_kernel_name(p: RaysParams, nray: int = 0, recording: bool = True) -> str:

@@ -183,11 +183,14 @@ class RayDeposition:
     n_bins: int
     grid_min: float
     grid_max: float
-    profile: np.ndarray          # [n_bins]   sum(work, 2) in ray order
+    profile: np.ndarray          # [n_bins]   sum(work, 2) in ray order ([n_seg][n_bins] of a trace with segments=)
     work: Optional[np.ndarray]   # [nray][n_bins]  the reference's work(n_bins, nray); None if not asked for
 
     @property
-    def Q_sum(self) -> float:    # the ordered sum of the profile (deposition_profiles_m.f90:251)
+    def Q_sum(self):             # the ordered sum of the profile (deposition_profiles_m.f90:251); one per segment
+        if np.ndim(self.profile) == 2:
+            return np.array([RayDeposition(self.summaries, self.profile_name, self.n_bins, self.grid_min, self.grid_max,
+                                           row, None).Q_sum for row in self.profile], dtype=np.float64)
         q = 0.0
         for x in self.profile:
             q = q + float(x)
@@ -259,6 +262,29 @@ def _profile_list(params: RaysParams, deposition, n_bins, who: str):
             raise ValueError(f"{who}: deposition profile {w!r} does not exist for this equilib_model (slab: Ptotal_x; "
                              "axisym_toroid: Ptotal_psi, Ptotal_rho)")
     return specs
+
+
+def check_segments(segments, nray: int, who: str):
+    """A `segments=` argument: (n_seg, offsets or None, rays_per_seg).  A host sequence of offsets is checked here --
+    non-decreasing, within 0..nray -- and returned as an int32 array; an int k means uniform segments of k rays, the last
+    one as long as the fan allows; an int32 torch tensor on the device is taken as it is (the kernel clamps what it reads)."""
+    if isinstance(segments, (int, np.integer)) and not isinstance(segments, bool):
+        k = int(segments)
+        if k < 1:
+            raise ValueError(f"{who}: segments={k}: a uniform segment holds at least one ray")
+        return (int(nray) + k - 1) // k, None, k
+    if hasattr(segments, "data_ptr"):
+        if str(segments.dtype) != "torch.int32" or segments.dim() != 1 or len(segments) < 1:
+            raise ValueError(f"{who}: segments= as a tensor is int32[n_seg + 1]")
+        return len(segments) - 1, segments, 0
+    off = np.asarray(segments)
+    if off.ndim != 1 or off.size < 1 or not np.issubdtype(off.dtype, np.integer):
+        raise ValueError(f"{who}: segments= is a sequence of n_seg + 1 integer offsets, or an int (rays per segment)")
+    if (np.diff(off) < 0).any():
+        raise ValueError(f"{who}: segments= offsets must be non-decreasing")
+    if off[0] < 0 or off[-1] > nray:
+        raise ValueError(f"{who}: segments= offsets must lie within 0..nray = {int(nray)}")
+    return off.size - 1, np.ascontiguousarray(off, dtype=np.int32), 0
 
 
 class WindowedDeposition:
@@ -542,11 +568,16 @@ class DeviceTrace:
     trajectories=False, deposition=[(which, n_bins), ...], ray_power=power: one or two profiles from ONE trace pass
     (rays_hip_trace_profiles_device) -- .works, .profiles and .deposition are lists in the order asked, profile_in a
     list of tensors / None of the same length, and results() returns a list of RayDeposition that share one
-    RaySummaries.  deposition="all", n_bins=n: the equilibrium's whole set (hip.deposition_profile_set)."""
+    RaySummaries.  deposition="all", n_bins=n: the equilibrium's whole set (hip.deposition_profile_set).
+    ... segments=offsets | int (with the list spelling): one profile per SEGMENT of rays -- the beams of an aiming survey
+    (rays_hip_trace_profiles_segments_device).  offsets: n_seg + 1 ray indices, segment s being the rays offsets[s] ..
+    offsets[s + 1] - 1 (a host sequence is checked: non-decreasing, within 0..nray); an int k: uniform segments of k
+    rays.  Every .profiles[i], profile_in[i] and RayDeposition.profile is then [n_seg][n_bins], and Q_sum has one value
+    per segment; .works are unchanged."""
 
     def __init__(self, params: RaysParams, rvec0, rindex_vec0, device=None, trajectories: bool = True, deposition=None,
                  profile_in=None, window: Optional[int] = None, state: Optional[RayState] = None, ray_power=None,
-                 n_bins: Optional[int] = None):
+                 n_bins: Optional[int] = None, segments=None):
         import torch
 
         self.torch = torch
@@ -560,6 +591,12 @@ class DeviceTrace:
         self.profile_in = profile_in
         self.works = self.profiles = None
         self.profile_list = deposition is not None and _is_profile_list(deposition)
+        self.segments = None
+        if segments is not None:
+            if not self.profile_list:
+                raise ValueError("DeviceTrace: segments= goes with the list spelling deposition=[(which, n_bins), ...] "
+                                 'or "all"')
+            self.segments = check_segments(segments, self.nray, "DeviceTrace")
         if self.profile_list:
             if self.trajectories:
                 raise ValueError("DeviceTrace: deposition=... is the fused trace without trajectories -- pass "
@@ -628,6 +665,13 @@ class DeviceTrace:
                 self.works = [torch.zeros((max(nb, 0), self.nray), dtype=f64, device=self.device)
                               for _, nb in self.deposition]
                 self.profiles = [torch.zeros(max(nb, 0), dtype=f64, device=self.device) for _, nb in self.deposition]
+                if self.segments is not None:
+                    n_seg, off, per = self.segments
+                    self.profiles = [torch.zeros((n_seg, max(nb, 0)), dtype=f64, device=self.device)
+                                     for _, nb in self.deposition]
+                    if off is not None:
+                        off = off.to(self.device).contiguous() if torch.is_tensor(off) else torch.as_tensor(off).to(self.device)
+                    self.segments = (n_seg, off, per)
             elif self.deposition is not None:
                 nb = max(self.deposition[1], 0)
                 pw = deposition[2]
@@ -647,6 +691,14 @@ class DeviceTrace:
             pin = self.profile_in or [None] * len(self.deposition)
             records = [(w, nb, work.data_ptr(), None if c is None else c.data_ptr(), prof.data_ptr())
                        for (w, nb), work, c, prof in zip(self.deposition, self.works, pin, self.profiles)]
+            if self.segments is not None:
+                n_seg, off, per = self.segments
+                hip.trace_profiles_segments_device(
+                    self.params, self.nray, self.rvec0.data_ptr(), self.rindex_vec0.data_ptr(), self.power.data_ptr(),
+                    records, n_seg, None if off is None else off.data_ptr(), per, self.npoints.data_ptr(),
+                    self.stop_code.data_ptr(), self.start_ray_vec.data_ptr(), self.end_ray_vec.data_ptr(),
+                    self.end_residuals.data_ptr(), self.max_residuals.data_ptr(), stream=stream)
+                return
             hip.trace_profiles_device(self.params, self.nray, self.rvec0.data_ptr(), self.rindex_vec0.data_ptr(),
                                       self.power.data_ptr(), records, self.npoints.data_ptr(), self.stop_code.data_ptr(),
                                       self.start_ray_vec.data_ptr(), self.end_ray_vec.data_ptr(),
