@@ -83,6 +83,17 @@
         type(c_ptr) :: work, profile_in, profile
     end type rays_dep_profile_t
 
+    ! The result block of the O-X conversion analysis (include/rays_hip.h: rays_ox_result_t): one array per field,
+    ! indexed by ray -- status, step_number, iterations (int32); alpha_max, conv_coeff; x_max, k_max, x_cut, nvecx_c,
+    ! nvecy_c, nvecz_c (3, nray); aux (5, nray) = cos_theta, gamma, L, ny_c, nz_c.  c_null_ptr: the field is not wanted.
+    integer(c_int32_t), parameter :: RAYS_OX_FOUND_MAX = 1, RAYS_OX_FOUND_CUTOFF = 2, RAYS_OX_CONVERTED = 4, &
+         & RAYS_OX_EQ_REFUSED = 8
+    integer(c_int), parameter :: RAYS_OX_NAUX = 5
+    type, bind(C) :: rays_ox_result_t
+        type(c_ptr) :: status, step_number, iterations
+        type(c_ptr) :: alpha_max, x_max, k_max, x_cut, conv_coeff, nvecx_c, nvecy_c, nvecz_c, aux
+    end type rays_ox_result_t
+
     type, bind(C) :: rays_params_t
         integer(c_int32_t) :: abi_version
         integer(c_int32_t) :: nv, nspec, nstep_max
@@ -596,6 +607,35 @@
           integer(c_int32_t), value :: fields
           type(c_ptr), value :: d_out, d_first_bad_point, hip_stream
        end function rays_hip_ray_diagnostics_packed_device
+
+       ! The post-processors' analyze_OX_conv (post_process_lib/OX_conv_analysis_m.f90:91-198) on the GPU: host arrays in
+       ! the reference's layouts in, the host arrays `res` points to out (one element per ray, vectors (3, nray), aux
+       ! (5, nray)); number_of_rays_converted and converted_ray_number(1:number_of_rays_converted), 1-based ray numbers in
+       ! ray order (fortran/ox_conv_analysis_hip.f90 is the caller)
+       integer(c_int) function rays_hip_ox_conv(p, nray, ray_vec, npoints, res, number_of_rays_converted, &
+                    & converted_ray_number) bind(C, name='rays_hip_ox_conv')
+          import :: c_int, c_int32_t, c_double, rays_params_t, rays_ox_result_t
+          type(rays_params_t), intent(in) :: p
+          integer(c_int), value :: nray
+          real(c_double), intent(in) :: ray_vec(*)
+          integer(c_int32_t), intent(in) :: npoints(*)
+          type(rays_ox_result_t), intent(in) :: res
+          integer(c_int32_t), intent(out) :: number_of_rays_converted
+          integer(c_int32_t), intent(inout) :: converted_ray_number(*)
+       end function rays_hip_ox_conv
+
+       ! The same on device arrays (include/rays_hip.h): in_layout = RAYS_DIAG_IN_PADDED (the trace's ray_vec, d_offsets
+       ! may be c_null_ptr) or RAYS_DIAG_IN_PACKED (ray_vec(nv, total) with d_offsets(0:nray)); `res` holds device
+       ! pointers; asynchronous on hip_stream
+       integer(c_int) function rays_hip_ox_conv_device(p, nray, in_layout, d_ray_vec, d_npoints, d_offsets, res, &
+                    & hip_stream) bind(C, name='rays_hip_ox_conv_device')
+          import :: c_int, c_ptr, rays_params_t, rays_ox_result_t
+          type(rays_params_t), intent(in) :: p
+          integer(c_int), value :: nray, in_layout
+          type(c_ptr), value :: d_ray_vec, d_npoints, d_offsets
+          type(rays_ox_result_t), intent(in) :: res
+          type(c_ptr), value :: hip_stream
+       end function rays_hip_ox_conv_device
 
        ! Replaces the serial launch loops of ray_init_m's launchers (solovev_ray_init_nphi_ntheta_m.f90:
        ! 60-198 etc.): fills rvec0(3,nray_max), rindex_vec0(3,nray_max), ray_pwr_wt(nray_max), nray.

@@ -852,6 +852,73 @@ int rays_hip_ray_diagnostics_packed_device(const rays_params_t* p, int nray, int
 int rays_hip_ray_diagnostics(const rays_params_t* p, int nray, const double* ray_vec, const double* residual,
                              const int32_t* npoints, uint32_t fields, double* out, int32_t* first_bad_point);
 
+/* ---- O-X mode conversion analysis on the device (the post-processors' analyze_OX_conv) -----------------
+ * Replaces the serial ray loop of post_process_lib/OX_conv_analysis_m.f90:91-198, which calls `equilibrium` at every
+ * recorded point of every ray until alpha = omega_pe**2/omega**2 first decreases.  Per ray:
+ *   find_x_max_ray (:202-252)     the first point j >= 2 with alpha(j) < alpha(j-1): step_number = j - 1, alpha_max,
+ *                                 x_max = ray_vec(1:3, j-1), k_max = ray_vec(4:6, j-1); none: no maximum
+ *   find_x_cutoff_ray (:256-311)  steepest ascent from x_max to abs(alpha - 1) <= 1e-4, at most 10 iterations, no step
+ *                                 longer than a quarter of the distance from the z axis; `iterations` is the
+ *                                 reference's `iteration` on exit: 1 .. 10, or 11 when no cutoff was found
+ *   OX_conv_coeff (:315-407)      unit vectors xc (along grad ne), yc, zc at x_cut; cos_theta = xc . bunit,
+ *                                 gamma = abs(gamma(0)), L = ne / |grad ne|; ny_c, nz_c and the vectors nvec*_c of
+ *                                 k_max / k0 in that frame; conv_coeff, Mjolhus' formula
+ *   converted                     conv_coeff > conversion_threshold = 0.0001 (a default-real literal)
+ * status holds RAYS_OX_FOUND_MAX, RAYS_OX_FOUND_CUTOFF, RAYS_OX_CONVERTED or, alone, RAYS_OX_EQ_REFUSED.
+ *   - A ray without a maximum holds the reference's zeros (:126-129) in every field.
+ *   - A ray with a maximum and no cutoff holds step_number, alpha_max, x_max, k_max, iterations = 11 and zeros
+ *     elsewhere (:143).
+ *   - A ray with a cutoff holds everything, CONVERTED or not: the reference stores conv_coeff and the three vectors of
+ *     converted rays only and leaves them UNDEFINED for the others; here they are the computed values.
+ *   - The reference never looks at equib_err in this module.  Here a ray for which `equilibrium` refuses a point the
+ *     analysis needs -- a recorded point up to and including the one that shows the first decrease (any point of a
+ *     ray without one), an ascent iterate, x_cut -- gets status = RAYS_OX_EQ_REFUSED and zeros in every other field.
+ *     Points behind the first decrease are never evaluated by the reference and influence nothing here.
+ * Everything but conv_coeff is bit-identical to the reference's arithmetic (products, sums, quotients, square roots;
+ * norm2, minval and dot_product as its compiler evaluates them).  conv_coeff passes through acos, sin and cos: the
+ * device-pointer form computes it with the device library's (within 1e-10 relative of the reference's per unit of the
+ * exponent, measured far below: DESIGN.md 4.11), the host-pointer form recomputes it on the host with libm from
+ * aux[5] and is bit-identical.  Exact arithmetic only: the numerics setting does not reach this analysis.  Built for
+ * the species counts and equilibria of the trace kernels; another shape is refused by name. */
+enum { RAYS_OX_FOUND_MAX = 1, RAYS_OX_FOUND_CUTOFF = 2, RAYS_OX_CONVERTED = 4, RAYS_OX_EQ_REFUSED = 8 };
+enum { RAYS_OX_AUX_COS_THETA = 0, RAYS_OX_AUX_GAMMA, RAYS_OX_AUX_L, RAYS_OX_AUX_NY_C, RAYS_OX_AUX_NZ_C, RAYS_OX_NAUX };
+/* One array per field, indexed by ray (0-based; vectors [nray][3], aux [nray][RAYS_OX_NAUX]).  A null pointer: the
+ * field is not wanted. */
+typedef struct rays_ox_result_t {
+  int32_t* status;
+  int32_t* step_number;  /* 1-based index of the point of x_max */
+  int32_t* iterations;
+  double* alpha_max;
+  double* x_max;
+  double* k_max;
+  double* x_cut;
+  double* conv_coeff;
+  double* nvecx_c;
+  double* nvecy_c;
+  double* nvecz_c;
+  double* aux;
+} rays_ox_result_t;
+/* Device-pointer form (current device, asynchronous on hip_stream): two kernels, a scan with one wave per ray that
+ * leaves at the chunk of 64 points holding the first decrease, and the ascent with one lane per ray.
+ *   in_layout   RAYS_DIAG_IN_PADDED: d_ray_vec[nray][nstep_max+1][nv] as the trace entries leave it, d_offsets unused
+ *               (may be NULL); RAYS_DIAG_IN_PACKED: d_ray_vec[total][nv] with d_offsets[nray + 1], the prefix sum of
+ *               the point counts (the point offsets entry above)
+ *   d_npoints   clamped to 0 .. nstep_max + 1 (packed: and to the ray's own run) whatever it holds
+ *   out         device pointers.  The call keeps 8 bytes per ray of its own per (device, stream). */
+int rays_hip_ox_conv_device(const rays_params_t* p, int nray, int in_layout, const double* d_ray_vec,
+                            const int32_t* d_npoints, const int64_t* d_offsets /* may be NULL (padded) */,
+                            const rays_ox_result_t* out, void* hip_stream);
+/* Host-pointer form: the ray_results_m arrays in (ray_vec[nray][nstep_max+1][nv], npoints[nray]), host arrays out.
+ * Blocking, on the CURRENT device, in blocks of rays of bounded device footprint (at most 2**21 trajectory slots; the
+ * environment variable RAYS_HIP_OX_BLOCK_RAYS sets the rays per block instead); only the points up to each ray's end
+ * are uploaded.  conv_coeff and RAYS_OX_CONVERTED are finished on the host with libm (bit-identical to the reference).
+ * *number_of_rays_converted and converted_ray_number[0 .. *number_of_rays_converted - 1] (1-based ray numbers in ray
+ * order, capacity nray) are the reference's compacted list; either may be NULL. */
+int rays_hip_ox_conv(const rays_params_t* p, int nray, const double* ray_vec, const int32_t* npoints,
+                     const rays_ox_result_t* out, int32_t* number_of_rays_converted, int32_t* converted_ray_number);
+/* The scan kernel's name for p's shape, "ox_scan_kernel<EQ, NS>"; "" (and the last-error text) when it is not built. */
+const char* rays_hip_ox_conv_kernel_name_for(const rays_params_t* p);
+
 /* Diagnostic entry used by the parity tests: evaluates equilibrium + deriv_cold + deriv_num +
  * eqn_ray + check_save at n states on the current device (host pointers; nv must be 7, nspec 1|2).
  * cold7/num7[n][7] = dddx(3) dddk(3) dddw; dvds[n][7]; resid[n]; codes[n][4] = equilibrium err,

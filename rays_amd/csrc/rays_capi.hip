@@ -375,6 +375,8 @@ StreamWorkspace g_step_ws;
 // rewritten on the stream before every launch that reads it.
 StreamWorkspace g_dep_ws;
 StreamWorkspace g_dep2_ws;   // the same for the Dep2TraceArgs block of a two-profile launch (rays_hip_trace_profiles*)
+StreamWorkspace g_post_ws;   // scratch of a post-processor that lives in a translation unit of its own (rays_oxconv.hip:
+                             // the scan's hand-over to the ascent, 8 bytes per ray; capi_stream_workspace)
 // A fused ds scan (rays_hip_scan_profiles_device) keeps its tiled power weights in the same block, kDepArgsRoom bytes
 // behind the argument block: one weight per ray of the launch.
 constexpr size_t kDepArgsRoom = 128;
@@ -558,7 +560,7 @@ int rays_hip_finalize(void) {
         if (e) (void)hipEventDestroy(e);
       g_ws[d] = DeviceWorkspace();
     }
-  for (StreamWorkspace* w : {&g_sg_ws, &g_sched_ws, &g_step_ws, &g_dep_ws, &g_dep2_ws}) w->release_all();
+  for (StreamWorkspace* w : {&g_sg_ws, &g_sched_ws, &g_step_ws, &g_dep_ws, &g_dep2_ws, &g_post_ws}) w->release_all();
   for (DeviceTable* t : std::initializer_list<DeviceTable*>{&g_zfun, &g_axi, &g_rho}) t->release_all();
   release_staging();
   release_cached_device_blocks();
@@ -825,6 +827,10 @@ extern "C++" {
 namespace rays {
 int capi_fail(const char* msg) { return fail(msg); }
 int capi_hip_fail(hipError_t e, const char* what) { return hip_fail(e, what); }
+int capi_stream_workspace(hipStream_t stream, size_t bytes, void** out) {
+  HIP_TRY_AS("hipMalloc (post-processor workspace)", g_post_ws.get(stream, bytes, out));
+  return 0;
+}
 int capi_dev_params(const rays_params_t* p, DevParams* D, bool* unit_exp) {
   int rc = rays_hip_check_params(p);
   if (rc) return rc;

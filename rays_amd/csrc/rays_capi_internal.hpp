@@ -17,4 +17,9 @@ int capi_hip_fail(hipError_t e, const char* what);
 // message set.
 int capi_dev_params(const rays_params_t* p, DevParams* D, bool* unit_exponents);
 
+// A device block of at least `bytes` for a post-processor's scratch on the current device: one block per (device,
+// stream), grown on demand, kept between calls and released by rays_hip_finalize (launches on a stream run one after
+// another, so they may share it).  0, or an error code with the message set.
+int capi_stream_workspace(hipStream_t stream, size_t bytes, void** out);
+
 }  // namespace rays

@@ -44,6 +44,7 @@ EXPORTED_SYMBOLS = (
     "rays_hip_window_kernel_name_for", "rays_hip_trace_windowed",
     "rays_hip_trace_window_profiles_device", "rays_hip_window_profiles_kernel_name_for",
     "rays_hip_profile_sum_segments_device", "rays_hip_scan_profiles_device", "rays_hip_trace_profiles_segments_device",
+    "rays_hip_ox_conv_device", "rays_hip_ox_conv", "rays_hip_ox_conv_kernel_name_for",
 )
 
 _lib = None
@@ -69,6 +70,20 @@ class DepProfileStruct(C.Structure):
 
 
 DEP_MAX_PROFILES = 2   # RAYS_DEP_MAX_PROFILES
+
+
+# rays_ox_result_t (include/rays_hip.h), in the struct's order: (field, numpy dtype, values per ray)
+OX_FIELDS = (("status", np.int32, 1), ("step_number", np.int32, 1), ("iterations", np.int32, 1), ("alpha_max", np.float64, 1),
+             ("x_max", np.float64, 3), ("k_max", np.float64, 3), ("x_cut", np.float64, 3), ("conv_coeff", np.float64, 1),
+             ("nvecx_c", np.float64, 3), ("nvecy_c", np.float64, 3), ("nvecz_c", np.float64, 3), ("aux", np.float64, 5))
+OX_AUX = ("cos_theta", "gamma", "L", "ny_c", "nz_c")             # RAYS_OX_AUX_*
+OX_FOUND_MAX, OX_FOUND_CUTOFF, OX_CONVERTED, OX_EQ_REFUSED = 1, 2, 4, 8   # RAYS_OX_*
+OX_CONVERSION_THRESHOLD = float(np.float32(0.0001))              # OX_conv_analysis_m.f90:32: a default-real literal
+
+
+class OxResultStruct(C.Structure):
+    """rays_ox_result_t (include/rays_hip.h): one pointer per field, null = not wanted"""
+    _fields_ = [(name, C.c_void_p) for name, _, _ in OX_FIELDS]
 
 
 def load():
@@ -236,6 +251,14 @@ def load():
         lib.rays_hip_ray_diagnostics_packed_device.restype = C.c_int
         lib.rays_hip_ray_diagnostics_packed_device.argtypes = [pp, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int64, C.c_uint32,
                                                                vp, vp, vp]
+    # (likewise rays_oxconv.hip)
+    if hasattr(lib, "rays_hip_ox_conv_device"):
+        lib.rays_hip_ox_conv_device.restype = C.c_int
+        lib.rays_hip_ox_conv_device.argtypes = [pp, C.c_int, C.c_int, vp, vp, vp, C.POINTER(OxResultStruct), vp]
+        lib.rays_hip_ox_conv.restype = C.c_int
+        lib.rays_hip_ox_conv.argtypes = [pp, C.c_int, dp, ip, C.POINTER(OxResultStruct), ip, ip]
+        lib.rays_hip_ox_conv_kernel_name_for.restype = C.c_char_p
+        lib.rays_hip_ox_conv_kernel_name_for.argtypes = [pp]
     _lib = lib
     return lib
 
@@ -549,6 +572,66 @@ def ray_diagnostics_host(p: RaysParams, ray_vec, residual, npoints, fields=None,
                 os.environ["RAYS_HIP_DIAG_BLOCK_RAYS"] = saved
     _check(rc, "rays_hip_ray_diagnostics")
     return {n: out[k] for k, n in enumerate(names)}, bad
+
+
+def ox_conv_kernel_name(p: RaysParams) -> str:
+    """The scan kernel of the O-X conversion analysis for p's shape; raises where it is not built (make FULL=1)."""
+    name = load().rays_hip_ox_conv_kernel_name_for(C.byref(p)).decode()
+    if not name:
+        raise RaysHipError("rays_hip_ox_conv_kernel_name_for: " + last_error())
+    return name
+
+
+def ox_conv_device(p: RaysParams, nray: int, d_ray_vec: int, d_npoints: int, out: dict, d_offsets: int = 0,
+                   packed_input: bool = False, stream: int = 0):
+    """rays_hip_ox_conv_device on device pointers: `out` maps field names of OX_FIELDS to device pointers (torch
+    `.data_ptr()`s); a field that is missing or None is not wanted.  d_ray_vec: the padded trace array, or with
+    packed_input the packed one with d_offsets[nray + 1].  Asynchronous on `stream`."""
+    ensure_tables(p)
+    unknown = [k for k in out if k not in [f for f, _, _ in OX_FIELDS]]
+    if unknown:
+        raise ValueError(f"ox_conv_device: unknown result fields {unknown}")
+    res = OxResultStruct(**{f: (int(out[f]) if out.get(f) else None) for f, _, _ in OX_FIELDS})
+    _check(load().rays_hip_ox_conv_device(C.byref(p), int(nray), DIAG_IN_PACKED if packed_input else DIAG_IN_PADDED,
+                                          d_ray_vec, d_npoints, d_offsets or None, C.byref(res), stream),
+           "rays_hip_ox_conv_device")
+
+
+def ox_conv_host(p: RaysParams, ray_vec, npoints, fields=None, block_rays: int = 0) -> dict:
+    """rays_hip_ox_conv: the ray_results_m arrays in; {field: array} for `fields` (names of OX_FIELDS; None = all) plus
+    "number_of_rays_converted" and "converted_ray_number" (1-based, in ray order) out.  conv_coeff and the CONVERTED bit
+    are the host libm's.  Blocking, on the current device.  block_rays > 0 is a TEST HOOK: rays per device block, handed
+    over by setting RAYS_HIP_OX_BLOCK_RAYS in os.environ around the call (not thread-safe)."""
+    ensure_tables(p)
+    known = [f for f, _, _ in OX_FIELDS]
+    fields = known if fields is None else list(fields)
+    unknown = [k for k in fields if k not in known]
+    if unknown:
+        raise ValueError(f"ox_conv_host: unknown result fields {unknown}; known: {known}")
+    ray_vec = np.ascontiguousarray(ray_vec, dtype=np.float64)
+    npoints = np.ascontiguousarray(npoints, dtype=np.int32)
+    nray, npt = len(npoints), p.nstep_max + 1
+    if ray_vec.shape != (nray, npt, p.nv):
+        raise ValueError("ox_conv_host: ray_vec does not have the ray_results_m shape of this run")
+    out = {f: np.zeros((nray, w) if w > 1 else nray, dtype=dt) for f, dt, w in OX_FIELDS if f in fields}
+    res = OxResultStruct(**{f: (out[f].ctypes.data if f in out else None) for f, _, _ in OX_FIELDS})
+    n_conv = C.c_int32(0)
+    conv = np.zeros(max(nray, 1), dtype=np.int32)
+    saved = os.environ.get("RAYS_HIP_OX_BLOCK_RAYS")
+    if block_rays:
+        os.environ["RAYS_HIP_OX_BLOCK_RAYS"] = str(int(block_rays))
+    try:
+        rc = load().rays_hip_ox_conv(C.byref(p), nray, _dp(ray_vec), _ip(npoints), C.byref(res), C.byref(n_conv), _ip(conv))
+    finally:
+        if block_rays:
+            if saved is None:
+                del os.environ["RAYS_HIP_OX_BLOCK_RAYS"]
+            else:
+                os.environ["RAYS_HIP_OX_BLOCK_RAYS"] = saved
+    _check(rc, "rays_hip_ox_conv")
+    out["number_of_rays_converted"] = int(n_conv.value)
+    out["converted_ray_number"] = conv[:n_conv.value].copy()
+    return out
 
 
 NO_KEPT_RESULT = 5   # RAYS_HIP_NO_KEPT_RESULT

@@ -6,6 +6,8 @@ in finalize_run, so that post_process_RAYS and graphics_RAYS consume a GPU run u
     read_results_LD / read_results_NC              the matching readers (425-600 / 253-361)
     write_deposition_profiles_LD / _NC  ->  deposition_profiles.<label>[.nc]   the post-processor's profile files
                                             (post_process_lib/deposition_profiles_m.f90:296-331, 336-420)
+    write_OX_conversion_data_LD  ->  OX_conv_data.<label>.dat   the post-processor's list of converted rays
+                                            (post_process_lib/OX_conv_analysis_m.f90:411-444), from an OXConversion
 
 The text writer reproduces the record layout the reference's own build produces (flang
 list-directed output: one leading blank per record, records of at most 79 columns, a shortest
@@ -22,6 +24,7 @@ writers run on the arrays the shim filled.  This module serves the Python mirror
 """
 from __future__ import annotations
 
+import dataclasses
 import datetime
 import decimal
 import math
@@ -162,6 +165,82 @@ def write_deposition_profiles_LD(path: str, profiles: Sequence[Dict[str, Any]]) 
         lines += reals([pr["Q_sum"]])
     with open(path, "w") as f:
         f.write("\n".join(lines) + "\n")
+
+
+@dataclasses.dataclass
+class OXConversion:
+    """analyze_OX_conv (post_process_lib/OX_conv_analysis_m.f90:91-198) of a fan: the per-ray arrays of
+    rays_ox_result_t (include/rays_hip.h), one entry per ray whether it converted or not, and the reference's compacted
+    list.  OX_conv_data(i) of the reference is entry converted_ray_number[i - 1] - 1 of every array."""
+
+    status: np.ndarray        # [nray] int32: hip.OX_FOUND_MAX | OX_FOUND_CUTOFF | OX_CONVERTED, or OX_EQ_REFUSED
+    step_number: np.ndarray   # [nray] int32: 1-based index of the point of x_max
+    iterations: np.ndarray    # [nray] int32
+    alpha_max: np.ndarray     # [nray]
+    x_max: np.ndarray         # [nray][3]
+    k_max: np.ndarray         # [nray][3]
+    x_cut: np.ndarray         # [nray][3]
+    conv_coeff: np.ndarray    # [nray]
+    nvecx_c: np.ndarray       # [nray][3]
+    nvecy_c: np.ndarray       # [nray][3]
+    nvecz_c: np.ndarray       # [nray][3]
+    aux: np.ndarray           # [nray][5]: cos_theta, gamma, L, ny_c, nz_c
+    number_of_rays_converted: int = 0
+    converted_ray_number: np.ndarray = None   # [number_of_rays_converted] int32, 1-based ray numbers in ray order
+
+    @classmethod
+    def from_fields(cls, fields: Dict[str, Any]) -> "OXConversion":
+        """from the dictionary hip.ox_conv_host returns"""
+        return cls(**{f.name: fields[f.name] for f in dataclasses.fields(cls)})
+
+
+def _norm2(v) -> float:
+    """norm2 as the reference's build evaluates it (flang's runtime: a running maximum m and the sum s of the squares of
+    the other elements over m; m * sqrt(1 + s))"""
+    m, s = 0.0, 0.0
+    for t in v:
+        a = abs(float(t))
+        if m == 0.0:
+            m = a
+        elif a > m:
+            q = m / a
+            s = s * (q * q) + q * q
+            m = a
+        else:
+            q = float(np.float64(a) / np.float64(m))
+            s = s + q * q
+    return m * math.sqrt(1.0 + s)
+
+
+def ox_conversion_file_name(run_label: str) -> str:
+    """'OX_conv_data.<label>.dat' (OX_conv_analysis_m.f90:425)"""
+    return "OX_conv_data." + str(run_label).strip() + ".dat"
+
+
+def write_OX_conversion_data_LD(path: str, ox: OXConversion) -> None:
+    """write_OX_conversion_data_LD (OX_conv_analysis_m.f90:411-444): one list-directed record group per CONVERTED ray,
+        'ray ', i, '  conv coeff = ', conv_coeff, 'nz_c = ', norm2(nvecz_c), 'ny_c = ', norm2(nvecy_c)
+    where i is the reference's loop index 1 .. number_of_rays_converted (the position in the compacted list, not the
+    ray number).  Same list-directed rules as write_results_LD: a blank in front of every item but a character item
+    that follows a character item, records of at most 79 columns."""
+    lines: List[str] = []
+    for i, ray in enumerate(np.asarray(ox.converted_ray_number, dtype=np.int64), start=1):
+        r = int(ray) - 1
+        lines += _records(["ray ", str(i), "  conv coeff = ", ld_real(ox.conv_coeff[r]), "nz_c = ",
+                           ld_real(_norm2(ox.nvecz_c[r])), "ny_c = ", ld_real(_norm2(ox.nvecy_c[r]))])
+    with open(path, "w") as f:
+        f.write("\n".join(lines) + ("\n" if lines else ""))
+
+
+def read_OX_conversion_data_LD(path: str) -> List[Dict[str, Any]]:
+    """The records of an OX_conv_data file: [{"index", "conv_coeff", "nz_c", "ny_c"}] (a record group may span lines)"""
+    import re
+    text = " ".join(open(path).read().split("\n"))
+    out = []
+    for m in re.finditer(r"ray\s+(\d+)\s+conv coeff =\s+(\S+)\s+nz_c =\s+(\S+)\s+ny_c =\s+(\S+)", text):
+        conv = lambda s: float(s.replace("D", "E").replace("d", "E"))
+        out.append(dict(index=int(m.group(1)), conv_coeff=conv(m.group(2)), nz_c=conv(m.group(3)), ny_c=conv(m.group(4))))
+    return out
 
 
 def _ld_values(tok: str) -> List[str]:

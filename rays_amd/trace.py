@@ -64,6 +64,14 @@ class RayResults:
         out["first_bad_point"] = bad
         return out
 
+    def ox_conversion(self, params: RaysParams):
+        """The post-processors' analyze_OX_conv (post_process_lib/OX_conv_analysis_m.f90:91-198) of these host arrays,
+        evaluated on the GPU (hip.ox_conv_host): a results.OXConversion with one entry per ray in every array and the
+        reference's compacted list of converted rays.  conv_coeff is the host libm's: bit-identical to the reference."""
+        from .results import OXConversion
+
+        return OXConversion.from_fields(hip.ox_conv_host(params, self.ray_vec, self.npoints))
+
     def _diagnostics_packed(self, params: RaysParams, fields) -> Dict[str, np.ndarray]:
         import torch
 
@@ -791,6 +799,32 @@ class DeviceTrace:
         res: Dict[str, Any] = {n: out[k] for k, n in enumerate(names)}
         res["first_bad_point"] = bad
         return res
+
+    def ox_conversion(self, fields=None) -> Dict[str, Any]:
+        """analyze_OX_conv of the trace as it lies on the device (hip.ox_conv_device): {field name: tensor} for
+        `fields` (names of hip.OX_FIELDS; None = all) -- status, step_number, iterations int32[nray]; alpha_max,
+        conv_coeff float64[nray]; x_max, k_max, x_cut, nvecx_c, nvecy_c, nvecz_c [nray][3]; aux [nray][5]
+        (hip.OX_AUX).  No trajectory leaves the device.  conv_coeff and the CONVERTED bit of status come from the
+        device library's acos / sin / cos (include/rays_hip.h); everything else is bit-identical to the reference.
+        Asynchronous on the current torch stream, behind launch()."""
+        t = self.torch
+        if self.window is not None:
+            raise RuntimeError("DeviceTrace.ox_conversion: a windowed trace holds one window of points, not the trajectories")
+        if not self.trajectories:
+            raise RuntimeError("DeviceTrace.ox_conversion: this trace is summary-only (trajectories=False) -- the analysis "
+                               "scans the recorded points; trace with trajectories=True")
+        known = [f for f, _, _ in hip.OX_FIELDS]
+        fields = known if fields is None else list(fields)
+        unknown = [f for f in fields if f not in known]
+        if unknown:
+            raise ValueError(f"DeviceTrace.ox_conversion: unknown fields {unknown}; known: {known}")
+        with t.cuda.device(self.device):
+            out = {f: t.empty((self.nray, w) if w > 1 else (self.nray,), dtype=t.int32 if dt is np.int32 else t.float64,
+                              device=self.device) for f, dt, w in hip.OX_FIELDS if f in fields}
+            hip.ox_conv_device(self.params, self.nray, self.ray_vec.data_ptr(), self.npoints.data_ptr(),
+                               {f: v.data_ptr() for f, v in out.items()},
+                               stream=t.cuda.current_stream(self.device).cuda_stream)
+        return out
 
     def results(self):
         if self.window is not None:
